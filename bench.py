@@ -16,11 +16,23 @@ N > 1 ranks, the single all-reduce of the flat gradient buffer).
 
 --scaling weak (default): every rank evaluates its own K samples (eps keyed by the global sample index): K * N samples per iteration.
 --scaling strong: the config's K is the job's total, split over the ranks (cfg3 as BASELINE states it: K = 32 over 4 GPUs).
-With N > 1 and the default weak mode the JSON line also carries a `strong_scaling` object (K total = the config's K) measured right after
-the timed region, so one driver run records both curves.
+With N > 1, --full and the default weak mode the JSON line also carries a `strong_scaling` object (K total = the config's K) measured right
+after the timed region, so one driver run records both curves.
 
 Prints ONE JSON line on rank 0.  Data are synthetic (seeded phantom + noise from the package's own generator), weights random-init;
 inputs are resident in HBM before the timed region.
+
+A plain run does only what the headline figure needs: set-up, --warmup iterations, the --steps timed iterations, the JSON line
+(metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds per timed iteration, ...).
+--full adds everything else the benchmark measures, in untimed work around the timed region: five instrumented iterations (per-kernel
+times, the dominant kernel's `roofline`, `bf16x6_kernels`, --profile-all's table), the forward-only and with-bookkeeping rates, the
+strong-scaling leg of an N > 1 weak run, `reference_cpu_probe`, and the unfused PyTorch-ROCm and CPU-oracle baselines.
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed iteration handed its caller as DIR/<name>.npy (float32 /
+float64, at most 64 MB in all; a fixed seeded sample of the largest arrays where they would not fit): `out` (the MC outputs of the
+iteration's last launch), `mu`, `rho`, `bn` (the parameters after the update; --mode dropin: `params`, every Parameter flattened),
+`grads` (the gradient buffer of the iteration) and `losses` ([nll, kl, loss], float64).  With the same arguments the inputs are the same
+from run to run, and so are the kernel tilings (configs/bench_tilings.json, see TILINGS): two runs of one build compute the same, and
+two builds can be compared output for output.
 """
 import argparse
 import json
@@ -281,8 +293,45 @@ def unfused_gpu_baseline(cfg, K, torch, steps=20, warmup=5, max_passes=480, devi
                 software="torch %s" % torch.__version__)
 
 
-def make_engine(cfg, K, rank, world, torch):
-    """Engine + synthetic target of a config, inputs from the package's own generator (runner.phantom)."""
+# Kernel tilings of the benchmark's plans, picked once by the autotuner on an MI355X (scripts/bench_tilings.py writes the file).  The
+# autotuner times the tilings of every layer in each run and, where two time alike, two runs may take different ones: different
+# summation orders, last-bit differences that the fit carries forward over the steps.  With the tilings from this table two runs with
+# the same arguments compute the same sums in the same order; `--autotune` restores the per-run search.
+TILINGS = os.path.join(ROOT, "configs", "bench_tilings.json")
+
+
+def plan_signature(prog, n):
+    """The key a plan's tilings are filed under: samples per launch + every op's shape (the MFVI_TUNE_CACHE key of program.Plan.autotune)."""
+    T = prog.tensors
+    return "%d:%s" % (n, ";".join("%d,%d,%d,%d>%d,%dx%d" % (o["type"], o["ksize"], o["stride"], T[o["in1"] if o["in0"] < 0 else o["in0"]]["C"],
+                                                            T[o["out"]]["C"], T[o["out"]]["H"], T[o["out"]]["W"]) for o in prog.ops))
+
+
+def plan_tilings(plan):
+    """{conv op index (str): [forward, backward-data, backward-weight tiling code]} of a plan as it stands (0 = built-in heuristic)."""
+    from mfvi_dip_mia_amd import _lib as L
+    lib = L.lib()
+    return {str(i): [max(lib.mfvi_plan_get_tune(plan.handle, i, w), 0) for w in range(3)] for i, o in enumerate(plan.prog.ops) if o["type"] == L.OP_CONV}
+
+
+def pin_tilings(plan, n):
+    """Sets the tilings of TILINGS on a plan of n samples per launch -> "table"; a plan the table lacks keeps the built-in heuristics
+    (deterministic as well) -> "heuristic".  No search runs."""
+    from mfvi_dip_mia_amd import _lib as L
+    with open(TILINGS) as f:
+        entry = json.load(f).get(plan_signature(plan.prog, n))
+    plan.tuned = True
+    if entry is None:
+        return "heuristic"
+    for i, tri in entry["tunes"].items():
+        for w, v in enumerate(tri):
+            L.check(L.lib().mfvi_plan_set_tune(plan.handle, int(i), w, int(v)))
+    return "table"
+
+
+def make_engine(cfg, K, rank, world, torch, autotune=False):
+    """Engine + synthetic target of a config, inputs from the package's own generator (runner.phantom).  Tilings from TILINGS, or
+    (autotune=True) from the autotuner's search in this run."""
     import numpy as np
     from mfvi_dip_mia_amd import _lib as L
     from mfvi_dip_mia_amd.engine import ElboEngine
@@ -290,7 +339,8 @@ def make_engine(cfg, K, rank, world, torch):
     S, hp, task = cfg["size"], cfg["hp"], cfg["task"]
     kw = dict(param_dtype=cfg["param_dtype"]) if "param_dtype" in cfg else {}
     eng = ElboEngine(S, S, task=task, K=K, input_depth=cfg["input_depth"], temp=hp["temp"], sigma=hp["sigma"], lr=hp["lr"], seed=hp["seed"],
-                     rank=rank, world_size=world, samples_per_launch=cfg.get("spl"), **kw)
+                     rank=rank, world_size=world, samples_per_launch=cfg.get("spl"), autotune=autotune, **kw)
+    eng.tilings = "autotuned" if autotune else pin_tilings(eng.plan, eng.chunk)
     rng = np.random.default_rng(hp["seed"] + 1)
     if task == "inp":
         img = np.stack([phantom(S, S, hp["seed"] + c) for c in range(3)])
@@ -315,7 +365,7 @@ class DropInLoop:
     (:1363-1364), net(z), gaussian_nll + temp * net.kl(), loss.backward(), optimizer.step().  K MC samples come from ONE call
     (MeanFieldVI(n_samples=K)); the reference's loop is K = 1.  Exposes what main() needs from an engine."""
 
-    def __init__(self, cfg, K, torch, flat=False):
+    def __init__(self, cfg, K, torch, flat=False, autotune=False):
         import numpy as np
         import mfvi_dip_mia_amd as M
         from mfvi_dip_mia_amd.runner import phantom
@@ -328,7 +378,7 @@ class DropInLoop:
         net = M.get_net(cfg["input_depth"], 'skip', 'reflection', 'bilinear', n_channels=2, skip_n33d=[16, 32, 64, 128, 128],
                         skip_n33u=[16, 32, 64, 128, 128], skip_n11=4, num_scales=5)
         self.net = M.MeanFieldVI(net, prior={'mu': 0.0, 'sigma': float(np.sqrt(hp["temp"]) * hp["sigma"])}, replace_layers='all', device=dev,
-                                 reparam='', n_samples=K, seed=hp["seed"], flat_parameters=flat)
+                                 reparam='', n_samples=K, seed=hp["seed"], flat_parameters=flat, autotune=autotune)
         self.opt = torch.optim.AdamW(self.net.parameters(), lr=hp["lr"], weight_decay=0)
         self.temp = hp["temp"]
         self.K_local = self.chunk = K
@@ -337,8 +387,9 @@ class DropInLoop:
         self.target = torch.from_numpy(np.clip(img + rng.normal(scale=hp["p_sigma"], size=img.shape), 0, 1).astype(np.float32)).to(dev)[None, None]
         self.z0 = 0.1 * torch.rand((1, cfg["input_depth"], S, S), device=dev)
         self.last = None
-        self.step()                                          # compiles (and autotunes) the plan of this input shape
+        self.step()                                          # compiles (and with autotune=True autotunes) the plan of this input shape
         self.plan = next(iter(self.net._plans.values()))
+        self.tilings = "autotuned" if autotune else pin_tilings(self.plan, K)
         self.prog = self.plan.prog
 
     def _loss(self, out):
@@ -356,6 +407,7 @@ class DropInLoop:
         loss.backward()
         self.opt.step()
         self.last = (nll.detach(), kl.detach(), loss.detach())
+        self.out = out.detach()
 
     def forward_only(self, step=0):
         with self.torch.no_grad():
@@ -367,6 +419,48 @@ class DropInLoop:
 
     def allreduce_ms(self):
         return None
+
+
+DUMP_BUDGET = 60 << 20           # bytes of array data --dump-outputs writes at most (64 MB in all with the .npy headers)
+
+
+def step_outputs(eng, torch):
+    """What the last iteration of `eng` handed its caller, as host arrays by name (--dump-outputs)."""
+    import numpy as np
+    nll, kl, loss = eng.losses()
+    outs = {"losses": np.array([nll, kl, loss], dtype=np.float64), "out": eng.out}
+    if isinstance(eng, DropInLoop):
+        ps = list(eng.net.parameters())
+        outs["params"] = torch.cat([p.detach().reshape(-1).float() for p in ps])
+        outs["grads"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in ps])
+    else:
+        mu, rho, bn = eng.params_f32()
+        outs.update(mu=mu, rho=rho, bn=bn, grads=eng.grads[:eng.n_params])
+    return {k: v.detach().float().cpu().numpy() if hasattr(v, "detach") else v for k, v in outs.items()}
+
+
+def write_outputs(outs, out_dir, budget=DUMP_BUDGET):
+    """DIR/<name>.npy for every array (float32 / float64).  Above `budget` bytes in all, the largest arrays are replaced by a fixed,
+    seeded sample of their flattened elements (sorted indices, the same for every build) until the set fits."""
+    import numpy as np
+    arrs = {}
+    for k, a in outs.items():
+        a = np.ascontiguousarray(a)
+        arrs[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    for k in sorted(arrs, key=lambda k_: (-arrs[k_].nbytes, k_)):
+        if total <= budget:
+            break
+        a = arrs[k].reshape(-1)
+        keep = max(1, a.size - -(-(total - budget) // a.itemsize))
+        idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+        total -= a.nbytes - keep * a.itemsize
+        arrs[k] = a[idx]
+        sys.stderr.write("bench.py: --dump-outputs: %s.npy holds a seeded sample of %d of its %d elements\n" % (k, keep, a.size))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return arrs
 
 
 def child_commands(n, argv, env, port=None):
@@ -426,8 +520,17 @@ def main():
     ap.add_argument("--graph", action="store_true", help="--mode engine, one GPU: capture one iteration into a HIP graph (device-resident step counters) and time its replays")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gpu-baseline", action="store_true", help="skip the unfused PyTorch-ROCm leg (SURVEY 8d's same-node row)")
-    ap.add_argument("--profile-all", action="store_true", help="print the per-kernel time table of one iteration to stderr")
+    ap.add_argument("--profile-all", action="store_true", help="with --full: print the per-kernel time table of one iteration to stderr")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline figure (instrumented iterations, roofline, "
+                    "forward-only / bookkeeping rates, strong-scaling leg, CPU and unfused PyTorch-ROCm baselines)")
+    ap.add_argument("--autotune", action="store_true", help="pick the kernel tilings by timing them in this run (MFVI_TUNE_CACHE honoured) "
+                    "instead of configs/bench_tilings.json; two runs may then differ in the last bits")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.profile_all and not args.full:
+        ap.error("--profile-all reads the instrumented iterations of --full: add --full")
     cfg = dict(CONFIGS[args.config])
     if args.size:
         cfg["size"] = args.size
@@ -465,74 +568,76 @@ def main():
     if args.mode == "dropin":
         if world > 1:
             sys.exit("--mode dropin runs on one GPU (the reference's loop has no sharding)")
-        eng = DropInLoop(cfg, K_total, torch, flat=args.flat_parameters)
+        eng = DropInLoop(cfg, K_total, torch, flat=args.flat_parameters, autotune=args.autotune)
     else:
-        eng = make_engine(cfg, K_total, rank, world, torch)
+        eng = make_engine(cfg, K_total, rank, world, torch, autotune=args.autotune)
 
     def barrier():
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- untimed: warm-up, then one fully instrumented iteration to find the dominant kernel ----
+    # ---- untimed: warm-up ----
     for _ in range(args.warmup):
         eng.step()
     torch.cuda.synchronize()
-    # (the instrumented iteration runs every kernel ALONE on the stream: in the timed region the backward-weight kernels overlap the
-    #  backward-data / concat chain on the plan's side stream, which stretches the launches that share the chip)
-    eng.plan.side_stream(False)
-    eng.plan.profile(1)
-    runs = []
-    for _ in range(5):          # five instrumented iterations, the median per kernel: one sample of a 100 us launch moves by 10 % from run to run
-        eng.step()
-        torch.cuda.synchronize()
-        one = {}
-        for op, ps_, ms in eng.plan.profile_read():
-            one[(op, ps_)] = one.get((op, ps_), 0.0) + ms
-        runs.append(one)
-    eng.plan.profile(0)
-    eng.plan.side_stream(True)
-    by = {k_: sorted(r_.get(k_, 0.0) for r_ in runs)[len(runs) // 2] for k_ in runs[0]}
-    n_launch = max(1, (eng.K_local + eng.chunk - 1) // eng.chunk)        # launches of a kernel per iteration (cfg5: 4)
-    (dom_op, dom_pass), dom_ms = max(((k_, v) for k_, v in by.items() if k_[1] in (0, 1, 2) and k_[0] >= 0 and conv_cost(eng.prog, k_[0], 1)), key=lambda kv: kv[1])
-    if args.profile_all and rank == 0:
-        tot = sum(by.values())
-        cls = {}
-        for (op, ps_), ms in by.items():
-            c = conv_cost(eng.prog, op, eng.chunk) if op >= 0 else None
-            kind = PASS_NAMES[ps_] + (" " + c["desc"].split(" ")[0] + ("/s2" if c["desc"].endswith("s2") else "") if c else "")
-            cls[kind] = cls.get(kind, 0.0) + ms
-        for kind, ms in sorted(cls.items(), key=lambda kv: -kv[1]):
-            sys.stderr.write("  %-22s %8.3f ms %5.1f%%\n" % (kind, ms, 100 * ms / tot))
-        for (op, ps_), ms in sorted(by.items(), key=lambda kv: -kv[1])[:(200 if os.environ.get('MFVI_PROFILE_FULL') else 24)]:
-            c = conv_cost(eng.prog, op, eng.chunk) if op >= 0 else None
-            ms1 = ms / n_launch
-            rate = "  %6.1f TFLOP/s %6.0f GB/s(alg)" % (c["flops"] / ms1 / 1e9, c["bytes"] / ms1 / 1e6) if c and ps_ in (0, 1, 2) else ""
-            sys.stderr.write("op %2d %-10s %8.3f ms %5.1f%%  %s%s\n" % (op, PASS_NAMES[ps_], ms, 100 * ms / tot, c["desc"] if c else ("all layers" if op < 0 else "concat_up"), rate))
-        sys.stderr.write("sum of kernel times in one iteration: %.3f ms\n" % tot)
+    by = dom_op = dom_pass = n_launch = fwd_only = with_book = None
+    if args.full:
+        # ---- --full, untimed: fully instrumented iterations to find the dominant kernel, forward-only and bookkeeping rates ----
+        # (the instrumented iteration runs every kernel ALONE on the stream: in the timed region the backward-weight kernels overlap the
+        #  backward-data / concat chain on the plan's side stream, which stretches the launches that share the chip)
+        eng.plan.side_stream(False)
+        eng.plan.profile(1)
+        runs = []
+        for _ in range(5):          # five instrumented iterations, the median per kernel: one sample of a 100 us launch moves by 10 % from run to run
+            eng.step()
+            torch.cuda.synchronize()
+            one = {}
+            for op, ps_, ms in eng.plan.profile_read():
+                one[(op, ps_)] = one.get((op, ps_), 0.0) + ms
+            runs.append(one)
+        eng.plan.profile(0)
+        eng.plan.side_stream(True)
+        by = {k_: sorted(r_.get(k_, 0.0) for r_ in runs)[len(runs) // 2] for k_ in runs[0]}
+        n_launch = max(1, (eng.K_local + eng.chunk - 1) // eng.chunk)        # launches of a kernel per iteration (cfg5: 4)
+        (dom_op, dom_pass), dom_ms = max(((k_, v) for k_, v in by.items() if k_[1] in (0, 1, 2) and k_[0] >= 0 and conv_cost(eng.prog, k_[0], 1)), key=lambda kv: kv[1])
+        if args.profile_all and rank == 0:
+            tot = sum(by.values())
+            cls = {}
+            for (op, ps_), ms in by.items():
+                c = conv_cost(eng.prog, op, eng.chunk) if op >= 0 else None
+                kind = PASS_NAMES[ps_] + (" " + c["desc"].split(" ")[0] + ("/s2" if c["desc"].endswith("s2") else "") if c else "")
+                cls[kind] = cls.get(kind, 0.0) + ms
+            for kind, ms in sorted(cls.items(), key=lambda kv: -kv[1]):
+                sys.stderr.write("  %-22s %8.3f ms %5.1f%%\n" % (kind, ms, 100 * ms / tot))
+            for (op, ps_), ms in sorted(by.items(), key=lambda kv: -kv[1])[:(200 if os.environ.get('MFVI_PROFILE_FULL') else 24)]:
+                c = conv_cost(eng.prog, op, eng.chunk) if op >= 0 else None
+                ms1 = ms / n_launch
+                rate = "  %6.1f TFLOP/s %6.0f GB/s(alg)" % (c["flops"] / ms1 / 1e9, c["bytes"] / ms1 / 1e6) if c and ps_ in (0, 1, 2) else ""
+                sys.stderr.write("op %2d %-10s %8.3f ms %5.1f%%  %s%s\n" % (op, PASS_NAMES[ps_], ms, 100 * ms / tot, c["desc"] if c else ("all layers" if op < 0 else "concat_up"), rate))
+            sys.stderr.write("sum of kernel times in one iteration: %.3f ms\n" % tot)
 
-    # forward-only rate (extra information, untimed region)
-    torch.cuda.synchronize(); t0 = time.perf_counter()
-    for i in range(5):
-        eng.forward_only(step=1000 + i)
-    torch.cuda.synchronize(); fwd_only = 5 * eng.K_local * world / (time.perf_counter() - t0)
-
-    # ELBO iterations WITH the reference loop's per-iteration bookkeeping (EMA, clips, ring buffers, 2 MSE + 3 PSNR + 3 SSIM:
-    # bayesian_optimization.py:1374-1406) — SURVEY 8(d)(ii) asks for the rate with and without it (extra information, untimed region)
-    with_book = None
-    if world == 1 and cfg["task"] == "den" and args.mode == "engine":
-        from mfvi_dip_mia_amd.runner import _Book, phantom
-        gt = phantom(S, S, cfg["hp"]["seed"])
-        book = _Book(eng, 16, gt, eng.target.cpu().numpy())
-        for i in range(3):
-            eng.step(after_forward=book.hook(eng, i, eng.chunk))
+        # forward-only rate (extra information, untimed region)
         torch.cuda.synchronize(); t0 = time.perf_counter()
-        for i in range(3, 13):
-            eng.step(after_forward=book.hook(eng, i, eng.chunk))
-        torch.cuda.synchronize(); with_book = 10 / (time.perf_counter() - t0)
-        book.wait()          # the side-stream bookkeeping has read eng.out before the timed steps overwrite it
+        for i in range(5):
+            eng.forward_only(step=1000 + i)
+        torch.cuda.synchronize(); fwd_only = 5 * eng.K_local * world / (time.perf_counter() - t0)
 
-    # ---- timed region: exactly --steps iterations, only the dominant kernel carries events ----
+        # ELBO iterations WITH the reference loop's per-iteration bookkeeping (EMA, clips, ring buffers, 2 MSE + 3 PSNR + 3 SSIM:
+        # bayesian_optimization.py:1374-1406) — SURVEY 8(d)(ii) asks for the rate with and without it (extra information, untimed region)
+        if world == 1 and cfg["task"] == "den" and args.mode == "engine":
+            from mfvi_dip_mia_amd.runner import _Book, phantom
+            gt = phantom(S, S, cfg["hp"]["seed"])
+            book = _Book(eng, 16, gt, eng.target.cpu().numpy())
+            for i in range(3):
+                eng.step(after_forward=book.hook(eng, i, eng.chunk))
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for i in range(3, 13):
+                eng.step(after_forward=book.hook(eng, i, eng.chunk))
+            torch.cuda.synchronize(); with_book = 10 / (time.perf_counter() - t0)
+            book.wait()          # the side-stream bookkeeping has read eng.out before the timed steps overwrite it
+
+    # ---- timed region: exactly --steps iterations; with --full the dominant kernel carries events, nothing else does ----
     def timed(e, steps):
         barrier()
         t0 = time.perf_counter()
@@ -576,16 +681,21 @@ def main():
         for _ in range(3):
             eng.step()
         graph_info = {"captured": True, "what": "one ELBO iteration (both streams of the plan) as ONE hipGraphLaunch; RNG step counter and Adam's update count read from device memory"}
-    eng.plan.profile(0 if args.graph else 2, dom_op, dom_pass)      # (a replayed graph carries no per-kernel events)
+    if args.full:
+        eng.plan.profile(0 if args.graph else 2, dom_op, dom_pass)      # (a replayed graph carries no per-kernel events)
     dt = timed(eng, args.steps)
-    recs = eng.plan.profile_read()
-    eng.plan.profile(0)
+    recs = []
+    if args.full:
+        recs = eng.plan.profile_read()
+        eng.plan.profile(0)
     nll, kl, loss = eng.losses()
+    if args.dump_outputs and rank == 0:
+        write_outputs(step_outputs(eng, torch), args.dump_outputs)
 
-    # second curve of a multi-GPU weak run: the config's K split over the ranks (untimed by the contract's value, reported beside it)
+    # --full: second curve of a multi-GPU weak run: the config's K split over the ranks (untimed by the contract's value, reported beside it)
     strong_extra = None
-    if world > 1 and not strong and k_strong % world == 0:
-        eng2 = make_engine(cfg, k_strong, rank, world, torch)
+    if args.full and world > 1 and not strong and k_strong % world == 0:
+        eng2 = make_engine(cfg, k_strong, rank, world, torch, autotune=args.autotune)
         eng2.set_allreduce_overlap(bool(overlap and overlap["used"]))
         for _ in range(max(args.warmup, 6)):      # a collective's first calls on a new buffer set up staging / channels (gloo: ~0.25 s once)
             eng2.step()
@@ -595,41 +705,6 @@ def main():
         del eng2
 
     if rank == 0:
-        kms = [ms for _, _, ms in recs]
-        avg_ms = sum(kms) / max(len(kms), 1) if kms else by[(dom_op, dom_pass)] / n_launch      # --graph: the instrumented iteration's duration
-        cost = conv_cost(eng.prog, dom_op, eng.chunk)
-        ai = cost["flops"] / cost["bytes"]
-        ridge = F32_PEAK_TFLOPS * 1e12 / (HBM_PEAK_GBS * 1e9)
-        if ai >= ridge:      # fp32 arithmetic: above the ridge the matrix/vector fp32 rate bounds the kernel
-            roof = dict(bound="mfma", achieved=cost["flops"] / (avg_ms * 1e-3) / 1e12, peak=F32_PEAK_TFLOPS, unit="TFLOP/s")
-        else:
-            roof = dict(bound="hbm", achieved=cost["bytes"] / (avg_ms * 1e-3) / 1e9, peak=HBM_PEAK_GBS, unit="GB/s")
-        roof["frac"] = roof["achieved"] / roof["peak"]
-        roof["traffic"] = None
-        # the same kernel timed alone (untimed instrumented iteration, side stream off): what the kernel achieves when it has the chip
-        iso_ms = by[(dom_op, dom_pass)] / n_launch
-        roof["alone"] = dict(avg_launch_ms=iso_ms, achieved=(cost["flops"] / 1e12 if roof["bound"] == "mfma" else cost["bytes"] / 1e9) / (iso_ms * 1e-3),
-                             frac=(cost["flops"] / 1e12 if roof["bound"] == "mfma" else cost["bytes"] / 1e9) / (iso_ms * 1e-3) / roof["peak"])
-        if world > 1 and backend != "nccl":      # the one-GPU rehearsal (MFVI_BENCH_BACKEND=gloo): the ranks share the chip, no kernel runs alone
-            roof["alone"] = None
-        roof["note"] = ("achieved/frac: launch duration inside the timed region, where the backward-weight kernels run on the plan's low-priority side "
-                        "stream and share the chip with the backward-data / concat chain of the caller's stream (the overlap shortens the "
-                        "iteration and stretches the individual launches); 'alone': the same kernel in untimed instrumented iterations (median of five), side "
-                        "stream off, chip to itself.  algorithmic_bytes counts the layer's input, output, mu and rho once; the sampled-weight slab "
-                        "the kernel actually reads its weights from ([K][n_vi] floats written once per pass by sample_weights_kernel, DESIGN.md §5) "
-                        "adds slab_bytes to what crosses HBM / L2")
-        o = eng.prog.ops[dom_op]
-        nw = eng.prog.tensors[o["out"]]["C"] * eng.prog.tensors[o["in0"]]["C"] * o["ksize"] ** 2 + eng.prog.tensors[o["out"]]["C"]
-        roof.update(kernel="%s of op %d: %s, %d samples/launch" % (PASS_NAMES[dom_pass], dom_op, cost["desc"], eng.chunk),
-                    avg_launch_ms=avg_ms, launches=len(kms), algorithmic_bytes=cost["bytes"], algorithmic_flops=cost["flops"], slab_bytes=4 * nw * eng.chunk,
-                    hbm_gbs_algorithmic=cost["bytes"] / (avg_ms * 1e-3) / 1e9, hbm_frac_algorithmic=cost["bytes"] / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
-        roof["traffic"] = traffic_lookup("%s:%s" % (PASS_NAMES[dom_pass], cost["desc"]))     # None unless measured on THIS build of the library
-        ic = iteration_cost(eng.prog, eng.K_local)
-        sec = dt / args.steps
-        roof["iteration"] = dict(algorithmic_flops=ic["flops"], algorithmic_bytes=ic["bytes"], tflops=ic["flops"] / sec / 1e12,
-                                 frac_of_f32_mfma_peak=ic["flops"] / sec / 1e12 / F32_PEAK_TFLOPS, hbm_gbs=ic["bytes"] / sec / 1e9,
-                                 frac_of_hbm_peak=ic["bytes"] / sec / 1e9 / HBM_PEAK_GBS,
-                                 note="whole ELBO iteration per GPU: conv FLOPs / bytes of 1 forward + 2 backward passes over K samples, KL, Adam")
         total_samples = eng.K_local * world * args.steps
         res = {
             "metric": "MC-forward-passes/sec (each inside a full ELBO iteration: fwd+data term+bwd+KL+Adam), %dx%d skip MFVI %s" % (S, S, cfg["task"]),
@@ -638,59 +713,95 @@ def main():
             "dtype": "f32" if cfg.get("param_dtype", "f32") == "f32" else "f32 arithmetic on bf16-stored mu/rho", "data": "synthetic",
             "config": {"workload": cfg["what"] + ("" if cfg["k"] == CONFIGS[args.config]["k"] else " [--k %d]" % cfg["k"]), "name": args.config,
                        "mc_samples_per_iteration": eng.K_local * world, "mc_samples_per_gpu": eng.K_local,
-                       "parallelism": "mc-sample sharding x%d, 1 all-reduce/iter" % world,
+                       "parallelism": "mc-sample sharding x%d, 1 all-reduce/iter" % world, "tilings": eng.tilings,
                        "mode": "engine: fused runner (ElboEngine), no autograd" if args.mode == "engine" else
                                "dropin: get_net + MeanFieldVI%s + gaussian_nll + net.kl() + loss.backward() + torch.optim.AdamW (INTEGRATION.md loop)" % ("(flat_parameters=True)" if args.flat_parameters else "")},
             "rccl_ranks": dist.get_world_size() if world > 1 else 1, "backend": backend if world > 1 else None,
-            "elbo_iters_per_sec": args.steps / dt, "elbo_iters_per_sec_with_bookkeeping": with_book, "fwd_only_mc_passes_per_sec": fwd_only,
-            "final_loss": loss, "final_nll": nll, "final_kl": kl,
-            "roofline": roof,
+            "elbo_iters_per_sec": args.steps / dt, "final_loss": loss, "final_nll": nll, "final_kl": kl,
         }
-        # convolutions that ran on the bf16 matrix instruction with three-way split fp32 operands (same fp32 results: DESIGN.md section 1)
-        try:
-            from mfvi_dip_mia_amd import _lib as L_
-            fam = lambda i, w: L_.lib().mfvi_plan_last_kernel(eng.plan.handle, i, w)
-            x6 = []
-            for i, o_ in enumerate(eng.prog.ops):
-                if o_["type"] != 1:
-                    continue
-                for which, ps_, n_ in ((0, 0, "fwd"), (1, 2, "bwd_data"), (2, 1, "bwd_weight")):       # (family query index, profile pass id)
-                    if fam(i, which) != 3:
-                        continue
-                    c = conv_cost(eng.prog, i, eng.chunk)
-                    e_ = {"kernel": "%s:%s" % (n_, c["desc"])}
-                    if (i, ps_) in by:       # duration alone on the chip, from the untimed instrumented iteration (side stream off)
-                        ms1 = by[(i, ps_)] / n_launch
-                        tf = c["flops"] / ms1 / 1e9
-                        e_.update(alone_ms=ms1, tflops=tf, frac_of_f32_mfma_peak=tf / F32_PEAK_TFLOPS, frac_of_bf16_peak_over_6=tf / (BF16_PEAK_TFLOPS / 6.0))
-                    x6.append(e_)
-            res["bf16x6_kernels"] = x6
-        except Exception:
-            res["bf16x6_kernels"] = None
         if graph_info:
             res["graph"] = graph_info
-        if strong_extra:
-            res["strong_scaling"] = strong_extra
         if world > 1:
             res["allreduce_ms"] = eng.allreduce_ms()        # mean time of the exchange on the caller's stream (HIP events); overlapped: what is left exposed
             res["allreduce_overlap"] = overlap
-        if cfg["task"] == "den" and S == 256:
-            res["reference_cpu_probe"] = REFERENCE_CPU_PROBE
-        k_local = eng.K_local
-        if world == 1 and not args.no_gpu_baseline:
+        if args.full:
+            res.update(elbo_iters_per_sec_with_bookkeeping=with_book, fwd_only_mc_passes_per_sec=fwd_only)
+            kms = [ms for _, _, ms in recs]
+            avg_ms = sum(kms) / max(len(kms), 1) if kms else by[(dom_op, dom_pass)] / n_launch      # --graph: the instrumented iteration's duration
+            cost = conv_cost(eng.prog, dom_op, eng.chunk)
+            ai = cost["flops"] / cost["bytes"]
+            ridge = F32_PEAK_TFLOPS * 1e12 / (HBM_PEAK_GBS * 1e9)
+            if ai >= ridge:      # fp32 arithmetic: above the ridge the matrix/vector fp32 rate bounds the kernel
+                roof = dict(bound="mfma", achieved=cost["flops"] / (avg_ms * 1e-3) / 1e12, peak=F32_PEAK_TFLOPS, unit="TFLOP/s")
+            else:
+                roof = dict(bound="hbm", achieved=cost["bytes"] / (avg_ms * 1e-3) / 1e9, peak=HBM_PEAK_GBS, unit="GB/s")
+            roof["frac"] = roof["achieved"] / roof["peak"]
+            roof["traffic"] = None
+            # the same kernel timed alone (untimed instrumented iteration, side stream off): what the kernel achieves when it has the chip
+            iso_ms = by[(dom_op, dom_pass)] / n_launch
+            roof["alone"] = dict(avg_launch_ms=iso_ms, achieved=(cost["flops"] / 1e12 if roof["bound"] == "mfma" else cost["bytes"] / 1e9) / (iso_ms * 1e-3),
+                                 frac=(cost["flops"] / 1e12 if roof["bound"] == "mfma" else cost["bytes"] / 1e9) / (iso_ms * 1e-3) / roof["peak"])
+            if world > 1 and backend != "nccl":      # the one-GPU rehearsal (MFVI_BENCH_BACKEND=gloo): the ranks share the chip, no kernel runs alone
+                roof["alone"] = None
+            roof["note"] = ("achieved/frac: launch duration inside the timed region, where the backward-weight kernels run on the plan's low-priority side "
+                            "stream and share the chip with the backward-data / concat chain of the caller's stream (the overlap shortens the "
+                            "iteration and stretches the individual launches); 'alone': the same kernel in untimed instrumented iterations (median of five), side "
+                            "stream off, chip to itself.  algorithmic_bytes counts the layer's input, output, mu and rho once; the sampled-weight slab "
+                            "the kernel actually reads its weights from ([K][n_vi] floats written once per pass by sample_weights_kernel, DESIGN.md §5) "
+                            "adds slab_bytes to what crosses HBM / L2")
+            o = eng.prog.ops[dom_op]
+            nw = eng.prog.tensors[o["out"]]["C"] * eng.prog.tensors[o["in0"]]["C"] * o["ksize"] ** 2 + eng.prog.tensors[o["out"]]["C"]
+            roof.update(kernel="%s of op %d: %s, %d samples/launch" % (PASS_NAMES[dom_pass], dom_op, cost["desc"], eng.chunk),
+                        avg_launch_ms=avg_ms, launches=len(kms), algorithmic_bytes=cost["bytes"], algorithmic_flops=cost["flops"], slab_bytes=4 * nw * eng.chunk,
+                        hbm_gbs_algorithmic=cost["bytes"] / (avg_ms * 1e-3) / 1e9, hbm_frac_algorithmic=cost["bytes"] / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
+            roof["traffic"] = traffic_lookup("%s:%s" % (PASS_NAMES[dom_pass], cost["desc"]))     # None unless measured on THIS build of the library
+            ic = iteration_cost(eng.prog, eng.K_local)
+            sec = dt / args.steps
+            roof["iteration"] = dict(algorithmic_flops=ic["flops"], algorithmic_bytes=ic["bytes"], tflops=ic["flops"] / sec / 1e12,
+                                     frac_of_f32_mfma_peak=ic["flops"] / sec / 1e12 / F32_PEAK_TFLOPS, hbm_gbs=ic["bytes"] / sec / 1e9,
+                                     frac_of_hbm_peak=ic["bytes"] / sec / 1e9 / HBM_PEAK_GBS,
+                                     note="whole ELBO iteration per GPU: conv FLOPs / bytes of 1 forward + 2 backward passes over K samples, KL, Adam")
+            res["roofline"] = roof
+            # convolutions that ran on the bf16 matrix instruction with three-way split fp32 operands (same fp32 results: DESIGN.md section 1)
             try:
-                del eng
-                torch.cuda.empty_cache()
-                res["unfused_gpu_baseline"] = unfused_gpu_baseline(cfg, K_total, torch)
-                res["unfused_gpu_baseline"]["speedup_of_this_path"] = res["unfused_gpu_baseline"]["ms_per_iteration"] / res["ms_per_step"]
-            except Exception as ex:      # a baseline leg must never take the benchmark line down
-                res["unfused_gpu_baseline"] = {"error": "%s: %s" % (type(ex).__name__, ex)}
-        if args.mode == "dropin":
-            res["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(cfg, min(cfg["cpu_samples"], 8 * max(1, k_local)))
-        elif world == 1 and not args.no_cpu_baseline and cfg["cpu_samples"]:
-            res["cpu_baseline"] = cpu_baseline(cfg, cfg["cpu_samples"])
-        elif world == 1 and not args.no_cpu_baseline:
-            res["cpu_baseline"] = None       # the oracle has no 5x5 / no-skip net driver: the inpainting variant is pinned by reference goldens only
+                from mfvi_dip_mia_amd import _lib as L_
+                fam = lambda i, w: L_.lib().mfvi_plan_last_kernel(eng.plan.handle, i, w)
+                x6 = []
+                for i, o_ in enumerate(eng.prog.ops):
+                    if o_["type"] != 1:
+                        continue
+                    for which, ps_, n_ in ((0, 0, "fwd"), (1, 2, "bwd_data"), (2, 1, "bwd_weight")):       # (family query index, profile pass id)
+                        if fam(i, which) != 3:
+                            continue
+                        c = conv_cost(eng.prog, i, eng.chunk)
+                        e_ = {"kernel": "%s:%s" % (n_, c["desc"])}
+                        if (i, ps_) in by:       # duration alone on the chip, from the untimed instrumented iteration (side stream off)
+                            ms1 = by[(i, ps_)] / n_launch
+                            tf = c["flops"] / ms1 / 1e9
+                            e_.update(alone_ms=ms1, tflops=tf, frac_of_f32_mfma_peak=tf / F32_PEAK_TFLOPS, frac_of_bf16_peak_over_6=tf / (BF16_PEAK_TFLOPS / 6.0))
+                        x6.append(e_)
+                res["bf16x6_kernels"] = x6
+            except Exception:
+                res["bf16x6_kernels"] = None
+            if strong_extra:
+                res["strong_scaling"] = strong_extra
+            if cfg["task"] == "den" and S == 256:
+                res["reference_cpu_probe"] = REFERENCE_CPU_PROBE
+            k_local = eng.K_local
+            if world == 1 and not args.no_gpu_baseline:
+                try:
+                    del eng
+                    torch.cuda.empty_cache()
+                    res["unfused_gpu_baseline"] = unfused_gpu_baseline(cfg, K_total, torch)
+                    res["unfused_gpu_baseline"]["speedup_of_this_path"] = res["unfused_gpu_baseline"]["ms_per_iteration"] / res["ms_per_step"]
+                except Exception as ex:      # a baseline leg must never take the benchmark line down
+                    res["unfused_gpu_baseline"] = {"error": "%s: %s" % (type(ex).__name__, ex)}
+            if args.mode == "dropin":
+                res["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(cfg, min(cfg["cpu_samples"], 8 * max(1, k_local)))
+            elif world == 1 and not args.no_cpu_baseline and cfg["cpu_samples"]:
+                res["cpu_baseline"] = cpu_baseline(cfg, cfg["cpu_samples"])
+            elif world == 1 and not args.no_cpu_baseline:
+                res["cpu_baseline"] = None       # the oracle has no 5x5 / no-skip net driver: the inpainting variant is pinned by reference goldens only
         print(json.dumps(res))
     if world > 1:
         dist.destroy_process_group()

@@ -9,5 +9,5 @@ for lib in "$@"; do
     MFVI_TUNE=$3 python3 scripts/bench_layer.py $1 $2 3 1 $5 $5 16 10 | grep -E "fwd" || true
     MFVI_TUNE=$4 python3 scripts/bench_layer.py $1 $2 3 1 $5 $5 16 10 | grep -E "bwd_data|bwd_weight" || true
   done
-  python3 bench.py --no-cpu-baseline --steps 30 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('ms_per_step', d['ms_per_step'], 'fwd_only', d['fwd_only_mc_passes_per_sec'], d['roofline']['alone'])"
+  python3 bench.py --full --no-cpu-baseline --steps 30 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('ms_per_step', d['ms_per_step'], 'fwd_only', d['fwd_only_mc_passes_per_sec'], d['roofline']['alone'])"
 done

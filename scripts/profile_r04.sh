@@ -13,16 +13,16 @@ cd "$(dirname "$0")/.." || exit 1
 OUT=gpurun_out/prof_r04; rm -rf $OUT; mkdir -p $OUT
 R=$(pwd)
 export MFVI_TUNE_CACHE=$R/$OUT/tunes_cfg2.json      # absolute: the profiled commands run from /tmp
-python3 bench.py > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err
-python3 bench.py --profile-all --no-cpu-baseline --no-gpu-baseline --steps 20 2> $OUT/kernel_table_cfg2.txt > /dev/null
+python3 bench.py --full > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err
+python3 bench.py --full --profile-all --no-cpu-baseline --no-gpu-baseline --steps 20 2> $OUT/kernel_table_cfg2.txt > /dev/null
 cd /tmp
 rm -rf /tmp/p_stats /tmp/p_fetch /tmp/p_write /tmp/p_trace      # (a reused box keeps /tmp: the copies below take the first match)
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stats -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-gpu-baseline > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stats -- python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-gpu-baseline > /dev/null 2>&1
 cp $(find /tmp/p_stats -name "*kernel_stats.csv" | head -1) $R/$OUT/kernel_stats_cfg2.csv
 python3 $R/scripts/timeline.py $(find /tmp/p_stats -name "*kernel_trace.csv" | head -1) > $R/$OUT/timeline.txt
-MFVI_SIDE_STREAM=0 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/p_fetch -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-gpu-baseline > /dev/null 2>&1
-MFVI_SIDE_STREAM=0 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d /tmp/p_write -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-gpu-baseline > /dev/null 2>&1
-MFVI_SIDE_STREAM=0 rocprofv3 --kernel-trace --output-format csv -d /tmp/p_trace -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-gpu-baseline > /dev/null 2>&1
+MFVI_SIDE_STREAM=0 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/p_fetch -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-gpu-baseline > /dev/null 2>&1
+MFVI_SIDE_STREAM=0 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d /tmp/p_write -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-gpu-baseline > /dev/null 2>&1
+MFVI_SIDE_STREAM=0 rocprofv3 --kernel-trace --output-format csv -d /tmp/p_trace -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-gpu-baseline > /dev/null 2>&1
 python3 $R/scripts/hbm_traffic.py /tmp/p_fetch /tmp/p_write /tmp/p_trace > $R/$OUT/pmc_hbm_traffic.txt 2>&1
 cd $R
 unset MFVI_TUNE_CACHE
@@ -41,17 +41,17 @@ python3 scripts/dev/x6_layers.py 36 16 256 68 32 128 132 64 64 132 128 32 > $OUT
 rm -f $OUT/pmc_sq_up7.txt; scripts/dev/pmc_sq.sh $OUT/pmc_sq_up7.txt 68 32 3 1 128 128
 echo "done x6 layers"
 export MFVI_TUNE_CACHE=$R/$OUT/tunes_cfg2_k1.json
-python3 bench.py --k 1 > $OUT/bench_cfg2_k1.json 2> /dev/null
-(cd /tmp && rm -rf /tmp/p_k1 && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_k1 -- python3 $R/bench.py --k 1 --steps 50 --warmup 3 --no-cpu-baseline --no-gpu-baseline > /dev/null 2>&1)
+python3 bench.py --full --k 1 > $OUT/bench_cfg2_k1.json 2> /dev/null
+(cd /tmp && rm -rf /tmp/p_k1 && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_k1 -- python3 $R/bench.py --full --k 1 --steps 50 --warmup 3 --no-cpu-baseline --no-gpu-baseline > /dev/null 2>&1)
 cp $(find /tmp/p_k1 -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_cfg2_k1.csv
 unset MFVI_TUNE_CACHE
-python3 bench.py --mode dropin --k 1 > $OUT/bench_dropin.json 2> /dev/null
-python3 bench.py --mode dropin --k 1 --flat-parameters --no-cpu-baseline > $OUT/bench_dropin_flat.json 2> /dev/null
+python3 bench.py --full --mode dropin --k 1 > $OUT/bench_dropin.json 2> /dev/null
+python3 bench.py --full --mode dropin --k 1 --flat-parameters --no-cpu-baseline > $OUT/bench_dropin_flat.json 2> /dev/null
 echo "done k1 / dropin"
 for c in cfg1 cfg3 cfg4 cfg5 inp; do
   export MFVI_TUNE_CACHE=$R/$OUT/tunes_$c.json
-  python3 bench.py --config $c > $OUT/bench_$c.json 2> /dev/null
-  (cd /tmp && rm -rf /tmp/p_$c && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$c -- python3 $R/bench.py --config $c --steps 10 --warmup 2 --no-cpu-baseline --no-gpu-baseline > /dev/null 2>&1)
+  python3 bench.py --full --config $c > $OUT/bench_$c.json 2> /dev/null
+  (cd /tmp && rm -rf /tmp/p_$c && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$c -- python3 $R/bench.py --full --config $c --steps 10 --warmup 2 --no-cpu-baseline --no-gpu-baseline > /dev/null 2>&1)
   cp $(find /tmp/p_$c -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_$c.csv
   echo "done $c"
 done
