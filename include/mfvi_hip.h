@@ -342,6 +342,34 @@ int mfvi_ring_stats(const float* ring, int R, int H, int W, float* var_out, floa
 /* post-step output handling: mean[n][HW] kept, out[:,1] <- exp(-out[:,1]); ema = ema*w + out*(1-w) (first: copy) */
 int mfvi_post_step(float* out, int n, int C, int H, int W, float* ema, float ema_weight, int first, void* stream);
 
+/* ---- posterior predictive statistics (BayTorch/inference/utils.py:11-24 uncert_regression_gal) ----------- */
+/* N draws y_k[C][H][W] of the fitted net map to image channels m_k[c] and an aleatoric variance a_k by `mode`:
+ *   MFVI_PRED_RAW        C >= 2: m = y[0..C-2], a = y[C-1]            (uncert_regression_gal's input: the last channel already a variance)
+ *   MFVI_PRED_LOGPREC    C == 2: m = y[0], a = exp(-y[1])             (den / SR: bayesian_optimization.py:1376-1377)
+ *   MFVI_PRED_INP        C == 4: m = sigmoid(y[0..2]), a = exp(-y[3]) (inpainting: bayesian_optimization.py:3039-3041)
+ *   MFVI_PRED_MEAN_ONLY  C == 1: m = y[0], no a                       (CT)
+ * clip = 1 clips m_k and a_k to [0, 1] per draw (what the runner's ring stores). */
+#define MFVI_PRED_RAW 0
+#define MFVI_PRED_LOGPREC 1
+#define MFVI_PRED_INP 2
+#define MFVI_PRED_MEAN_ONLY 3
+/* length in doubles of the accumulator: [sum m (Cimg*H*W) | sum m^2 (Cimg*H*W) | sum a (H*W; not in MEAN_ONLY) | finalize partials];
+ * -1 for an invalid (C, mode).  Only the part before the partials carries state between calls (what a K-sharded job all-reduces):
+ * (2*Cimg + has_ale)*H*W doubles. */
+int64_t mfvi_predictive_acc_doubles(int C, int H, int W, int mode);
+/* Fold one chunk out[n][C][H][W] (fp32, contiguous) into the accumulator (uncert_regression_gal's sums over img_list, utils.py:13-16):
+ * first = 1 overwrites instead of adding (no zeroing launch).  Every pixel adds its samples in increasing k, so the sums over several
+ * calls are bit-identical for any chunking of the same draws.  No atomics. */
+int mfvi_predictive_accumulate(const float* out, int n, int C, int H, int W, int mode, int clip, int first, double* acc, void* stream);
+/* The maps of utils.py:13-24 from the sums of n_total >= 2 draws (fp32 [H][W] unless noted): mean [Cimg][H][W] = sum m / N;
+ * epi = mean over c of the unbiased variance (clamped at >= 0); ale = sum a / N (NULL in MEAN_ONLY); total = ale + epi.  With a ground
+ * truth ref [Cimg][H][W] (else NULL): err2 = mean_c (mean[c] - ref[c])^2 and mse_mc = err2 + (N-1)/N * epi, the per-pixel
+ * (1/N) sum_k mean_c (m_k[c] - ref[c])^2 of the evaluation notebooks' uceloss input (err2 / mse_mc may be NULL).  sums: 3 device
+ * doubles, overwritten with sum ale, sum epi, sum total over the pixels (reduction 'sum'; / (H*W) is 'mean'), reduced in a fixed
+ * order (per-block partials in the accumulator's tail, then one block): deterministic. */
+int mfvi_predictive_finalize(double* acc, int n_total, int C, int H, int W, int mode, const float* ref, float* mean, float* epi, float* ale,
+                             float* total, float* err2, float* mse_mc, double* sums, void* stream);
+
 const char* mfvi_last_error(void);
 int mfvi_abi_version(void);
 

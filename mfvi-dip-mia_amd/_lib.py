@@ -9,6 +9,7 @@ LIB_PATH = os.environ.get("MFVI_LIB_PATH") or os.path.join(HERE, "libmfvi_hip.so
 OP_CONV, OP_CONCAT_UP, OP_CONV_LRT = 1, 2, 3
 DOMAIN_EPS, DOMAIN_INPUT, DOMAIN_INIT, DOMAIN_UNIFORM, DOMAIN_SGLD, DOMAIN_DROPOUT, DOMAIN_ROUND, DOMAIN_LRT = 0, 1, 2, 3, 4, 5, 6, 7
 PARAM_F32, PARAM_BF16 = 0, 1
+PRED_RAW, PRED_LOGPREC, PRED_INP, PRED_MEAN_ONLY = 0, 1, 2, 3             # MFVI_PRED_* (posterior predictive statistics)
 
 
 class TensorDesc(C.Structure):
@@ -85,6 +86,9 @@ SIGNATURES = {
     "mfvi_bookkeep_inpainting": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfvi_ring_stats": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "mfvi_post_step": (_I, [_P, _I, _I, _I, _I, _P, _F, _I, _P]),
+    "mfvi_predictive_acc_doubles": (_I64, [_I, _I, _I, _I]),
+    "mfvi_predictive_accumulate": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "mfvi_predictive_finalize": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfvi_last_error": (C.c_char_p, []),
     "mfvi_abi_version": (_I, []),
 }

@@ -449,6 +449,51 @@ class MeanFieldVI(nn.Module):
             self._step += 1                  # fresh eps / dropout masks for every call, like randn_like in VIModule.rsample
         return out, (self._token, plan, x3, step, sample, bn_eval)
 
+    def predictive(self, x, n_samples, mode=None, target=None, clip=False, step=None):
+        """Posterior predictive sampling through the module's plan: n_samples forwards of the current posterior on
+        x, drawn in launches of self.n_samples with consecutive global sample indices at RNG step `step` (default 2**31), reduced on the
+        device like uncert_regression_gal (BayTorch/inference/utils.py:11-24).  mode: 'raw' | 'logprec' | 'inp' | 'mean_only' (default by
+        the output channels: 1 -> mean_only, 2 -> logprec, 4 -> inp).  Returns {mean [Cimg,H,W], epi, ale | None, total, err2 | None,
+        mse_mc | None, n, step}.  BatchNorm / Dropout2d / weight sampling follow the module's mode as in forward(); the forward counter,
+        the BN running statistics and the next forward's draw are left as they were.  The plan's workspace is reused: a backward of an
+        earlier forward is refused afterwards."""
+        from .predictive import Accumulator, DEFAULT_STEP, default_mode
+        N = int(n_samples)
+        if N < 2:
+            raise ValueError("posterior predictive statistics need at least 2 samples, got n_samples=%d" % N)
+        if x.dim() == 4:
+            if x.shape[0] != 1:
+                raise NotImplementedError("batch size %d: the deep-image-prior nets run on one image (batch 1)" % x.shape[0])
+            x = x[0]
+        x3 = x.contiguous().float()
+        if not x3.is_cuda:
+            raise NotImplementedError("this implementation runs on the GPU only; there is no CPU path")
+        cin, H, W = x3.shape
+        plan = self._plan_for(cin, H, W, self.n_samples)
+        mu, rho, bn = self._blocks()
+        if self._autotune and not getattr(plan, "tuned", False):
+            plan.autotune(mu, rho, bn, x3, self.n_samples)
+        mode = default_mode(plan.out_shape[0]) if mode is None else mode
+        step = DEFAULT_STEP if step is None else int(step)
+        sample = bool(self.training and self._sampling)
+        if self._drops:
+            L.check(L.lib().mfvi_plan_set_dropout(plan.handle, int(any(d.training for d in self._drops))))
+        if self._bn and not self._running_intact():
+            self._bind_running()
+        bn_eval = bool(self._bn) and not self._bn[0].training
+        L.check(L.lib().mfvi_plan_set_bn_eval(plan.handle, L.ptr(self._running) if bn_eval else None))
+        acc = Accumulator(plan.out_shape[0], H, W, mode)
+        out = torch.empty((self.n_samples,) + plan.out_shape, dtype=torch.float32, device=self.device)
+        self._token += 1                     # the workspace is overwritten: a backward of an earlier forward must fail
+        for k0 in range(0, N, self.n_samples):
+            n = min(self.n_samples, N - k0)
+            plan.forward(mu, rho, bn, x3, self.seed, step, k0, n, sample, out)
+            acc.add(out, n, clip)
+        r = acc.finalize(N, target)
+        r.pop("sums")
+        r.update(n=N, step=step)
+        return r
+
     def _check_token(self, token):
         """The forward a backward call belongs to must be the latest one (one workspace per plan) and a training-mode one."""
         tok, plan, x3, step, sample, bn_eval = token
@@ -636,6 +681,9 @@ class FusedNet(MeanFieldVI):
             raise ValueError("a deterministic net has nothing to sample")
         return self
 
+    def predictive(self, *a, **kw):
+        raise NotImplementedError("posterior predictive sampling is built for MeanFieldVI and the engines; FusedNet holds point weights")
+
     def _hip_backward(self, token, dout, want_dz):
         plan, x3, step, sample = self._check_token(token)
         mu, rho, bn = self._blocks()
@@ -690,6 +738,32 @@ class _GaussianNLL(torch.autograd.Function):
         L.check(L.lib().mfvi_gaussian_nll_tensors_backward(L.ptr(mu_c), L.ptr(s_c), L.ptr(t_c), L.ptr(m_c), C, Cs, Cm, hw, mean,
                                                            L.ptr(g.reshape(1).contiguous().float()), L.ptr(dmu), L.ptr(ds), L.stream_ptr()))
         return dmu.view(mu_shape), ds.view(s_shape), None, None, None
+
+
+def uncert_regression_gal(img_list, reduction='mean'):
+    """Drop-in for BayTorch/inference/utils.py:11-24 on the HIP kernels (mfvi_predictive_*, mode 'raw'): img_list is a list of
+    (1, C, H, W) CUDA tensors whose last channel is already a variance.  -> (ale, epi, uncert): Python floats for reduction 'mean' /
+    'sum', otherwise detached (1, 1, H, W) tensors.  ale = sample mean of the last channel, epi = unbiased variance over the samples
+    averaged over the image channels, uncert = ale + epi."""
+    from .predictive import Accumulator
+    x = torch.cat([t.detach() for t in img_list], dim=0)
+    if not x.is_cuda:
+        raise NotImplementedError("this implementation runs on the GPU only; there is no CPU path")
+    if x.dim() != 4 or x.shape[1] < 2:
+        raise NotImplementedError("uncert_regression_gal needs (1, C >= 2, H, W) samples (image channels + one variance channel), got %s"
+                                  % (tuple(x.shape),))
+    N, C, H, W = x.shape
+    if N < 2:
+        raise ValueError("the unbiased variance over samples needs at least 2 samples, got %d" % N)
+    x = x.float().contiguous()
+    acc = Accumulator(C, H, W, "raw")
+    acc.add(x, N)
+    r = acc.finalize(N)
+    if reduction in ('mean', 'sum'):
+        s = r["sums"].cpu().tolist()
+        d = float(H * W) if reduction == 'mean' else 1.0
+        return s[0] / d, s[1] / d, s[2] / d
+    return r["ale"].view(1, 1, H, W), r["epi"].view(1, 1, H, W), r["total"].view(1, 1, H, W)
 
 
 def _reduction(reduction):

@@ -86,6 +86,8 @@ class ElboEngine:
         self._graph = None
         self.target = None
         self.sample_weights = True       # w = mu + softplus(rho) * eps; the non-Bayesian siblings run w = mu
+        self._autotune = bool(autotune)
+        self._pred_plans = {}            # predict(): chunk size -> (forward plan, output buffer), apart from the training plan
         self.init_params()
         if autotune:      # one-time: pick the fastest kernel tiling per layer on this device (results unchanged)
             self.plan.autotune(self.mu, self.rho, self.bn, self.z0, self.chunk)
@@ -134,6 +136,58 @@ class ElboEngine:
             self.plan.forward(self.mu, self.rho, self.bn, self.z if perturb else self.z0, self.seed, step, self.k0 + c0, n, self.sample_weights,
                               self.out)
         return self.out
+
+    def _pred_plan(self, chunk):
+        """The forward plan (and output buffer) of predict() for launches of `chunk` samples: its own workspace, sampled-weight slab and
+        step counter (always the host value), so prediction never touches the training plan's state or self.out."""
+        if chunk not in self._pred_plans:
+            plan = self.prog.compile(self.zin, self.zout, chunk, param_dtype=self.param_dtype)
+            if self._autotune:
+                import os
+                cache = os.environ.get("MFVI_TUNE_CACHE")      # a file of its own: the training plan's entry in the cache stays
+                plan.autotune(self.mu, self.rho, self.bn, self.z0, chunk, cache=cache + ".predict%d" % chunk if cache else None)
+            out = self.torch.empty((chunk,) + plan.out_shape, dtype=self.torch.float32, device="cuda")
+            self._pred_plans[chunk] = (plan, out)
+        return self._pred_plans[chunk]
+
+    def predict(self, n_samples, target=None, clip=False, step=None, chunk=None, z=None):
+        """Posterior predictive sampling (BayTorch/inference/utils.py:11-24 uncert_regression_gal over N draws of the fit, DESIGN.md
+        section 11): N forwards y_k = net_k(z) with the current mu / rho / BN, eps keyed by the GLOBAL sample index k at RNG step
+        `step` (default 2**31: no training iteration's draw is reused), reduced on the device into
+            {mean [Cimg,H,W], epi [H,W], ale [H,W] | None, total [H,W], err2 | None, mse_mc | None, n, step}
+        with the task's transform (den / sr: m = y0, a = exp(-y1); inp: m = sigmoid(y0..2), a = exp(-y3); ct: m = y0, no ale).
+        target: the clean image ([H,W]; inp [3,H,W]; sr at the high resolution) for err2 = mean_c (mean - g)^2 and
+        mse_mc = err2 + (N-1)/N epi.  clip: clip m_k, a_k to [0,1] per draw (what the runner's ring stores).  z: the input (default z0,
+        no perturbation).  With world_size > 1 the N draws are sharded like K and the fp64 sums all-reduced once.  Leaves the fit's
+        state (params, Adam moments, counters, self.out) untouched."""
+        from .predictive import Accumulator, DEFAULT_STEP
+        torch = self.torch
+        N = int(n_samples)
+        if N < 2:
+            raise ValueError("posterior predictive statistics need at least 2 samples, got n_samples=%d" % N)
+        k0, n_local = shard_samples(N, self.rank, self.world)
+        chunk = int(chunk) if chunk else min(n_local, max(self.chunk, 16))
+        if chunk < 1:
+            raise ValueError("chunk=%d" % chunk)
+        step = DEFAULT_STEP if step is None else int(step)
+        if not 0 <= step < 2 ** 32:
+            raise ValueError("step %d outside the 32-bit counter word" % step)
+        zin = self.z0 if z is None else z.to(device="cuda", dtype=torch.float32).contiguous()
+        if zin.numel() != self.z0.numel():
+            raise ValueError("input of %d elements, expected %s" % (zin.numel(), tuple(self.z0.shape)))
+        mode = {TASK_CT: "mean_only", TASK_INP: "inp"}.get(self.task, "logprec")
+        plan, out = self._pred_plan(chunk)
+        acc = Accumulator(out.shape[1], self.H, self.W, mode)
+        for c0 in range(0, n_local, chunk):
+            n = min(chunk, n_local - c0)
+            plan.forward(self.mu, self.rho, self.bn, zin, self.seed, step, k0 + c0, n, self.sample_weights, out)
+            acc.add(out, n, clip)
+        if self.world > 1:
+            allreduce_sum_(acc.state, self.pg)
+        r = acc.finalize(N, target)
+        r.pop("sums")
+        r.update(n=N, step=step)
+        return r
 
     def _perturb(self, step):
         lib, sp = L.lib(), L.stream_ptr()
@@ -406,6 +460,15 @@ class SiblingEngine(ElboEngine):
                                                 1.0 / self.K, L.ptr(self.dout), L.ptr(self.acc), sp))
         else:                                                    # gaussian_nll / radon MSE / masked NLL as in the MFVI runners
             super()._loss_and_dout(n)
+
+    def predict(self, n_samples, **kw):
+        """mcd: posterior predictive sampling with the Dropout2d masks (w = mu; masks keyed by seed, step, global sample, layer).
+        dip has no posterior to sample; SGLD's posterior samples are its iterates (the runner's ring)."""
+        if self.method == METHOD_DIP:
+            raise ValueError("the plain deep image prior (method 'dip') is deterministic: there is no posterior to sample")
+        if self.method == METHOD_SGLD:
+            raise NotImplementedError("SGLD's posterior samples are its iterates (the runner's ring buffer), not draws of one network")
+        return super().predict(n_samples, **kw)
 
     def add_noise(self, step):
         """add_noise(net, param_noise_sigma, LR): 4-D parameters (the conv weights) only, std = sigma * lr0 (RNG domain 4)."""

@@ -23,6 +23,7 @@ from . import artifacts as A
 from .engine import ElboEngine, SiblingEngine
 
 MC_ITER = 25            # ring-buffer length (bayesian_optimization.py:1314)
+PREDICT_METHODS = ("mfvi", "mcd")      # methods whose fit is a posterior predict_samples can draw from (engine.ElboEngine.predict)
 EXP_WEIGHT = 0.99       # EMA weight (:1292)
 
 
@@ -218,9 +219,29 @@ def _make_engine(method, H, W, task, K, input_depth, temp, sigma, lr, seed, net_
     return SiblingEngine(H, W, method=method, task=task, K=K, input_depth=input_depth, lr=lr, seed=seed, net_kwargs=net_kwargs, **sib, **kw)
 
 
-def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, seed, show_every, plot, save, save_path, K, factor=4,
-         theta_step=4.0, verbose=False, net_kwargs=None, method="mfvi", weight_decay=0.0, dropout_p=0.3, gamma=0.996, param_dtype="f32", **unused):
+def _check_predict(method, predict_samples):
+    if predict_samples and method not in PREDICT_METHODS:
+        raise ValueError("predict_samples=%d: posterior predictive sampling needs a posterior to draw from (mfvi, mcd), not %r"
+                         % (predict_samples, method))
+    if predict_samples and predict_samples < 2:
+        raise ValueError("predict_samples=%d: at least 2 draws" % predict_samples)
+
+
+def _predict(eng, n, gt, run_dir, drop_ale=False):
+    """After the last iteration: eng.predict(n, target=gt) -> predictive.npz in the run directory (when saving); returns the arrays."""
     import torch
+    r = eng.predict(n, target=torch.from_numpy(np.ascontiguousarray(gt, np.float32)))
+    arrs = {k: r[k].cpu().numpy() for k in ("mean", "epi", "ale", "total", "err2", "mse_mc") if r[k] is not None and not (drop_ale and k == "ale")}
+    arrs.update(n_samples=np.int64(r["n"]), step=np.int64(r["step"]))
+    if run_dir is not None:
+        np.savez(os.path.join(run_dir, "predictive.npz"), **arrs)
+    return arrs
+
+
+def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, seed, show_every, plot, save, save_path, K, factor=4,
+         theta_step=4.0, verbose=False, net_kwargs=None, method="mfvi", weight_decay=0.0, dropout_p=0.3, gamma=0.996, param_dtype="f32", predict_samples=0, **unused):
+    import torch
+    _check_predict(method, predict_samples)
     sib = dict(weight_decay=weight_decay, dropout_p=dropout_p, gamma=gamma)
     timestamp = str(time.time())
     run_dir = os.path.join(save_path, timestamp)
@@ -275,6 +296,7 @@ def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, see
                 mn, mg, ps_, _ = book.results()
                 A.snapshot_pngs(run_dir, method, i, mn, mg, ps_, recon[None], None if method == "dip" else var[None],
                                 None if (method == "dip" or task == "ct") else ale[None])
+    pred = _predict(eng, predict_samples, img_np, run_dir if save else None, drop_ale=task == "ct") if predict_samples else None
     torch.cuda.synchronize()
     mse_noisy, mse_gt, psnrs, ssims = book.results()
     if save:
@@ -289,8 +311,11 @@ def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, see
                 A.plot_results({method: mse_noisy}, {method: mse_gt}, {method: psnrs}, {method: ssims}, run_dir, f)
         if plot and task == "sr":
             A.sr_input_png(run_dir, img_np[None], extra["img_lr"], factor)
-    return dict(psnr=float(psnrs[-1, 2]), run_dir=run_dir if save else None, psnrs=psnrs, ssims=ssims, mse_noisy=mse_noisy, mse_gt=mse_gt,
-                recons=recons, uncerts=uncerts_epi, uncerts_ale=uncerts_ale, seconds=time.perf_counter() - t0, engine=eng)
+    res = dict(psnr=float(psnrs[-1, 2]), run_dir=run_dir if save else None, psnrs=psnrs, ssims=ssims, mse_noisy=mse_noisy, mse_gt=mse_gt,
+               recons=recons, uncerts=uncerts_epi, uncerts_ale=uncerts_ale, seconds=time.perf_counter() - t0, engine=eng)
+    if pred is not None:
+        res["predictive"] = pred
+    return res
 
 
 def run_den_mfvi(img="phantom", imsize=(256, 256), p_sigma=0.1, num_iter=5000, lr=3e-4, temp=4e-6, sigma=0.01, input_depth=16, seed=42,
@@ -345,12 +370,13 @@ run_ct_sgld = _sibling("ct", "sgld", dict(gamma=0.996, weight_decay=5e-8))
 
 def run_inp_mfvi(img="phantom", mask=None, imsize=(256, 256), num_iter=5000, lr=2e-3, temp=4e-6, sigma=0.01, input_depth=32, seed=42,
                  show_every=100, plot=False, save=True, save_path="../logs", K=1, net_kwargs=None, verbose=False, method="mfvi",
-                 weight_decay=1e-4, dropout_p=0.2, gamma=0.996, **unused):
+                 weight_decay=1e-4, dropout_p=0.2, gamma=0.996, predict_samples=0, **unused):
     """bayesian_optimization.py:2892-3114: inpainting with the 6-scale no-skip net (5x5 down filters, nearest up-sampling), sigmoid on
     the colour channels, masked Gaussian NLL.  img: (3, H, W) array in [0, 1] or 'phantom' (three synthetic planes); mask: (1|3, H, W),
     1 = known pixel (the reference ships its masks in data/inpainting/).  save.npz carries the reference's keys for this task
     (img_inpainting, img_mask, mse_corrupted, mse_gt, recons, uncerts, uncerts_ale, psnrs, ssims)."""
     import torch
+    _check_predict(method, predict_samples)
     timestamp = str(time.time())
     run_dir = os.path.join(save_path, timestamp)
     if save:
@@ -390,6 +416,7 @@ def run_inp_mfvi(img="phantom", mask=None, imsize=(256, 256), num_iter=5000, lr=
             if verbose:
                 nll, kl, loss = eng.losses()
                 print("iter %6d  loss %.5f  nll %.5f  kl %.4e  (%.1f it/s)" % (i, loss, nll, kl, (i + 1) / (time.perf_counter() - t0)))
+    pred = _predict(eng, predict_samples, img_np, run_dir if save else None) if predict_samples else None
     torch.cuda.synchronize()
     mse_corrupted, mse_gt, psnrs, ssims = book.results()
     if save:
@@ -401,8 +428,11 @@ def run_inp_mfvi(img="phantom", mask=None, imsize=(256, 256), num_iter=5000, lr=
         if plot:
             A.snapshot_pngs(run_dir, method, num_iter - 1, mse_corrupted, mse_gt, psnrs, recons[-1], None if method == "dip" else uncerts_epi[-1],
                             None if method == "dip" else uncerts_ale[-1])
-    return dict(psnr=float(psnrs[-1, 2]), run_dir=run_dir if save else None, psnrs=psnrs, ssims=ssims, mse_corrupted=mse_corrupted, mse_gt=mse_gt,
-                recons=recons, uncerts=uncerts_epi, uncerts_ale=uncerts_ale, seconds=time.perf_counter() - t0, engine=eng)
+    res = dict(psnr=float(psnrs[-1, 2]), run_dir=run_dir if save else None, psnrs=psnrs, ssims=ssims, mse_corrupted=mse_corrupted, mse_gt=mse_gt,
+               recons=recons, uncerts=uncerts_epi, uncerts_ale=uncerts_ale, seconds=time.perf_counter() - t0, engine=eng)
+    if pred is not None:
+        res["predictive"] = pred
+    return res
 
 
 run_inp_dip = _sibling("inp", "dip", dict(input_depth=32, lr=2e-3))
@@ -449,7 +479,13 @@ def main(argv=None):
     ap.add_argument("--bo-rounds", type=int, default=0, help="> 0: the reference's Gaussian-process outer loop over the method's two hyper-parameters "
                                                              "(bo_params.<name>.logbounds of the config) for this many rounds, each round's candidates "
                                                              "run as independent fits (bo.py; parity unpinned: gpytorch is not available here)")
+    ap.add_argument("--predict-samples", type=int, default=0, help="> 0: after the last iteration draw N posterior samples of the fit (mfvi, mcd) "
+                                                                 "and write predictive.npz (mean, epi, ale, total, err2, mse_mc) beside save.npz")
     a = ap.parse_args(argv)
+    if a.predict_samples and a.bayes not in PREDICT_METHODS:
+        ap.error("--predict-samples needs a posterior to draw from (--bayes mfvi or mcd), not %s" % a.bayes)
+    if a.predict_samples < 0 or a.predict_samples == 1:
+        ap.error("--predict-samples %d: 0 (off) or at least 2" % a.predict_samples)
     cands, rp, cfg_devices = load_config(a.config, a.bayes, with_devices=True)
     short = {"denoising": "den", "super-resolution": "sr", "ct": "ct", "inpainting": "inp"}[a.task]
     fn_name = "run_%s_%s" % (short, a.bayes)
@@ -465,6 +501,8 @@ def main(argv=None):
     rp["plot"] = False
     if a.param_dtype != "f32":
         rp["param_dtype"] = a.param_dtype
+    if a.predict_samples:
+        rp["predict_samples"] = a.predict_samples
     imgs = a.img.split(",") if a.img else [rp.pop("img", "phantom")]
     rp.pop("img", None)
     jobs = [dict(cand, img=im) for im in imgs for cand in cands]
