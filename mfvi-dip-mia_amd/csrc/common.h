@@ -4,21 +4,31 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
-// A kernel launch that carries a pending "stop" event on its own dispatch packet (hipExtLaunchKernelGGL): mfvi_backward arms the event in
-// front of the last launch on the caller's stream before it forks work onto the side stream, so the fork costs that stream no marker
-// packet of its own (scripts/micro/fork_gap.hip: hipEventRecord + hipStreamWaitEvent add 5.1 us to the recording stream per fork, the
-// event on the kernel's packet 1.8 us).  Not armed (the normal case, and every launch outside mfvi_backward): a plain launch.
-extern thread_local hipEvent_t mfvi_tl_stop_event;
-// kernel family of the conv launch in progress, for mfvi_plan_last_kernel: the plan sets 1 (fp32 MFMA kernels) in front of an MFMA-path
-// launcher, the row-phase launchers (conv_rp.hip) overwrite it with 2, the bf16x6 launchers (conv_x6.hip, conv_bww_x6.hip) with 3
-extern thread_local int mfvi_tl_family;
+// Kernel family that served a convolution (mfvi_plan_last_kernel: the numbers are documented ABI, include/mfvi_hip.h), and what a conv launcher
+// answers besides 0 / a hipError_t: shape not served (try the next family / the generic kernel), tiling not valid for the shape
+enum ConvFamily { FAM_GENERIC = 0, FAM_MFMA = 1, FAM_ROWPHASE = 2, FAM_BF16X6 = 3, FAM_ONE_STAGE = 4, FAM_FOLD_SKIP = 5, FAM_STREAM_1X1 = 6 };
+enum { CONV_NOT_SERVED = -2, CONV_BAD_TILING = -3 };
+inline bool conv_declined(int rc) { return rc == CONV_NOT_SERVED || rc == CONV_BAD_TILING; }
+// Launch context of ONE op on ONE stream: the plan creates it on its stack and the launchers take it in place of a bare stream.
+struct Launch {
+    hipStream_t st;
+    // Pending fork / join event: rides on the dispatch packet of the FIRST kernel launched through mfvi_launch and is cleared there, so nullptr
+    // afterwards means "sent".  The plan arms it in front of the last launch on a stream before it forks work onto another one, so the fork
+    // costs that stream no marker packet of its own (scripts/micro/fork_gap.hip: hipEventRecord + hipStreamWaitEvent add 5.1 us to the
+    // recording stream per fork, the event on the kernel's packet 1.8 us); a launcher that takes a plain hipLaunchKernelGGL leaves it armed
+    // and the plan falls back to hipEventRecord.
+    hipEvent_t stop = nullptr;
+    float* x6_scratch = nullptr;      // split weight pieces of THIS op and pass for the bf16x6 forward / backward-data kernel (nullptr: not served)
+    bool x6_ready = false;            // a pass-wide split launch already filled them (launch_x6_split_all / launch_x6b_split_all)
+    int family = FAM_GENERIC;         // written by the launcher that enqueues the kernel, behind its last "not served" return
+};
 template <typename F, typename... Args>
-inline void mfvi_launch(F kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args)
+inline void mfvi_launch(Launch& L, F kernel, dim3 grid, dim3 block, size_t lds, Args... args)
 {
-    if (mfvi_tl_stop_event) {
-        hipEvent_t e = mfvi_tl_stop_event; mfvi_tl_stop_event = nullptr;
-        hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, st, nullptr, e, 0, args...);
-    } else hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+    if (L.stop) {
+        hipEvent_t e = L.stop; L.stop = nullptr;
+        hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, L.st, nullptr, e, 0, args...);
+    } else hipLaunchKernelGGL(kernel, grid, block, lds, L.st, args...);
 }
 
 #define MFVI_MAX_C 256           // max channels of any activation tensor handled by the kernels
@@ -375,25 +385,45 @@ int launch_conv_bwd_data(const GView& gy, const ConvGeom& g, const float* mu, co
                          float* dxp, long long dxp_sstride, int n_samples, hipStream_t st);
 int launch_conv_bwd_weight(const TView& in, const GView& gy, const ConvGeom& g, const float* rho, RngKey key, int sample_weights,
                            float* dmu, float* drho, int n_samples, hipStream_t st);
-// MFMA variants (conv_mfma.hip): return -2 when the shape is not served and the generic kernel must run.
-// w: weights of sample 0, sample k at w + k*wstride (plan.hip: the buffer filled by launch_sample_weights, or mu with stride 0)
-int launch_conv_fwd_mfma(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int n_samples, hipStream_t st);
-// fuse (optional, 1x1 layers whose input has no other consumer): the epilogue does the fold of that input tensor itself — multiplies by
+// ---- dispatch of one convolution (conv_dispatch.hip): the ONE path from the plan (passes and autotuner alike) to a kernel family ----
+// Weights as the kernels want them: the slab for the matrix-core families (w: sample 0, sample k at w + k*wstride — the buffer filled by
+// launch_sample_weights, or mu with stride 0) and mu / rho / key for the generic kernels, which draw eps themselves (mu == nullptr: bf16
+// parameters, which reach those only through the plan's float32 expansion of the layers outside the sampling table).
+struct ConvWeights { const float* w; long long wstride; const float* mu; const float* rho; RngKey key; int sample_weights; };
+// fuse (1x1 / 3x3 stride-1 layers whose input has no other consumer): the epilogue does the fold of that input tensor itself — multiplies by
 // LeakyReLU'(view(x)), accumulates the BN-backward sums of x (bsums, nullptr when x carries no BatchNorm) and writes ga directly; no
 // padded-gradient scratch, no finalize_dx launch.
 struct FoldFuse { TView x; float* ga = nullptr; long long ga_sstride = 0; double* bsums = nullptr; };
+// Each: MFMA-path guards, the layer's tiling (ConvGeom::tune: MFVI_TUNE_ST / SM / X6 / RP / GENERIC bits, else rp_default_tune), that family's
+// launcher, the round-2 tiles, last the generic kernel; L.family = what ran.  generic_fallback = false (the autotuner's candidates) and
+// backward-data with `fuse` (the plan then takes the un-fused route) hand CONV_NOT_SERVED / CONV_BAD_TILING back instead.
+bool use_mfma();      // MFVI_DISABLE_MFMA=1 forces the generic fp32 VALU kernels (A/B timing and parity cross-checks)
+int conv_forward(Launch& L, const TView& in, const ConvGeom& g, const ConvWeights& W, OutDesc out, int n_samples, bool generic_fallback = true);
+int conv_backward_data(Launch& L, const GView& gy, const ConvGeom& g, const ConvWeights& W, float* dxp, long long dxp_sstride, int n_samples,
+                       const FoldFuse* fuse = nullptr, bool generic_fallback = true);
+// The MFMA backward-weight kernels write per-(pixel strip, sample) partial sums of dW (and of the bias gradient) with plain
+// stores: part.base[(strip * n_samples + k) * part.stride + j], j < n_w weights then n_b biases; launch_grad_finalize reduces
+// them, multiplies by eps * sigmoid(rho) per sample and accumulates into dmu / drho — no atomics, deterministic.
+struct BwwPart { float* base; long long stride; int max_strips; };
+// (L.family == FAM_GENERIC afterwards: the generic kernel accumulated into dmu / drho itself; else dW sits in *strips_used partial slabs)
+int conv_backward_weight(Launch& L, const TView& in, const GView& gy, const ConvGeom& g, const ConvWeights& W, BwwPart part, int* strips_used,
+                         float* dmu, float* drho, int n_samples, bool generic_fallback = true);
+// ---- the families' launchers.  Round-2 tiles (conv_mfma.hip, conv_bww_mfma.hip): tiling from ConvGeom::tune, MFVI_TUNE / MFVI_TUNE_W, heuristic
+int env_tune(); int env_tune_w();
+int launch_conv_fwd_mfma(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int n_samples, Launch& L);
 int launch_conv_bwd_data_mfma(const GView& gy, const ConvGeom& g, const float* w, long long wstride, float* dxp, long long dxp_sstride,
-                              int n_samples, hipStream_t st, const FoldFuse* fuse = nullptr);
+                              int n_samples, Launch& L, const FoldFuse* fuse = nullptr);
+int launch_conv_bwd_weight_mfma(const TView& in, const GView& gy, const ConvGeom& g, BwwPart part, int* strips_used, int cfg, int n_samples, Launch& L);      // cfg 0: heuristic
 // Row-phase kernels for 3x3 stride-1 layers on maps whose width is a multiple of 64 (conv_rp.hip).  tune = mf | r << 8 | rem << 12 | T << 16
-// (output fragments per block, rows per wave, 4 extra channels on the 4x4x1 instruction, tiles per block); -2: shape not served, -3: tiling
-// not valid for the shape.  Backward-data always runs the fold of the input tensor in its epilogue (fuse.ga required).
+// (output fragments per block, rows per wave, 4 extra channels on the 4x4x1 instruction, tiles per block).  Backward-data always runs the
+// fold of the input tensor in its epilogue (fuse.ga required).
 #define MFVI_TUNE_RP (1 << 24)
-int launch_conv_fwd_rp(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int tune, int n_samples, hipStream_t st);
-int launch_conv_bwd_data_rp(const GView& gy, const ConvGeom& g, const float* w, long long wstride, int tune, int n_samples, hipStream_t st, const FoldFuse& fuse);
+int launch_conv_fwd_rp(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int tune, int n_samples, Launch& L);
+int launch_conv_bwd_data_rp(const GView& gy, const ConvGeom& g, const float* w, long long wstride, int tune, int n_samples, Launch& L, const FoldFuse& fuse);
 int rp_default_tune(const ConvGeom& g, int mode, int n_samples);      // 0: not served / disabled (MFVI_RP=0)
 // Forward of the 3x3 stride-1 layers with 32 n (+ 4) input channels on maps whose width is a multiple of 64, on the bf16 matrix cores with
 // three-way split operands (conv_x6.hip).  tune = mf | sr << 8 (output fragments per block, output rows per block).  Needs a scratch region
-// of x6_fwd_scratch_floats() floats for the split weight pieces: the plan hands it over in mfvi_tl_x6w around the launch (nullptr: -2).
+// of x6_fwd_scratch_floats() floats for the split weight pieces: Launch::x6_scratch (nullptr: CONV_NOT_SERVED).
 #define MFVI_TUNE_X6 (1 << 25)
 // small-map forward (conv_small.hip): the whole reduction of a (sample, 16 output channels, 64 pixels) block in LDS, one stage; tune bit 26
 #define MFVI_TUNE_SM (1 << 26)
@@ -403,37 +433,37 @@ int rp_default_tune(const ConvGeom& g, int mode, int n_samples);      // 0: not 
 // weights (every 1x1 skip convolution, the 16 -> 16 layers): kept where it is at least as fast as the matrix-core kernel reading the slab.
 #define MFVI_TUNE_GENERIC (1 << 27)
 #define MFVI_INKERNEL_MAX_W 2560
-int launch_conv_fwd_small(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int n_samples, hipStream_t st);
-int launch_conv_bwd_data_small(const GView& gy, const ConvGeom& g, const float* w, long long wstride, int n_samples, hipStream_t st, const FoldFuse& fuse);
+int launch_conv_fwd_small(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int n_samples, Launch& L);
+int launch_conv_bwd_data_small(const GView& gy, const ConvGeom& g, const float* w, long long wstride, int n_samples, Launch& L, const FoldFuse& fuse);
 // Streaming forward of the narrow 1x1 layers (conv_1x1.hip, conv1_stream_kernel): Cin in {4, 8, 12, 16, 32, 64}, Cout <= 16 (<= 32 for Cin 16 / 32), H*W a multiple of 64;
-// nothing through LDS, the pixel operand straight from global memory into the matrix instruction.  Tune bit 28; -2: shape not served
+// nothing through LDS, the pixel operand straight from global memory into the matrix instruction.  Tune bit 28
 #define MFVI_TUNE_ST (1 << 28)
-int launch_conv1_fwd_stream(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int n_samples, hipStream_t st);
-// One-stage 1x1 kernels (conv_1x1.hip): 16 | Cin, Cout <= 128, H*W a multiple of 64; same tune bit (MFVI_TUNE_SM) on a 1x1 layer; -2: shape not served
-int launch_conv1_fwd_small(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int n_samples, hipStream_t st);
-int launch_conv1_bwd_data_small(const GView& gy, const ConvGeom& g, const float* w, long long wstride, int n_samples, hipStream_t st, const FoldFuse& fuse);
-extern thread_local float* mfvi_tl_x6w;
-extern thread_local bool mfvi_tl_x6w_ready;      // the pieces of this pass are already in the scratch (launch_x6_split_all)
+int launch_conv1_fwd_stream(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int n_samples, Launch& L);
+// One-stage 1x1 kernels (conv_1x1.hip): 16 | Cin, Cout <= 128, H*W a multiple of 64; same tune bit (MFVI_TUNE_SM) on a 1x1 layer
+int launch_conv1_fwd_small(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int n_samples, Launch& L);
+int launch_conv1_bwd_data_small(const GView& gy, const ConvGeom& g, const float* w, long long wstride, int n_samples, Launch& L, const FoldFuse& fuse);
 long long x6_fwd_scratch_floats(const ConvGeom& g, int n_samples);
 // one launch for all bf16x6 layers of a pass: dst_off = the layer's scratch offset (floats) in the arena, first_block = running block count
 struct X6SplitEntry { long long w_off, dst_off; int Cin, Cout, COp, ncg, rem, units, first_block, pad; };
 bool x6_split_entry(const ConvGeom& g, long long dst_off, X6SplitEntry* e);      // false: shape not served
 int launch_x6_split_all(const X6SplitEntry* table_dev, int n_entries, int n_blocks, const float* w, long long wstride, int n_k, float* arena, hipStream_t st);
-int launch_conv_fwd_x6(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int tune, int n_samples, hipStream_t st);
+int launch_conv_fwd_x6(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int tune, int n_samples, Launch& L);
 // Backward-data WITH the fold of the 3x3 stride-1 layers with 16 / 32 / 64 output channels on maps a multiple of 64 wide, on the bf16
 // matrix cores (conv_bwd_x6.hip).  tune = T | sr << 8 (strips per block, output rows per strip: 8 / 4 / 2 for 16 / 32 / 64 output channels).
-// Scratch for the split weight pieces: x6_bwd_scratch_floats() floats, handed over in mfvi_tl_x6bw around the launch (nullptr: -2).
-extern thread_local float* mfvi_tl_x6bw;
-extern thread_local bool mfvi_tl_x6bw_ready;
+// Scratch for the split weight pieces: x6_bwd_scratch_floats() floats in Launch::x6_scratch (nullptr: CONV_NOT_SERVED).
 long long x6_bwd_scratch_floats(const ConvGeom& g, int n_samples);
 struct X6BSplitEntry { long long w_off, dst_off; int CI, CO, NF, NG, k16, units, first_block, rem_units; };      // rem_units: the (ky, c) operand of the last 4 input channels (conv_bwd_x6s.hip), behind the regular units
 bool x6b_split_entry(const ConvGeom& g, long long dst_off, X6BSplitEntry* e);
 int launch_x6b_split_all(const X6BSplitEntry* table_dev, int n_entries, int n_blocks, const float* w, long long wstride, int n_k, float* arena, hipStream_t st);
-// strip-resident form for 32 (+4) -> 16 layers (conv_bwd_x6s.hip; bit 16 of the bf16x6 backward-data tiling); -3: shape not served
+// strip-resident form for 32 (+4) -> 16 layers (conv_bwd_x6s.hip; bit 16 of the bf16x6 backward-data tiling); CONV_BAD_TILING: shape not served
 bool x6s_shape_ok(const ConvGeom& g);
 int launch_conv_bwd_data_x6s(const GView& gy, const ConvGeom& g, const unsigned* wsp, long long wsp_stride_u4, int rem_off_u4, int T, int n_samples,
-                             hipStream_t st, const FoldFuse& fuse);
-int launch_conv_bwd_data_x6(const GView& gy, const ConvGeom& g, const float* w, long long wstride, int tune, int n_samples, hipStream_t st, const FoldFuse& fuse);
+                             Launch& L, const FoldFuse& fuse);
+int launch_conv_bwd_data_x6(const GView& gy, const ConvGeom& g, const float* w, long long wstride, int tune, int n_samples, Launch& L, const FoldFuse& fuse);
+// 3x3 stride-1 layers on maps whose width is a multiple of 64, on the bf16 matrix cores with three-way split operands (conv_bww_x6.hip):
+// cof = 16-channel output fragments per block (1 / 2), target = block-count target; same slabs as launch_conv_bwd_weight_mfma
+int launch_conv_bwd_weight_x6(const TView& in, const GView& gy, const ConvGeom& g, BwwPart part, int* strips_used, int cof, int target,
+                              int n_samples, Launch& L);
 // One launch per pass: W[k][j] = mu[j] + softplus(rho[j]) * eps_k[j] for the weights and biases of every layer in the table.
 struct SampleEntry { long long w_off, b_off; int n_w, n_b, layer_id, first_block; };
 // bf16: mu / rho point to bf16_t arrays; sample = 0 writes W = mu (RTLayer's eval branch) — callers then launch it for ONE sample
@@ -442,16 +472,6 @@ int launch_sample_weights(const SampleEntry* table_dev, int n_entries, int n_blo
 // bf16 -> float32 expansion (the generic fp32 kernels of shapes the MFMA path does not serve read float32 mu / rho)
 int launch_expand_bf16(const void* src, long long n, float* dst, hipStream_t st);
 constexpr int SAMPLE_QUADS = 256;       // weight quads per block of the sampling kernel
-// The MFMA backward-weight kernel writes per-(pixel strip, sample) partial sums of dW (and of the bias gradient) with plain
-// stores: part.base[(strip * n_samples + k) * part.stride + j], j < n_w weights then n_b biases; launch_grad_finalize reduces
-// them, multiplies by eps * sigmoid(rho) per sample and accumulates into dmu / drho — no atomics, deterministic.
-struct BwwPart { float* base; long long stride; int max_strips; };
-int launch_conv_bwd_weight_mfma(const TView& in, const GView& gy, const ConvGeom& g, BwwPart part, int* strips_used, int n_samples,
-                                hipStream_t st);
-// 3x3 stride-1 layers on maps whose width is a multiple of 64, on the bf16 matrix cores with three-way split operands (conv_bww_x6.hip):
-// cof = 16-channel output fragments per block (1 / 2), target = block-count target; same slabs as launch_conv_bwd_weight_mfma
-int launch_conv_bwd_weight_x6(const TView& in, const GView& gy, const ConvGeom& g, BwwPart part, int* strips_used, int cof, int target,
-                              int n_samples, hipStream_t st);
 struct GradFinEntry { long long w_off, b_off, part_off, stride; int n_w, n_b, strips, layer_id, first_block, pad; };
 // wsamp (optional): the sampled-weight slab of this pass, sample k at wsamp + k*wstride; then eps_k*softplus(rho) is read as W_k - mu
 struct BnGradEntry { long long bsums_off; long long bn_off; int C; int hw; };      // hw = H * W of the normalised tensor
@@ -480,9 +500,9 @@ constexpr int MAX_FOLD_SRC = 4;      // two consumers, each an RT (one source) o
 struct FoldSrcs { FoldSrc s[MAX_FOLD_SRC]; int n; };
 // ga_X = act'(X) * fold(sum of sources); accumulates BN-backward sums of X.
 int launch_finalize_dx(const FoldSrc* srcs, int n_src, const TView& x, float* ga, long long ga_sstride, double* bsums,
-                       int n_samples, hipStream_t st);
+                       int n_samples, Launch& L);
 int launch_finalize_dx_inline1x1(const FoldSrc& s0, const GView& g1, const float* w1, long long w1_sstride, int cs1, const TView& x, float* ga,
-                                 long long ga_sstride, double* bsums, int n_samples, hipStream_t st);
+                                 long long ga_sstride, double* bsums, int n_samples, Launch& L);
 // ---- local reparameterisation (LRTLayer.forward, BayTorch/modules/reparam_layers.py:59-72) around two ordinary convolutions ----
 // sig2[j] = softplus(rho[j])^2 for j in [0, n): the weights / bias of the variance convolution
 int launch_lrt_sigma2(const float* rho, long long n, float* sig2, hipStream_t st);
@@ -496,7 +516,7 @@ int launch_lrt_ds2(const GView& gy, const float* s2, long long sstride, RngKey k
 int launch_lrt_drho(const float* dsig2, const float* rho, long long n, float* drho, hipStream_t st);
 int launch_concat_up_fwd(const TView* a, const TView& b, OutDesc out, int nearest, int n_samples, hipStream_t st);
 int launch_concat_up_bwd(const GView& gc, const TView* a, float* ga_a, long long ga_a_sstride, double* bsums_a,
-                         const TView& b, float* ga_b, long long ga_b_sstride, double* bsums_b, int nearest, int n_samples, hipStream_t st);
+                         const TView& b, float* ga_b, long long ga_b_sstride, double* bsums_b, int nearest, int n_samples, Launch& L);
 // Dropout2d factors of one forward: arena[e.drop_off + k*C + c] for every entry, sample k, channel c (RNG domain 5, stream layer_id)
 struct DropEntry { long long drop_off; int C, layer_id; float p; int pad; };
 int launch_dropout_masks(const DropEntry* table_dev, int n_entries, RngKey key, int n_samples, float* arena, hipStream_t st);

@@ -201,22 +201,22 @@ bool c1_shape_ok(const ConvGeom& g)
     return (long long)max(g.Cin, g.Cout) * g.H * g.W < (1LL << 30);
 }
 
-int c1_launch(int mode, C1Args& A, int n_samples, hipStream_t st)
+int c1_launch(int mode, C1Args& A, int n_samples, Launch& L)
 {
     const ConvGeom& g = A.g;
     const int RED = mode == 0 ? g.Cin : g.Cout, MOUT = mode == 0 ? g.Cout : g.Cin;
     const int nfr = MOUT >> 4;
-    if (nfr != 2 && nfr != 4 && nfr != 8) return -2;
-    if (RED * MOUT / 16 > 1024) return -2;                 // weight items of two per thread
+    if (nfr != 2 && nfr != 4 && nfr != 8) return CONV_NOT_SERVED;
+    if (RED * MOUT / 16 > 1024) return CONV_NOT_SERVED;                 // weight items of two per thread
     A.nx = (g.H * g.W) >> 6; A.nz = n_samples;
     const size_t lds_bytes = sizeof(float) * ((size_t)(RED >> 4) * 64 * 16 + (size_t)(RED >> 4) * MOUT * 16);
-    if (lds_bytes > 144 * 1024) return -2;
+    if (lds_bytes > 144 * 1024) return CONV_NOT_SERVED;
     static const hipError_t attr0 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_sm_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
     static const hipError_t attr1 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1_sm_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
     if (attr0 != hipSuccess || attr1 != hipSuccess) return (int)(attr0 != hipSuccess ? attr0 : attr1);
-    mfvi_tl_family = 4;
-    if (mode == 0) mfvi_launch(conv1_sm_kernel<0>, dim3(A.nx * A.nz), dim3(512), lds_bytes, st, A);
-    else mfvi_launch(conv1_sm_kernel<1>, dim3(A.nx * A.nz), dim3(512), lds_bytes, st, A);
+    L.family = FAM_ONE_STAGE;
+    if (mode == 0) mfvi_launch(L, conv1_sm_kernel<0>, dim3(A.nx * A.nz), dim3(512), lds_bytes, A);
+    else mfvi_launch(L, conv1_sm_kernel<1>, dim3(A.nx * A.nz), dim3(512), lds_bytes, A);
     return (int)hipGetLastError();
 }
 
@@ -327,24 +327,23 @@ __global__ __launch_bounds__(256) void conv1_stream_kernel(C1Args A)
 }  // namespace
 
 // streaming forward of a narrow 1x1 layer (tune bit 28): Cin a multiple of 4 up to 64, Cout <= 16, H*W a multiple of 16.  -2: shape not served
-int launch_conv1_fwd_stream(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int n_samples, hipStream_t st)
+int launch_conv1_fwd_stream(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int n_samples, Launch& L)
 {
-    if (g.ks != 1 || g.stride != 1 || (g.Cin & 3) || g.Cin > 4 * C1S_MAXNS || g.Cout > 32 || (((long long)g.H * g.W) & 63) || (in.act & MFVI_ACT_SQUARE)) return -2;
-    if ((in.sstride & 3) || (out.sstride & 3) || (((uintptr_t)in.data | (uintptr_t)out.data) & 15)) return -2;      // float4 rows
-    if ((long long)max(g.Cin, g.Cout) * g.H * g.W >= (1LL << 31)) return -2;
+    if (g.ks != 1 || g.stride != 1 || (g.Cin & 3) || g.Cin > 4 * C1S_MAXNS || g.Cout > 32 || (((long long)g.H * g.W) & 63) || (in.act & MFVI_ACT_SQUARE)) return CONV_NOT_SERVED;
+    if ((in.sstride & 3) || (out.sstride & 3) || (((uintptr_t)in.data | (uintptr_t)out.data) & 15)) return CONV_NOT_SERVED;      // float4 rows
+    if ((long long)max(g.Cin, g.Cout) * g.H * g.W >= (1LL << 31)) return CONV_NOT_SERVED;
     C1Args A{};
     A.xin = in; A.g = g; A.w = w; A.wstride = wstride; A.out = out;
     const int n_groups = (g.H * g.W) >> 6;
     const int ns = g.Cin >> 2;
-    if (ns != 1 && ns != 2 && ns != 3 && ns != 4 && ns != 8 && ns != 16) return -2;      // (instantiated reduction depths: 4 ... 16, 32, 64 channels)
+    if (ns != 1 && ns != 2 && ns != 3 && ns != 4 && ns != 8 && ns != 16) return CONV_NOT_SERVED;      // (instantiated reduction depths: 4 ... 16, 32, 64 channels)
+    if (g.Cout > 16 && ns != 4 && ns != 8) return CONV_NOT_SERVED;      // two output fragments: the 16 / 32 -> 32 layers
     // blocks: enough to fill the chip four times over at most, each wave with at least one full unrolled batch where the map allows
     const int nb = max(1, min((n_groups + 7) / 8, (256 * 8 + n_samples - 1) / n_samples));
-    mfvi_tl_family = 6;
+    L.family = FAM_STREAM_1X1;
     const dim3 grid(nb, n_samples);
-#define C1S_GO(NS_, U_, NF_) mfvi_launch((conv1_stream_kernel<NS_, U_, NF_>), grid, dim3(256), 0, st, A)
-    if (g.Cout > 16) {      // two output fragments: the 16 / 32 -> 32 layers
-        if (ns == 4) C1S_GO(4, 2, 2); else if (ns == 8) C1S_GO(8, 1, 2); else return -2;
-    }
+#define C1S_GO(NS_, U_, NF_) mfvi_launch(L, (conv1_stream_kernel<NS_, U_, NF_>), grid, dim3(256), 0, A)
+    if (g.Cout > 16) { if (ns == 4) C1S_GO(4, 2, 2); else C1S_GO(8, 1, 2); }
     else if (ns <= 4) { if (ns == 4) C1S_GO(4, 2, 1); else if (ns == 3) C1S_GO(3, 2, 1); else if (ns == 2) C1S_GO(2, 4, 1); else C1S_GO(1, 4, 1); }
     else if (ns == 8) C1S_GO(8, 1, 1);
     else C1S_GO(16, 1, 1);
@@ -353,20 +352,20 @@ int launch_conv1_fwd_stream(const TView& in, const ConvGeom& g, const float* w, 
 }
 
 // -2: shape not served
-int launch_conv1_fwd_small(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int n_samples, hipStream_t st)
+int launch_conv1_fwd_small(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int n_samples, Launch& L)
 {
-    if (!c1_shape_ok(g) || (in.act & MFVI_ACT_SQUARE)) return -2;
-    if ((g.Cin & 3) || (uintptr_t)(w + g.w_off) & 15) return -2;      // float4 weight rows
+    if (!c1_shape_ok(g) || (in.act & MFVI_ACT_SQUARE)) return CONV_NOT_SERVED;
+    if ((g.Cin & 3) || (uintptr_t)(w + g.w_off) & 15) return CONV_NOT_SERVED;      // float4 weight rows
     C1Args A{};
     A.xin = in; A.g = g; A.w = w; A.wstride = wstride; A.out = out;
-    return c1_launch(0, A, n_samples, st);
+    return c1_launch(0, A, n_samples, L);
 }
 
-int launch_conv1_bwd_data_small(const GView& gy, const ConvGeom& g, const float* w, long long wstride, int n_samples, hipStream_t st, const FoldFuse& fuse)
+int launch_conv1_bwd_data_small(const GView& gy, const ConvGeom& g, const float* w, long long wstride, int n_samples, Launch& L, const FoldFuse& fuse)
 {
-    if (!c1_shape_ok(g) || !fuse.ga) return -2;
+    if (!c1_shape_ok(g) || !fuse.ga) return CONV_NOT_SERVED;
     C1Args A{};
     A.xin = fuse.x; A.gin = gy; A.g = g; A.w = w; A.wstride = wstride;
     A.fga = fuse.ga; A.fga_sstride = fuse.ga_sstride; A.fbsums = fuse.bsums;
-    return c1_launch(1, A, n_samples, st);
+    return c1_launch(1, A, n_samples, L);
 }

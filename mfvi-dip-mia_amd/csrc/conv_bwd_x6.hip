@@ -32,9 +32,6 @@
 #include <type_traits>
 #include <cstdlib>
 
-thread_local float* mfvi_tl_x6bw = nullptr;       // split weight pieces of the op being launched (plan.hip); nullptr: kernel not available
-thread_local bool mfvi_tl_x6bw_ready = false;     // the pieces of this pass are already there (launch_x6b_split_all ran behind the weight draw)
-
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -675,15 +672,15 @@ __global__ __launch_bounds__(512, 2) void conv_bwd_x6_kernel(X6BArgs A)
 }
 
 template <bool K16, int SR, int NG>
-int launch_one(X6BArgs& A, hipStream_t st)
+int launch_one(X6BArgs& A, Launch& L)
 {
     using C = X6BCfg<K16, SR, NG>;
     const size_t lds_bytes = (size_t)C::RING + C::WB + 16 * C::OPB + sizeof(BwdC) * A.g.Cout + sizeof(ChanFwd) * A.NF * 16 + sizeof(float) * C::SUMW * A.NF * 16 * 2;
-    if (lds_bytes > 160 * 1024) return -3;
+    if (lds_bytes > 160 * 1024) return CONV_BAD_TILING;
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_bwd_x6_kernel<K16, SR, NG>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (attr != hipSuccess) return (int)attr;
-    mfvi_tl_family = 3;
-    mfvi_launch((conv_bwd_x6_kernel<K16, SR, NG>), dim3(A.nx * A.nz), dim3(512), lds_bytes, st, A);
+    L.family = FAM_BF16X6;
+    mfvi_launch(L, (conv_bwd_x6_kernel<K16, SR, NG>), dim3(A.nx * A.nz), dim3(512), lds_bytes, A);
     return (int)hipGetLastError();
 }
 
@@ -718,35 +715,35 @@ int launch_x6b_split_all(const X6BSplitEntry* table_dev, int n_entries, int n_bl
 }
 
 // tune: T | sr << 8 (strips per block, output rows per strip; MFVI_TUNE_X6 stripped by the caller).  -2: shape not served / no scratch, -3: tiling not valid.
-int launch_conv_bwd_data_x6(const GView& gy, const ConvGeom& g, const float* w, long long wstride, int tune, int n_samples, hipStream_t st, const FoldFuse& fuse)
+int launch_conv_bwd_data_x6(const GView& gy, const ConvGeom& g, const float* w, long long wstride, int tune, int n_samples, Launch& L, const FoldFuse& fuse)
 {
-    float* scratch = mfvi_tl_x6bw;
-    if (!scratch || !x6b_shape_ok(g)) return -2;
-    if (!fuse.ga || (fuse.ga_sstride & 3) || ((uintptr_t)fuse.ga & 15)) return -2;
-    if ((fuse.x.sstride & 3) || ((uintptr_t)fuse.x.data & 15)) return -2;      // (the raw x is read as float4 whether or not it carries a BatchNorm)
-    if ((long long)max(g.Cin, g.Cout) * g.H * g.W >= (1LL << 29)) return -2;      // 32-bit element offsets per sample
+    float* scratch = L.x6_scratch;
+    if (!scratch || !x6b_shape_ok(g)) return CONV_NOT_SERVED;
+    if (!fuse.ga || (fuse.ga_sstride & 3) || ((uintptr_t)fuse.ga & 15)) return CONV_NOT_SERVED;
+    if ((fuse.x.sstride & 3) || ((uintptr_t)fuse.x.data & 15)) return CONV_NOT_SERVED;      // (the raw x is read as float4 whether or not it carries a BatchNorm)
+    if ((long long)max(g.Cin, g.Cout) * g.H * g.W >= (1LL << 29)) return CONV_NOT_SERVED;      // 32-bit element offsets per sample
     const int T = max(1, tune & 255), sr = (tune >> 8) & 255;
     const int want_sr = g.Cout == 16 ? 8 : g.Cout == 32 ? 4 : 2;          // SR * octets == 16 (the staging waves' task geometry)
-    if (sr != want_sr || (g.H % sr)) return -3;
+    if (sr != want_sr || (g.H % sr)) return CONV_BAD_TILING;
     X6BSplitEntry E;
-    if (!x6b_split_entry(g, 0, &E)) return -2;
+    if (!x6b_split_entry(g, 0, &E)) return CONV_NOT_SERVED;
     const int NV = E.k16 ? 2 : 3;
     const int n_k = wstride ? n_samples : 1;
-    if (!mfvi_tl_x6bw_ready) {      // no pass-wide split ran: this layer's own launch (dst_off 0: `scratch` is the layer's region)
+    if (!L.x6_ready) {      // no pass-wide split ran: this layer's own launch (dst_off 0: `scratch` is the layer's region)
         E.dst_off = 0;
-        hipLaunchKernelGGL(x6b_split_one_kernel, dim3((E.units + E.rem_units + 255) / 256, n_k), dim3(256), 0, st, E, w, wstride, scratch);
+        hipLaunchKernelGGL(x6b_split_one_kernel, dim3((E.units + E.rem_units + 255) / 256, n_k), dim3(256), 0, L.st, E, w, wstride, scratch);
     }
     X6BArgs A{};
     A.gin = gy; A.xin = fuse.x; A.g = g;
     A.wsp = reinterpret_cast<const unsigned*>(scratch); A.wsp_stride_u4 = wstride ? (long long)(E.units + E.rem_units) * NV : 0;
     if (tune & (1 << 16))      // strip-resident form (conv_bwd_x6s.hip)
-        return launch_conv_bwd_data_x6s(gy, g, A.wsp, A.wsp_stride_u4, E.units * NV, T, n_samples, st, fuse);
+        return launch_conv_bwd_data_x6s(gy, g, A.wsp, A.wsp_stride_u4, E.units * NV, T, n_samples, L, fuse);
     A.fga = fuse.ga; A.fga_sstride = fuse.ga_sstride; A.fbsums = fuse.bsums;
     A.NF = E.NF; A.bands = g.W / 64; A.strips = g.H / sr; A.tpb = T;
     A.nx = A.bands * ((A.strips + T - 1) / T); A.nz = n_samples;
-    if (g.Cout == 16) return launch_one<true, 8, 1>(A, st);
-    if (g.Cout == 32) return launch_one<false, 4, 1>(A, st);
-    return launch_one<false, 2, 2>(A, st);
+    if (g.Cout == 16) return launch_one<true, 8, 1>(A, L);
+    if (g.Cout == 32) return launch_one<false, 4, 1>(A, L);
+    return launch_one<false, 2, 2>(A, L);
 }
 
 #ifdef X6B_PROF

@@ -531,9 +531,9 @@ bool x6s_shape_ok(const ConvGeom& g)
 
 // tune: strips per block.  The caller (launch_conv_bwd_data_x6) has checked the fold's pointers and split this layer's weights.
 int launch_conv_bwd_data_x6s(const GView& gy, const ConvGeom& g, const unsigned* wsp, long long wsp_stride_u4, int rem_off_u4, int T, int n_samples,
-                             hipStream_t st, const FoldFuse& fuse)
+                             Launch& L, const FoldFuse& fuse)
 {
-    if (!x6s_shape_ok(g)) return -3;
+    if (!x6s_shape_ok(g)) return CONV_BAD_TILING;
     X6SArgs A{};
     A.gin = gy; A.xin = fuse.x; A.g = g;
     A.wsp = wsp; A.wsp_stride_u4 = wsp_stride_u4; A.rem_off_u4 = rem_off_u4;
@@ -544,10 +544,10 @@ int launch_conv_bwd_data_x6s(const GView& gy, const ConvGeom& g, const unsigned*
     static const hipError_t a0 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_bwd_x6s_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     static const hipError_t a1 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_bwd_x6s_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (a0 != hipSuccess || a1 != hipSuccess) return (int)(a0 != hipSuccess ? a0 : a1);
-    if (lds_bytes > 160 * 1024) return -3;
-    mfvi_tl_family = 3;
-    if (g.Cin == 36) mfvi_launch(conv_bwd_x6s_kernel<true>, dim3(A.nx * A.nz), dim3(512), lds_bytes, st, A);
-    else mfvi_launch(conv_bwd_x6s_kernel<false>, dim3(A.nx * A.nz), dim3(512), lds_bytes, st, A);
+    if (lds_bytes > 160 * 1024) return CONV_BAD_TILING;
+    L.family = FAM_BF16X6;
+    if (g.Cin == 36) mfvi_launch(L, conv_bwd_x6s_kernel<true>, dim3(A.nx * A.nz), dim3(512), lds_bytes, A);
+    else mfvi_launch(L, conv_bwd_x6s_kernel<false>, dim3(A.nx * A.nz), dim3(512), lds_bytes, A);
     return (int)hipGetLastError();
 }
 

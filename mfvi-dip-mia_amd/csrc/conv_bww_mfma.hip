@@ -656,33 +656,22 @@ __global__ __launch_bounds__(512, 4) void conv_bww_split_kernel(TView in, GView 
     if (do_bias && t < cot) o[(long long)Cout * Cin * KK + co0 + t] = s_db[t];
 }
 
+}  // namespace
+
 int env_tune_w()
 {
     static const int t = [] { int nb = 0, w = 0, tb = 0; const char* e = getenv("MFVI_TUNE_W"); if (e) sscanf(e, "%d,%d,%d", &nb, &w, &tb); return nb > 0 ? (nb | w << 8 | tb << 16) : 0; }();
     return t;
 }
 
-}  // namespace
-
 // Tiling (ConvGeom::tune[2], MFVI_TUNE_W=nb,w,target/256): nb | w << 8 | (target blocks / 256) << 16 with w = 4 (4 waves),
 // 8 (8 waves), 9 (8 waves, producer/consumer specialised), 10 (fragment-split variant, nb = 2: 3x3 stride 1, full-width tiles) or
-// 11 (bf16x6 kernel of conv_bww_x6.hip, nb = 16-channel output fragments per block: 3x3 stride 1 on maps whose width is a multiple of 64); 0 = heuristic.
-int launch_conv_bwd_weight_mfma(const TView& in, const GView& gy, const ConvGeom& g, BwwPart part, int* strips_used, int n_samples,
-                                hipStream_t st)
+// 11 (bf16x6 kernel of conv_bww_x6.hip, routed there by the dispatch); 0 = heuristic: stage dy once for up to 48 input channels when the
+// layer has them, 8 waves when the tile is big.
+int launch_conv_bwd_weight_mfma(const TView& in, const GView& gy, const ConvGeom& g, BwwPart part, int* strips_used, int cfg, int n_samples, Launch& L)
 {
-    if (!part.base || part.max_strips < 1 || (g.Cin & 3) || (g.w_off & 3)) return -2;
-    if (g.tune[2] & MFVI_TUNE_GENERIC) return -2;                           // in-kernel eps: the generic kernel accumulates d mu / d rho itself
-    int cfg = g.tune[2] ? g.tune[2] : env_tune_w();
     const bool forced = cfg != 0;
     if (!cfg) {
-        // heuristic: the bf16x6 kernel where it serves the shape and measured ahead of the fp32 ones (3x3 stride 1, >= 32 input channels, maps a
-        // multiple of 32 wide: profiles/r03_x6_layers.txt); otherwise stage dy once for up to 48 input channels when the layer has them, 8 waves
-        // when the tile is big
-        static const bool x6_on = [] { const char* e = getenv("MFVI_X6"); return !(e && e[0] == '0'); }();
-        if (x6_on && g.ks == 3 && g.stride == 1 && !(g.W & 31) && !(g.H & 1) && g.H >= 4 && g.Cin >= 32 && ((g.Cin & 15) == 0 || (g.Cin & 15) == 4)) {
-            const int rc = launch_conv_bwd_weight_x6(in, gy, g, part, strips_used, g.Cout >= 32 ? 2 : 1, 256, n_samples, st);
-            if (rc != -2 && rc != -3) return rc;
-        }
         const int nb = g.ks == 5 ? 1 : (g.Cin > 32 ? 3 : (g.Cin > 16 ? 2 : 1));
         cfg = nb | ((nb >= 2 || g.ks == 5 ? 9 : 4) << 8) | ((nb >= 2 ? 1 : 6) << 16);
     }
@@ -692,13 +681,12 @@ int launch_conv_bwd_weight_mfma(const TView& in, const GView& gy, const ConvGeom
     if (!forced && !vec_ok) cfg = (cfg & ~0xff00) | (4 << 8);      // heuristic falls back to the 4-wave variant
     const int nb = cfg & 255, wfield = (cfg >> 8) & 255, target = ((cfg >> 16) & 255) * 256;
     const bool spec = wfield == 9;
-    if (wfield == 11) return launch_conv_bwd_weight_x6(in, gy, g, part, strips_used, nb, target, n_samples, st);      // bf16x6 kernel (conv_bww_x6.hip), nb = output fragments per block
     if (wfield == 10) {
         // fragment-split variant: 3x3 stride 1, full-width tiles, aligned float4 staging, input-channel groups of 32 with a 4-channel remainder
         // riding in the last one (Cin = 16n or 16n + 4)
-        if (g.ks != 3 || g.stride != 1 || !vec_ok || (g.Wo & 31) || nb != 2 || target < 256) return -3;
+        if (g.ks != 3 || g.stride != 1 || !vec_ok || (g.Wo & 31) || nb != 2 || target < 256) return CONV_BAD_TILING;
         const int rem = g.Cin & 15;
-        if ((rem != 0 && rem != 4) || g.Cin < 16) return -3;
+        if ((rem != 0 && rem != 4) || g.Cin < 16) return CONV_BAD_TILING;
         const int ci_groups = (g.Cin % 32 == 4 || g.Cin % 32 == 0) ? g.Cin / 32 : g.Cin / 32 + 1;       // 36 -> 1, 68 -> 2, 132 -> 4, 48 -> 2 (32 + 16), 52 -> 2 (32 + 20)
         constexpr size_t lds_bytes = sizeof(float) * SCfg::LDS_FLOATS;
         const int tiles_x = g.Wo / SCfg::TW, tiles_y = (g.Ho + SCfg::TH - 1) / SCfg::TH, n_tiles = tiles_x * tiles_y;
@@ -711,7 +699,8 @@ int launch_conv_bwd_weight_mfma(const TView& in, const GView& gy, const ConvGeom
         strips = (n_tiles + tpb - 1) / tpb;
         static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_bww_split_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (attr != hipSuccess) return (int)attr;
-        mfvi_launch(conv_bww_split_kernel, dim3(strips * co_tiles * ci_groups * n_samples), dim3(512), lds_bytes, st, in, gy, g, part.base,
+        L.family = FAM_MFMA;
+        mfvi_launch(L, conv_bww_split_kernel, dim3(strips * co_tiles * ci_groups * n_samples), dim3(512), lds_bytes, in, gy, g, part.base,
                            part.stride, tiles_x, n_tiles, tpb, ci_groups, strips, co_tiles * ci_groups, n_samples);
         if (strips_used) *strips_used = strips;
         return (int)hipGetLastError();
@@ -721,12 +710,12 @@ int launch_conv_bwd_weight_mfma(const TView& in, const GView& gy, const ConvGeom
     {                                                                                                                          \
         using Cfg = WCfg<KS_, S_, NB_, NT_>;                                                                                   \
         constexpr size_t lds_bytes = sizeof(float) * Cfg::LDS_FLOATS;                                                          \
-        if (lds_bytes > 150 * 1024) return -3;                                                                                 \
-        if (SP_ && !vec_ok) return -3;                                         /* specialised producers stage aligned float4 */ \
+        if (lds_bytes > 150 * 1024) return CONV_BAD_TILING;                                                                                 \
+        if (SP_ && !vec_ok) return CONV_BAD_TILING;                                         /* specialised producers stage aligned float4 */ \
         const int tiles_x = (g.Wo + Cfg::TW - 1) / Cfg::TW, tiles_y = (g.Ho + Cfg::TH - 1) / Cfg::TH;                          \
         const int n_tiles = tiles_x * tiles_y;                                                                                 \
         const int co_tiles = (g.Cout + 15) / 16, ci_groups = (g.Cin + Cfg::CIB - 1) / Cfg::CIB;                                \
-        if (forced && NB_ > 1 && ci_groups == 1 && 16 * (NB_ - 1) >= g.Cin) return -3;   /* an input tile would be empty */           \
+        if (forced && NB_ > 1 && ci_groups == 1 && 16 * (NB_ - 1) >= g.Cin) return CONV_BAD_TILING;   /* an input tile would be empty */           \
         const long long pairs = (long long)co_tiles * ci_groups * n_samples;                                                   \
         int strips = (int)((target + pairs - 1) / pairs);                                                                      \
         strips = strips < 1 ? 1 : (strips > n_tiles ? n_tiles : strips);                                                       \
@@ -738,7 +727,8 @@ int launch_conv_bwd_weight_mfma(const TView& in, const GView& gy, const ConvGeom
             static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
             if (attr != hipSuccess) return (int)attr;                                                                          \
         }                                                                                                                      \
-        mfvi_launch(kern, dim3(strips * co_tiles * ci_groups * n_samples), dim3(NT_), lds_bytes, st, in, gy, g, part.base, \
+        L.family = FAM_MFMA;                                                                                                   \
+        mfvi_launch(L, kern, dim3(strips * co_tiles * ci_groups * n_samples), dim3(NT_), lds_bytes, in, gy, g, part.base,     \
                            part.stride, tiles_x, n_tiles, tpb, ci_groups, strips, co_tiles * ci_groups, n_samples);            \
         if (strips_used) *strips_used = strips;                                                                                \
         return (int)hipGetLastError();                                                                                         \
@@ -748,9 +738,9 @@ int launch_conv_bwd_weight_mfma(const TView& in, const GView& gy, const ConvGeom
         if (nt == 256) { if (nb == 1) LAUNCH(KS_, S_, 1, 256, false) if (nb == 2) LAUNCH(KS_, S_, 2, 256, false) if (nb == 3) LAUNCH(KS_, S_, 3, 256, false) } \
         if (nt == 512 && !spec) { if (nb == 1) LAUNCH(KS_, S_, 1, 512, false) if (nb == 2) LAUNCH(KS_, S_, 2, 512, false) if (nb == 3) LAUNCH(KS_, S_, 3, 512, false) } \
         if (nt == 512 && spec) { if (nb == 1) LAUNCH(KS_, S_, 1, 512, true) if (nb == 2) LAUNCH(KS_, S_, 2, 512, true) if (nb == 3) LAUNCH(KS_, S_, 3, 512, true) } \
-        return -3;                                                                                                             \
+        return CONV_BAD_TILING;                                                                                                             \
     }
-    if (target < 256) return -3;
+    if (target < 256) return CONV_BAD_TILING;
     if (g.ks == 3 && g.stride == 1) LAUNCH_NB(3, 1)
     if (g.ks == 3 && g.stride == 2) LAUNCH_NB(3, 2)
     if (g.ks == 1 && g.stride == 1) LAUNCH_NB(1, 1)
@@ -758,10 +748,10 @@ int launch_conv_bwd_weight_mfma(const TView& in, const GView& gy, const ConvGeom
     if (g.ks == 5 && nb == 1) {
         if (g.stride == 1) { if (nt == 256) LAUNCH(5, 1, 1, 256, false) if (nt == 512 && !spec) LAUNCH(5, 1, 1, 512, false) if (nt == 512 && spec) LAUNCH(5, 1, 1, 512, true) }
         if (g.stride == 2) { if (nt == 256) LAUNCH(5, 2, 1, 256, false) if (nt == 512 && !spec) LAUNCH(5, 2, 1, 512, false) if (nt == 512 && spec) LAUNCH(5, 2, 1, 512, true) }
-        return -3;
+        return CONV_BAD_TILING;
     }
-    if (g.ks == 5) return -3;
+    if (g.ks == 5) return CONV_BAD_TILING;
 #undef LAUNCH_NB
 #undef LAUNCH
-    return -2;
+    return CONV_NOT_SERVED;
 }

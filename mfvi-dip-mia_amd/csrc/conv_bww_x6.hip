@@ -443,7 +443,7 @@ __global__ __launch_bounds__(512, 2) void conv_bww_x6_kernel(X6Args A)
 }
 
 template <int COF, int BW>
-int launch_x6k(X6Args& A, dim3 grid, hipStream_t st)
+int launch_x6k(X6Args& A, dim3 grid, Launch& L)
 {
     using C = X6Cfg<BW>;
     constexpr size_t stage_bytes = 2 * (size_t)C::XBUF + (size_t)16 * COF * C::DCH, epi_bytes = sizeof(float) * (size_t)(4 / COF) * 16 * COF * C::ROWP;
@@ -451,8 +451,8 @@ int launch_x6k(X6Args& A, dim3 grid, hipStream_t st)
     static_assert(lds_bytes <= 150 * 1024, "LDS budget");
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_bww_x6_kernel<COF, BW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (attr != hipSuccess) return (int)attr;
-    mfvi_tl_family = 3;
-    mfvi_launch((conv_bww_x6_kernel<COF, BW>), grid, dim3(512), lds_bytes, st, A);
+    L.family = FAM_BF16X6;
+    mfvi_launch(L, (conv_bww_x6_kernel<COF, BW>), grid, dim3(512), lds_bytes, A);
     return (int)hipGetLastError();
 }
 
@@ -460,17 +460,17 @@ int launch_x6k(X6Args& A, dim3 grid, hipStream_t st)
 
 // tune: cof | 11 << 8 | (target blocks / 256) << 16.  Returns -2 when the shape is not served, -3 when the tiling is not valid for it.
 int launch_conv_bwd_weight_x6(const TView& in, const GView& gy, const ConvGeom& g, BwwPart part, int* strips_used, int cof, int target,
-                              int n_samples, hipStream_t st)
+                              int n_samples, Launch& L)
 {
-    if (g.ks != 3 || g.stride != 1 || (g.W & 31) || (g.H & 1) || g.H < 4 || g.Cin < 16) return -2;
+    if (g.ks != 3 || g.stride != 1 || (g.W & 31) || (g.H & 1) || g.H < 4 || g.Cin < 16) return CONV_NOT_SERVED;
     const int bw = (g.W & 63) ? 32 : 64, R = 128 / bw;
     const int rem = g.Cin & 15;
-    if (rem != 0 && rem != 4) return -2;
-    if ((in.sstride & 3) || ((uintptr_t)in.data & 15) || (gy.gstride & 3) || ((uintptr_t)gy.ga & 15) || (gy.y && ((gy.ystride & 3) || ((uintptr_t)gy.y & 15)))) return -2;
-    if (in.act & MFVI_ACT_SQUARE) return -2;
-    if ((long long)max(g.Cin, g.Cout) * g.H * g.W >= (1LL << 31)) return -2;
-    if (cof != 1 && cof != 2) return -3;
-    if (target < 256) return -3;
+    if (rem != 0 && rem != 4) return CONV_NOT_SERVED;
+    if ((in.sstride & 3) || ((uintptr_t)in.data & 15) || (gy.gstride & 3) || ((uintptr_t)gy.ga & 15) || (gy.y && ((gy.ystride & 3) || ((uintptr_t)gy.y & 15)))) return CONV_NOT_SERVED;
+    if (in.act & MFVI_ACT_SQUARE) return CONV_NOT_SERVED;
+    if ((long long)max(g.Cin, g.Cout) * g.H * g.W >= (1LL << 31)) return CONV_NOT_SERVED;
+    if (cof != 1 && cof != 2) return CONV_BAD_TILING;
+    if (target < 256) return CONV_BAD_TILING;
     const int cob = 16 * cof;
     const int ci_groups = (g.Cin % 32 == 4 || g.Cin % 32 == 0) ? g.Cin / 32 : g.Cin / 32 + 1;       // 36 -> 1, 68 -> 2, 132 -> 4, 48 -> 2 (32 + 16), 52 -> 2 (32 + 20)
     const int co_tiles = (g.Cout + cob - 1) / cob;
@@ -479,7 +479,7 @@ int launch_conv_bwd_weight_x6(const TView& in, const GView& gy, const ConvGeom& 
     int strips = (int)((target + pairs - 1) / pairs);
     strips = strips < 1 ? 1 : (strips > pr2 ? pr2 : strips);
     if (strips * bands > part.max_strips) strips = part.max_strips / bands;
-    if (strips < 1) return -3;
+    if (strips < 1) return CONV_BAD_TILING;
     const int spb = (pr2 + strips - 1) / strips;                            // stages per strip
     strips = (pr2 + spb - 1) / spb;
     X6Args A{};
@@ -488,8 +488,8 @@ int launch_conv_bwd_weight_x6(const TView& in, const GView& gy, const ConvGeom& 
     A.nx = strips * bands; A.ny = co_tiles * ci_groups; A.nz = n_samples;
     const dim3 grid(A.nx * A.ny * A.nz);
     int rc;
-    if (bw == 64) rc = cof == 1 ? launch_x6k<1, 64>(A, grid, st) : launch_x6k<2, 64>(A, grid, st);
-    else rc = cof == 1 ? launch_x6k<1, 32>(A, grid, st) : launch_x6k<2, 32>(A, grid, st);
+    if (bw == 64) rc = cof == 1 ? launch_x6k<1, 64>(A, grid, L) : launch_x6k<2, 64>(A, grid, L);
+    else rc = cof == 1 ? launch_x6k<1, 32>(A, grid, L) : launch_x6k<2, 32>(A, grid, L);
     if (rc == 0 && strips_used) *strips_used = strips * bands;
     return rc;
 }

@@ -1025,16 +1025,9 @@ bool phase_on()
     return on;
 }
 
-// Tiling override: MFVI_TUNE=mf,th,T (experiments) or the per-op choice made by mfvi_plan_autotune (ConvGeom::tune).
-int env_tune()
-{
-    static const int t = [] { int mf = 0, th = 0, T = 0; const char* e = getenv("MFVI_TUNE"); if (e) sscanf(e, "%d,%d,%d", &mf, &th, &T); return mf > 0 ? (mf | th << 8 | T << 16) : 0; }();
-    return t;
-}
-
 template <int KS, int STRIDE, int MODE>
 int launch_variant(const TView& xin, const GView& gin, const ConvGeom& g, const float* w, long long wstride, OutDesc out, float* dxp,
-                   long long dxp_sstride, int n_samples, hipStream_t st, FoldFuse fuse = FoldFuse{})
+                   long long dxp_sstride, int n_samples, Launch& L, FoldFuse fuse = FoldFuse{})
 {
     const int P = g.ks / 2, KK = KS * KS;
     constexpr bool CAN_FF = MODE == 1 && KS == 3 && STRIDE == 1;
@@ -1063,20 +1056,20 @@ int launch_variant(const TView& xin, const GView& gin, const ConvGeom& g, const 
         using Cfg = MCfg<KS, STRIDE, MF_, TH_>;                                                                            \
         A.tiles_x = (OW + 31) / 32;                                                                                        \
         A.n_tiles = A.tiles_x * ((OH + TH_ - 1) / TH_);                                                                    \
-        if (ff && !(FL_) && RED <= 3 * Cfg::CC) return -3;   /* producer-side fold: three parts in stages 0..2 of the next tile, dump at the last stage */ \
-        if ((FL_) && ff && (OW & 7)) return -3;       /* fused fold on FLAT tiles: rows are whole half-fragments (8x8 maps: two rows per fragment) */ \
+        if (ff && !(FL_) && RED <= 3 * Cfg::CC) return CONV_BAD_TILING;   /* producer-side fold: three parts in stages 0..2 of the next tile, dump at the last stage */ \
+        if ((FL_) && ff && (OW & 7)) return CONV_BAD_TILING;       /* fused fold on FLAT tiles: rows are whole half-fragments (8x8 maps: two rows per fragment) */ \
         if (FL_) {                                                                                                         \
             A.ow = OW; A.wpitch = (OW - 1) * STRIDE + KS;                                                                  \
             int rt = (TH_ * 32) / OW;                                                                                      \
             const int cap = (Cfg::IN_TH * Cfg::PITCH) / A.wpitch;            /* window rows that fit the LDS plane */      \
             if ((rt - 1) * STRIDE + KS > cap) rt = (cap - KS) / STRIDE + 1;                                                \
             if (rt > OH) rt = OH;                                                                                          \
-            if (rt < 1 || OW > 0xffff) return -3;                                                                          \
+            if (rt < 1 || OW > 0xffff) return CONV_BAD_TILING;                                                                          \
             A.rt = rt; A.nwin = ((rt - 1) * STRIDE + KS) * A.wpitch;                                                       \
             A.n_tiles = (OH + rt - 1) / rt;                                                                                \
         }                                                                                                                  \
         constexpr bool CAN_REM = CAN_FF && !(FL_) && TH_ == 8;                                                            \
-        if (want_rem && !(CAN_REM && ff && (MOUT & 15) == 4 && (MOUT - 4) % (16 * MF_) == 0)) return -3;                  \
+        if (want_rem && !(CAN_REM && ff && (MOUT & 15) == 4 && (MOUT - 4) % (16 * MF_) == 0)) return CONV_BAD_TILING;                  \
         const bool rem = want_rem;                                                                                         \
         const int my = rem ? (MOUT - 4) / (16 * MF_) : (MOUT + 16 * MF_ - 1) / (16 * MF_);                                 \
         constexpr bool CAN_BIG = (KS == 1 && !(FL_)) || (KS == 3 && STRIDE == 1 && (FL_) && TH_ <= 4);   /* 3x3: the small maps at the bottom of the hour-glass, both passes */ \
@@ -1096,27 +1089,27 @@ int launch_variant(const TView& xin, const GView& gin, const ConvGeom& g, const 
             if (lds_big + ws_bytes > 150 * 1024) big = false;                                                              \
             A.tiles_per_block = T;                                                                                         \
             A.nx = (A.n_tiles + T - 1) / T; A.ny = my; A.nz = n_samples;                                                   \
-            if (rem) mfvi_launch((conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, true, FL_, false, false, CAN_REM, CAN_REM>), dim3(A.nx * A.ny * A.nz), dim3(512), ws_bytes + chan_bytes, st, A); \
-            else if (ff && big) mfvi_launch((conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, true, FL_, CAN_BIG, false, CAN_FF && CAN_BIG>), dim3(A.nx * A.ny * A.nz), dim3(512), ws_bytes + chan_bytes, st, A); \
-            else if (ff) mfvi_launch((conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, true, FL_, false, false, CAN_FF>), dim3(A.nx * A.ny * A.nz), dim3(512), ws_bytes + chan_bytes, st, A); \
-            else if (big) mfvi_launch((conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, true, FL_, CAN_BIG>), dim3(A.nx * A.ny * A.nz), dim3(512), ws_bytes + chan_bytes, st, A); \
-            else if (ph) mfvi_launch((conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, true, FL_, false, CAN_PH>), dim3(A.nx * A.ny * A.nz), dim3(512), ws_bytes + chan_bytes, st, A); \
-            else mfvi_launch((conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, true, FL_>), dim3(A.nx * A.ny * A.nz), dim3(512), ws_bytes + chan_bytes, st, A); \
+            if (rem) mfvi_launch(L, (conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, true, FL_, false, false, CAN_REM, CAN_REM>), dim3(A.nx * A.ny * A.nz), dim3(512), ws_bytes + chan_bytes, A); \
+            else if (ff && big) mfvi_launch(L, (conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, true, FL_, CAN_BIG, false, CAN_FF && CAN_BIG>), dim3(A.nx * A.ny * A.nz), dim3(512), ws_bytes + chan_bytes, A); \
+            else if (ff) mfvi_launch(L, (conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, true, FL_, false, false, CAN_FF>), dim3(A.nx * A.ny * A.nz), dim3(512), ws_bytes + chan_bytes, A); \
+            else if (big) mfvi_launch(L, (conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, true, FL_, CAN_BIG>), dim3(A.nx * A.ny * A.nz), dim3(512), ws_bytes + chan_bytes, A); \
+            else if (ph) mfvi_launch(L, (conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, true, FL_, false, CAN_PH>), dim3(A.nx * A.ny * A.nz), dim3(512), ws_bytes + chan_bytes, A); \
+            else mfvi_launch(L, (conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, true, FL_>), dim3(A.nx * A.ny * A.nz), dim3(512), ws_bytes + chan_bytes, A); \
         } else {                                                                                                           \
             /* chunked weights: one tile per block, except for the fused fold on rectangular tiles, whose producer-side fold of tile i   \
                overlaps the stages of tile i+1 (the weights of a stage are re-read from L2 per tile) */                                   \
             const bool multi = ff && !(FL_);                                                                               \
-            if (forced_T > 1 && !multi) return -3;                                                                         \
+            if (forced_T > 1 && !multi) return CONV_BAD_TILING;                                                                         \
             if (lds_big + ck_big > 150 * 1024) big = false;                                                                \
             if (big) ck_bytes = ck_big;                                                                                    \
             A.tiles_per_block = multi ? T : 1;                                                                             \
             A.nx = (A.n_tiles + A.tiles_per_block - 1) / A.tiles_per_block; A.ny = my; A.nz = n_samples;                   \
-            if (rem) mfvi_launch((conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, false, FL_, false, false, CAN_REM, CAN_REM>), dim3(A.nx * A.ny * A.nz), dim3(512), ck_bytes + chan_bytes, st, A); \
-            else if (ff && big) mfvi_launch((conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, false, FL_, CAN_BIG, false, CAN_FF && CAN_BIG>), dim3(A.nx * A.ny * A.nz), dim3(512), ck_bytes + chan_bytes, st, A); \
-            else if (ff) mfvi_launch((conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, false, FL_, false, false, CAN_FF>), dim3(A.nx * A.ny * A.nz), dim3(512), ck_bytes + chan_bytes, st, A); \
-            else if (big) mfvi_launch((conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, false, FL_, CAN_BIG>), dim3(A.nx * A.ny * A.nz), dim3(512), ck_bytes + chan_bytes, st, A); \
-            else if (ph) mfvi_launch((conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, false, FL_, false, CAN_PH>), dim3(A.nx * A.ny * A.nz), dim3(512), ck_bytes + chan_bytes, st, A); \
-            else mfvi_launch((conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, false, FL_>), dim3(A.nx * A.ny * A.nz), dim3(512), ck_bytes + chan_bytes, st, A); \
+            if (rem) mfvi_launch(L, (conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, false, FL_, false, false, CAN_REM, CAN_REM>), dim3(A.nx * A.ny * A.nz), dim3(512), ck_bytes + chan_bytes, A); \
+            else if (ff && big) mfvi_launch(L, (conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, false, FL_, CAN_BIG, false, CAN_FF && CAN_BIG>), dim3(A.nx * A.ny * A.nz), dim3(512), ck_bytes + chan_bytes, A); \
+            else if (ff) mfvi_launch(L, (conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, false, FL_, false, false, CAN_FF>), dim3(A.nx * A.ny * A.nz), dim3(512), ck_bytes + chan_bytes, A); \
+            else if (big) mfvi_launch(L, (conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, false, FL_, CAN_BIG>), dim3(A.nx * A.ny * A.nz), dim3(512), ck_bytes + chan_bytes, A); \
+            else if (ph) mfvi_launch(L, (conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, false, FL_, false, CAN_PH>), dim3(A.nx * A.ny * A.nz), dim3(512), ck_bytes + chan_bytes, A); \
+            else mfvi_launch(L, (conv_mfma_kernel<KS, STRIDE, MF_, TH_, MODE, false, FL_>), dim3(A.nx * A.ny * A.nz), dim3(512), ck_bytes + chan_bytes, A); \
         }                                                                                                                  \
         return (int)hipGetLastError();                                                                                     \
     }
@@ -1128,27 +1121,27 @@ int launch_variant(const TView& xin, const GView& gin, const ConvGeom& g, const 
         const int mf = forced & 255;
         int th = (forced >> 8) & 255;
         forced_T = (forced >> 16) & 255;
-        if (th & 64) { want_rem = true; th &= ~64; if (th != 8) return -3; }
+        if (th & 64) { want_rem = true; th &= ~64; if (th != 8) return CONV_BAD_TILING; }
         if (th & 128) {        // FLAT tiles: 3x3 stride-1 kernels on domains up to 130 wide
             if constexpr (KS >= 3 && STRIDE == 2) {      // stride-2 forward on small outputs (MODE 1 always runs the stride-1 kernel)
-                if (OW > 32) return -3;
+                if (OW > 32) return CONV_BAD_TILING;
                 if ((th & 127) == 8) { if (mf == 1) GO_(1, 8, true) if (mf == 2) GO_(2, 8, true) if (mf == 4) GO_(4, 8, true) }
                 if ((th & 127) == 4) { if (mf == 1) GO_(1, 4, true) if (mf == 2) GO_(2, 4, true) if (mf == 4) GO_(4, 4, true) }
                 if ((th & 127) == 2) { if (mf == 1) GO_(1, 2, true) if (mf == 2) GO_(2, 2, true) if (mf == 4) GO_(4, 2, true) }
             }
             if constexpr (KS >= 3 && STRIDE == 1) {
-                if (OW > 132) return -3;
-                if constexpr (KS == 3) { if ((th & 127) == 16) { if (OH * OW >= 256) GO_MF_FLAT(mf, 16) return -3; } }
+                if (OW > 132) return CONV_BAD_TILING;
+                if constexpr (KS == 3) { if ((th & 127) == 16) { if (OH * OW >= 256) GO_MF_FLAT(mf, 16) return CONV_BAD_TILING; } }
                 if ((th & 127) == 8) { if constexpr (KS == 3) GO_MF_FLAT(mf, 8) else { if (mf == 1) GO_(1, 8, true) if (mf == 2) GO_(2, 8, true) } if (mf == 4) GO_(4, 8, true) }
                 // 128- and 64-pixel tiles for the 8x8 / 10x10 maps at the bottom of the hour-glass (a 256-pixel tile is 25-39% full there)
                 if ((th & 127) == 4) { if (mf == 1) GO_(1, 4, true) if (mf == 2) GO_(2, 4, true) if (mf == 4) GO_(4, 4, true) }
                 if ((th & 127) == 2) { if (mf == 1) GO_(1, 2, true) if (mf == 2) GO_(2, 2, true) if (mf == 4) GO_(4, 2, true) }
             }
-            return -3;
+            return CONV_BAD_TILING;
         }
-        if (th == 16) { if constexpr (STRIDE == 1 && KS != 5) { if (OH >= 16) GO_MF(mf, 16) } return -3; }
+        if (th == 16) { if constexpr (STRIDE == 1 && KS != 5) { if (OH >= 16) GO_MF(mf, 16) } return CONV_BAD_TILING; }
         if (th == 8) { if constexpr (KS == 5) { if (mf == 1) GO(1, 8) if (mf == 2) GO(2, 8) } else GO_MF(mf, 8) if (mf == 4) GO(4, 8) }
-        return -3;
+        return CONV_BAD_TILING;
     }
     if constexpr (KS == 5) {       // 25 taps per channel step: the variants are kept to 8-row tiles with 1, 2 or 4 output fragments
         for (int mf : {4, 2}) if (blocks(mf, 8) >= want && MOUT >= 16 * mf) { if (mf == 4) GO(4, 8) GO(2, 8) }
@@ -1167,97 +1160,39 @@ int launch_variant(const TView& xin, const GView& gin, const ConvGeom& g, const 
 #undef GO_
 }
 
+}  // namespace
+
+// Tiling override: MFVI_TUNE=mf,th,T (experiments) or the per-op choice made by mfvi_plan_autotune (ConvGeom::tune).
+int env_tune()
+{
+    static const int t = [] { int mf = 0, th = 0, T = 0; const char* e = getenv("MFVI_TUNE"); if (e) sscanf(e, "%d,%d,%d", &mf, &th, &T); return mf > 0 ? (mf | th << 8 | T << 16) : 0; }();
+    return t;
+}
+
+// The round-2 tiles of a layer the dispatch (conv_dispatch.hip) has checked the MFMA-path guards of; CONV_NOT_SERVED: no kernel for ks / stride
+int launch_conv_fwd_mfma(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int n_samples, Launch& L)
+{
+    GView none{}; int rc = CONV_NOT_SERVED;
+    if (g.ks == 3 && g.stride == 1) rc = launch_variant<3, 1, 0>(in, none, g, w, wstride, out, nullptr, 0, n_samples, L);
+    else if (g.ks == 3 && g.stride == 2) rc = launch_variant<3, 2, 0>(in, none, g, w, wstride, out, nullptr, 0, n_samples, L);
+    else if (g.ks == 1 && g.stride == 1) rc = launch_variant<1, 1, 0>(in, none, g, w, wstride, out, nullptr, 0, n_samples, L);
+    else if (g.ks == 5 && g.stride == 1) rc = launch_variant<5, 1, 0>(in, none, g, w, wstride, out, nullptr, 0, n_samples, L);
+    else if (g.ks == 5 && g.stride == 2) rc = launch_variant<5, 2, 0>(in, none, g, w, wstride, out, nullptr, 0, n_samples, L);
+    if (rc == 0) L.family = FAM_MFMA;
+    return rc;
+}
+
+// fuse: the fold in the epilogue (1x1 and 3x3 stride-1 layers; dxp = nullptr); stride-2 layers run the stride-1 kernel (zero-stuffed or by phase)
+int launch_conv_bwd_data_mfma(const GView& gy, const ConvGeom& g, const float* w, long long wstride, float* dxp, long long dxp_sstride,
+                              int n_samples, Launch& L, const FoldFuse* fuse)
+{
+    const FoldFuse ff = fuse ? *fuse : FoldFuse{}; OutDesc od{}; int rc = CONV_NOT_SERVED;      // (un-fused: an empty view, no fold target)
+    if (g.ks == 3) rc = launch_variant<3, 1, 1>(ff.x, gy, g, w, wstride, od, dxp, dxp_sstride, n_samples, L, ff);
+    else if (g.ks == 1) rc = launch_variant<1, 1, 1>(ff.x, gy, g, w, wstride, od, dxp, dxp_sstride, n_samples, L, ff);
+    else if (g.ks == 5 && !fuse) rc = launch_variant<5, 1, 1>(ff.x, gy, g, w, wstride, od, dxp, dxp_sstride, n_samples, L);
+    if (rc == 0) L.family = FAM_MFMA;
+    return rc;
+}
 #else
 }  // namespace
-#endif
-#ifndef MFVI_KERNEL_ONLY
-}  // namespace
-
-// Returns -2 when the shape is not served by the MFMA path (caller falls back to the generic kernels).
-int launch_conv_fwd_mfma(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int n_samples, hipStream_t st)
-{
-    if (g.Cin > MFVI_MAX_C || (g.Cin & 3) || (g.w_off & 3)) return -2;      // Philox blocks must tile every weight row
-    if (g.tune[0] & MFVI_TUNE_GENERIC) return -2;                           // in-kernel eps: the generic kernel draws and convolves in one launch
-    if ((long long)g.Cout * g.Ho * g.Wo >= (1LL << 31)) return -2;          // the epilogue uses 32-bit element offsets per sample
-    // aligned float4 staging: image rows, sample strides and the base pointer must be multiples of 4 floats
-    if ((g.W & 3) || g.W < 4 || (in.sstride & 3) || ((uintptr_t)in.data & 15)) return -2;
-    {   // row-phase kernels (conv_rp.hip): an explicit tiling of the plan / autotuner, or the default for the shapes they serve
-        int tn = g.tune[0] ? g.tune[0] : (env_tune() ? 0 : rp_default_tune(g, 0, n_samples));
-        if (tn & MFVI_TUNE_ST) {      // streaming forward of a narrow 1x1 layer (conv_1x1.hip): only as an explicit tiling of the plan / autotuner
-            const int rc = launch_conv1_fwd_stream(in, g, w, wstride, out, n_samples, st);
-            return rc == -2 ? -3 : rc;
-        }
-        if (tn & MFVI_TUNE_SM) {      // small-map forward (conv_small.hip): only as an explicit tiling of the plan / autotuner
-            const int rc = g.ks == 1 ? launch_conv1_fwd_small(in, g, w, wstride, out, n_samples, st) : launch_conv_fwd_small(in, g, w, wstride, out, n_samples, st);
-            return rc == -2 ? -3 : rc;
-        }
-        if (tn & MFVI_TUNE_X6) {      // bf16x6 forward (conv_x6.hip): only as an explicit tiling of the plan / autotuner
-            const int rc = launch_conv_fwd_x6(in, g, w, wstride, out, tn & (MFVI_TUNE_X6 - 1), n_samples, st);
-            if (rc != -2) return rc;
-            // no scratch for the weight pieces in this call (w = mu of the eval branch, sample_weights = 0: the plan hands the scratch over
-            // only behind a weight draw): the layer's fp32 default, not the generic kernels
-            tn = env_tune() ? 0 : rp_default_tune(g, 0, n_samples);
-        }
-        if (tn & MFVI_TUNE_RP) {
-            const int rc = launch_conv_fwd_rp(in, g, w, wstride, out, tn & (MFVI_TUNE_RP - 1), n_samples, st);
-            // an explicit tiling of the plan answers for itself (-3); a heuristic one the shape does not admit falls through to the round-2 tiles
-            if (g.tune[0] & MFVI_TUNE_RP) return rc == -2 ? -3 : rc;
-            if (rc != -2 && rc != -3) return rc;
-        }
-    }
-    GView none{};
-    if (g.ks == 3 && g.stride == 1) return launch_variant<3, 1, 0>(in, none, g, w, wstride, out, nullptr, 0, n_samples, st);
-    if (g.ks == 3 && g.stride == 2) return launch_variant<3, 2, 0>(in, none, g, w, wstride, out, nullptr, 0, n_samples, st);
-    if (g.ks == 1 && g.stride == 1) return launch_variant<1, 1, 0>(in, none, g, w, wstride, out, nullptr, 0, n_samples, st);
-    if (g.ks == 5 && g.stride == 1) return launch_variant<5, 1, 0>(in, none, g, w, wstride, out, nullptr, 0, n_samples, st);
-    if (g.ks == 5 && g.stride == 2) return launch_variant<5, 2, 0>(in, none, g, w, wstride, out, nullptr, 0, n_samples, st);
-    return -2;
-}
-
-int launch_conv_bwd_data_mfma(const GView& gy, const ConvGeom& g, const float* w, long long wstride, float* dxp, long long dxp_sstride,
-                              int n_samples, hipStream_t st, const FoldFuse* fuse)
-{
-    if (g.Cout > MFVI_MAX_C || (g.stride != 1 && !(g.stride == 2 && g.ks >= 3)) || (g.Cin & 3) || (g.w_off & 3)) return -2;
-    if (g.tune[1] & MFVI_TUNE_GENERIC) return -2;
-    if ((long long)g.Cin * (g.H + 4) * (g.W + 4) >= (1LL << 31)) return -2;   // 32-bit element offsets per sample
-    // aligned float4 (stride 2: float2) staging of the gradient and of the conv output it is normalised with
-    const int wa = g.stride == 2 ? 1 : 3;
-    if ((g.Wo & wa) || g.Wo < (wa + 1) || (gy.gstride & wa) || ((uintptr_t)gy.ga & 15) || (gy.y && ((gy.ystride & wa) || ((uintptr_t)gy.y & 15)))) return -2;
-    TView none{}; OutDesc od{};
-    if (fuse) {       // the fold runs in the epilogue: aligned float4 rows of the input tensor and of its gradient
-        if (!(g.ks == 1 || (g.ks == 3 && g.stride == 1)) || !fuse->ga || (g.W & 3) || (fuse->ga_sstride & 3) || ((uintptr_t)fuse->ga & 15)) return -2;
-        if (fuse->bsums && ((fuse->x.sstride & 3) || ((uintptr_t)fuse->x.data & 15))) return -2;
-        if (g.ks == 3 && (g.H < 4 || g.W < 4)) return -2;      // rows 1 and H-2 (columns 1 and W-2) must be distinct, interior lines
-        if (g.ks == 3) {
-            int tn = g.tune[1] ? g.tune[1] : (env_tune() ? 0 : rp_default_tune(g, 1, n_samples));
-            if (tn & MFVI_TUNE_X6) {      // bf16x6 backward-data with the fold (conv_bwd_x6.hip): only as an explicit tiling of the plan / autotuner
-                const int rc = launch_conv_bwd_data_x6(gy, g, w, wstride, tn & (MFVI_TUNE_X6 - 1), n_samples, st, *fuse);
-                if (rc != -2) return rc;
-                // no scratch for the weight pieces in this call (w = mu without a weight draw): the layer's fp32 default
-                tn = env_tune() ? 0 : rp_default_tune(g, 1, n_samples);
-                if (tn & MFVI_TUNE_RP) { const int r2 = launch_conv_bwd_data_rp(gy, g, w, wstride, tn & (MFVI_TUNE_RP - 1), n_samples, st, *fuse); if (r2 != -2 && r2 != -3) return r2; }
-                return launch_variant<3, 1, 1>(fuse->x, gy, g, w, wstride, od, nullptr, 0, n_samples, st, *fuse);
-            }
-            if (tn & MFVI_TUNE_SM) {      // small-map kernel (conv_small.hip): only as an explicit tiling of the plan / autotuner
-                const int rc = launch_conv_bwd_data_small(gy, g, w, wstride, n_samples, st, *fuse);
-                return rc == -2 ? -3 : rc;
-            }
-            if (tn & MFVI_TUNE_RP) {
-                const int rc = launch_conv_bwd_data_rp(gy, g, w, wstride, tn & (MFVI_TUNE_RP - 1), n_samples, st, *fuse);
-                if (g.tune[1]) return rc == -2 ? -3 : rc;
-                if (rc != -2 && rc != -3) return rc;      // (heuristic tiling not valid for this shape: the round-2 tiles below)
-            }
-        }
-        if (g.ks == 3) return launch_variant<3, 1, 1>(fuse->x, gy, g, w, wstride, od, nullptr, 0, n_samples, st, *fuse);
-        if (g.tune[1] & MFVI_TUNE_SM) {      // one-stage 1x1 kernel (conv_1x1.hip): only as an explicit tiling of the plan / autotuner
-            const int rc = launch_conv1_bwd_data_small(gy, g, w, wstride, n_samples, st, *fuse);
-            return rc == -2 ? -3 : rc;
-        }
-        return launch_variant<1, 1, 1>(fuse->x, gy, g, w, wstride, od, nullptr, 0, n_samples, st, *fuse);
-    }
-    if (g.ks == 3) return launch_variant<3, 1, 1>(none, gy, g, w, wstride, od, dxp, dxp_sstride, n_samples, st);
-    if (g.ks == 1) return launch_variant<1, 1, 1>(none, gy, g, w, wstride, od, dxp, dxp_sstride, n_samples, st);
-    if (g.ks == 5) return launch_variant<5, 1, 1>(none, gy, g, w, wstride, od, dxp, dxp_sstride, n_samples, st);
-    return -2;
-}
 #endif

@@ -612,18 +612,18 @@ __global__ __launch_bounds__(512, MINW) void conv_rp_kernel(RpArgs A)
 }
 
 template <int MODE, int MF, int R, bool REM, int KS, int WSH = 0>
-int launch_rp(RpArgs& A, int T, int n_samples, hipStream_t st)
+int launch_rp(RpArgs& A, int T, int n_samples, Launch& L)
 {
     using Cfg = RpCfg<R, MODE, WSH>;
     constexpr bool W32 = WSH > 0; constexpr int QPR = Cfg::QPR, NSUB = Cfg::NSUB;
     const ConvGeom& g = A.g;
     const int MOUT = MODE == 0 ? g.Cout : g.Cin;
     constexpr int CT = 16 * MF;
-    if (g.H % (W32 ? NSUB * Cfg::TH : Cfg::TH)) return -3;
+    if (g.H % (W32 ? NSUB * Cfg::TH : Cfg::TH)) return CONV_BAD_TILING;
     const int RED = MODE == 0 ? g.Cin : g.Cout;
-    if (RED % (4 * KS)) return -3;
-    if (MODE == 1 && RED / (4 * KS) < 4) return -3;       // the fold of a tile rides on stages 0..2 of the next one
-    if (REM && !((MOUT & 15) == 4 && (MOUT - 4) % CT == 0)) return -3;
+    if (RED % (4 * KS)) return CONV_BAD_TILING;
+    if (MODE == 1 && RED / (4 * KS) < 4) return CONV_BAD_TILING;       // the fold of a tile rides on stages 0..2 of the next one
+    if (REM && !((MOUT & 15) == 4 && (MOUT - 4) % CT == 0)) return CONV_BAD_TILING;
     A.tiles_x = W32 ? 1 : g.W / 64;
     A.n_tiles = W32 ? g.H / (NSUB * Cfg::TH) : A.tiles_x * (g.H / Cfg::TH);
     A.tiles_per_block = T;
@@ -632,82 +632,82 @@ int launch_rp(RpArgs& A, int T, int n_samples, hipStream_t st)
     constexpr int WCH = KS * (MF * 4 * 16 * 12 + (REM ? 4 * 4 * 12 : 0));
     const size_t dyn = sizeof(float) * 2 * WCH + sizeof(ChanFwd) * (size_t)((g.Cin + 3) & ~3) + sizeof(RpBwd) * (size_t)((g.Cout + 3) & ~3);
     constexpr int MINW = 4;
-    mfvi_tl_family = 2;
-    mfvi_launch((conv_rp_kernel<MODE, MF, R, REM, KS, MINW, WSH>), dim3(A.nx * A.ny * A.nz), dim3(512), dyn, st, A);
+    L.family = FAM_ROWPHASE;
+    mfvi_launch(L, (conv_rp_kernel<MODE, MF, R, REM, KS, MINW, WSH>), dim3(A.nx * A.ny * A.nz), dim3(512), dyn, A);
     return (int)hipGetLastError();
 }
 
 // tune code: mf | r << 8 | rem << 12 | ks << 13 | T << 16 | MFVI_TUNE_RP   (ks = k-steps per stage: 0 / 1 -> 1, 2)
 template <int MODE>
-int dispatch_rp(RpArgs& A, int tune, int n_samples, hipStream_t st)
+int dispatch_rp(RpArgs& A, int tune, int n_samples, Launch& L)
 {
     const int mf = tune & 255, r = (tune >> 8) & 15, rem = (tune >> 12) & 1, ks = max(1, (tune >> 13) & 7), T = max(1, (tune >> 16) & 255);
-#define RP_GO2(MF_, R_, KS_) if (mf == MF_ && r == R_ && ks == KS_) { if constexpr (MODE == 1) { if (rem) return launch_rp<MODE, MF_, R_, true, KS_>(A, T, n_samples, st); } if (rem) return -3; return launch_rp<MODE, MF_, R_, false, KS_>(A, T, n_samples, st); }
+#define RP_GO2(MF_, R_, KS_) if (mf == MF_ && r == R_ && ks == KS_) { if constexpr (MODE == 1) { if (rem) return launch_rp<MODE, MF_, R_, true, KS_>(A, T, n_samples, L); } if (rem) return CONV_BAD_TILING; return launch_rp<MODE, MF_, R_, false, KS_>(A, T, n_samples, L); }
 #define RP_GO(MF_, R_) RP_GO2(MF_, R_, 1)      /* two k-steps per stage (KS = 2) built and measured: no gain, register spills in backward-data; not instantiated */
     if (A.g.W == 32) {      // maps 32 wide: two image rows per 64-pixel strip
         if constexpr (MODE == 0) {
-#define RP_GO32(MF_, R_) if (mf == MF_ && r == R_ && ks == 1 && !rem) return launch_rp<0, MF_, R_, false, 1, 3>(A, T, n_samples, st);
+#define RP_GO32(MF_, R_) if (mf == MF_ && r == R_ && ks == 1 && !rem) return launch_rp<0, MF_, R_, false, 1, 3>(A, T, n_samples, L);
             RP_GO32(1, 1) RP_GO32(1, 2) RP_GO32(2, 1) RP_GO32(2, 2) RP_GO32(4, 1) RP_GO32(1, 4)
 #undef RP_GO32
         } else {
-#define RP_GO32(MF_, R_) if (mf == MF_ && r == R_ && ks == 1) { if (rem) return launch_rp<1, MF_, R_, true, 1, 3>(A, T, n_samples, st); return launch_rp<1, MF_, R_, false, 1, 3>(A, T, n_samples, st); }
+#define RP_GO32(MF_, R_) if (mf == MF_ && r == R_ && ks == 1) { if (rem) return launch_rp<1, MF_, R_, true, 1, 3>(A, T, n_samples, L); return launch_rp<1, MF_, R_, false, 1, 3>(A, T, n_samples, L); }
             RP_GO32(1, 1) RP_GO32(1, 2) RP_GO32(2, 1)
 #undef RP_GO32
         }
-        return -3;
+        return CONV_BAD_TILING;
     }
     if (A.g.W == 16) {      // maps 16 wide: four image rows per strip (a 16 x 16 map is ONE tile of 4-row groups)
         if constexpr (MODE == 0) {
-#define RP_GO16(MF_, R_) if (mf == MF_ && r == R_ && ks == 1 && !rem) return launch_rp<0, MF_, R_, false, 1, 2>(A, T, n_samples, st);
+#define RP_GO16(MF_, R_) if (mf == MF_ && r == R_ && ks == 1 && !rem) return launch_rp<0, MF_, R_, false, 1, 2>(A, T, n_samples, L);
             RP_GO16(1, 1) RP_GO16(2, 1) RP_GO16(4, 1) RP_GO16(1, 2) RP_GO16(2, 2)
 #undef RP_GO16
             // one 16 x 16 map = one tile per block and 32 stages of 4 channels: a latency chain of ~1.2 us per stage (barrier, LDS round
             // trip, load latency) with nothing else on the CU to hide it -> 2 or 4 k-steps per stage
-#define RP_GO16K(MF_, KS_) if (mf == MF_ && r == 1 && ks == KS_ && !rem) return launch_rp<0, MF_, 1, false, KS_, 2>(A, T, n_samples, st);
+#define RP_GO16K(MF_, KS_) if (mf == MF_ && r == 1 && ks == KS_ && !rem) return launch_rp<0, MF_, 1, false, KS_, 2>(A, T, n_samples, L);
             RP_GO16K(1, 2) RP_GO16K(1, 4) RP_GO16K(2, 2) RP_GO16K(2, 4)
 #undef RP_GO16K
         } else {
-#define RP_GO16K(MF_, KS_) if (mf == MF_ && r == 1 && ks == KS_) { if (rem) return launch_rp<1, MF_, 1, true, KS_, 2>(A, T, n_samples, st); return launch_rp<1, MF_, 1, false, KS_, 2>(A, T, n_samples, st); }
+#define RP_GO16K(MF_, KS_) if (mf == MF_ && r == 1 && ks == KS_) { if (rem) return launch_rp<1, MF_, 1, true, KS_, 2>(A, T, n_samples, L); return launch_rp<1, MF_, 1, false, KS_, 2>(A, T, n_samples, L); }
             RP_GO16K(1, 2) RP_GO16K(1, 4) RP_GO16K(2, 2)
 #undef RP_GO16K
-#define RP_GO16(MF_, R_) if (mf == MF_ && r == R_ && ks == 1) { if (rem) return launch_rp<1, MF_, R_, true, 1, 2>(A, T, n_samples, st); return launch_rp<1, MF_, R_, false, 1, 2>(A, T, n_samples, st); }
+#define RP_GO16(MF_, R_) if (mf == MF_ && r == R_ && ks == 1) { if (rem) return launch_rp<1, MF_, R_, true, 1, 2>(A, T, n_samples, L); return launch_rp<1, MF_, R_, false, 1, 2>(A, T, n_samples, L); }
             RP_GO16(1, 1) RP_GO16(2, 1) RP_GO16(1, 2)
 #undef RP_GO16
         }
-        return -3;
+        return CONV_BAD_TILING;
     }
     RP_GO(1, 1) RP_GO(1, 2) RP_GO(2, 1)
     if constexpr (MODE == 0) { RP_GO(2, 2) RP_GO2(4, 1, 1) RP_GO2(1, 4, 1) }       // backward-data: rows 1 / H-2 must be the last / first row of their wave (R <= 2); its out tile keeps (2, 2) / (4, 1) at one block per CU
 #undef RP_GO
 #undef RP_GO2
-    return -3;
+    return CONV_BAD_TILING;
 }
 
 }  // namespace
 
 // Returns -2 when the shape is not served by the row-phase kernels, -3 when the tiling is not valid for it.
-int launch_conv_fwd_rp(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int tune, int n_samples, hipStream_t st)
+int launch_conv_fwd_rp(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int tune, int n_samples, Launch& L)
 {
-    if (g.ks != 3 || g.stride != 1 || ((g.W & 63) && g.W != 32 && g.W != 16) || (g.H & 3) || (g.Cin & 3) || (g.w_off & 3) || g.Cin > MFVI_MAX_C) return -2;
-    if ((in.sstride & 3) || ((uintptr_t)in.data & 15) || (out.sstride & 3) || ((uintptr_t)out.data & 15)) return -2;
-    if (in.act & MFVI_ACT_SQUARE) return -2;                                          // variance convolution of the LRT layers: round-2 kernels
-    if ((long long)max(g.Cin, g.Cout) * g.H * g.W >= (1LL << 29)) return -2;          // 32-bit element offsets per sample, two flag bits
+    if (g.ks != 3 || g.stride != 1 || ((g.W & 63) && g.W != 32 && g.W != 16) || (g.H & 3) || (g.Cin & 3) || (g.w_off & 3) || g.Cin > MFVI_MAX_C) return CONV_NOT_SERVED;
+    if ((in.sstride & 3) || ((uintptr_t)in.data & 15) || (out.sstride & 3) || ((uintptr_t)out.data & 15)) return CONV_NOT_SERVED;
+    if (in.act & MFVI_ACT_SQUARE) return CONV_NOT_SERVED;                                          // variance convolution of the LRT layers: round-2 kernels
+    if ((long long)max(g.Cin, g.Cout) * g.H * g.W >= (1LL << 29)) return CONV_NOT_SERVED;          // 32-bit element offsets per sample, two flag bits
     RpArgs A{};
     A.xin = in; A.g = g; A.w = w; A.wstride = wstride; A.out = out;
-    return dispatch_rp<0>(A, tune & ~(1 << 12), n_samples, st);      // the remainder bit only concerns backward-data
+    return dispatch_rp<0>(A, tune & ~(1 << 12), n_samples, L);      // the remainder bit only concerns backward-data
 }
 
-int launch_conv_bwd_data_rp(const GView& gy, const ConvGeom& g, const float* w, long long wstride, int tune, int n_samples, hipStream_t st, const FoldFuse& fuse)
+int launch_conv_bwd_data_rp(const GView& gy, const ConvGeom& g, const float* w, long long wstride, int tune, int n_samples, Launch& L, const FoldFuse& fuse)
 {
-    if (g.ks != 3 || g.stride != 1 || ((g.W & 63) && g.W != 32 && g.W != 16) || (g.H & 3) || g.H < 4 || (g.Cin & 3) || (g.Cout & 3) || (g.w_off & 3) || g.Cout > MFVI_MAX_C || g.Cin > MFVI_MAX_C) return -2;
-    if (!fuse.ga || (fuse.ga_sstride & 3) || ((uintptr_t)fuse.ga & 15) || g.Cout < 16) return -2;      // the fold of a tile rides on stages 0..2 of the next one
-    if ((gy.gstride & 3) || ((uintptr_t)gy.ga & 15) || (gy.stats && ((gy.ystride & 3) || ((uintptr_t)gy.y & 15)))) return -2;
-    if (fuse.bsums && ((fuse.x.sstride & 3) || ((uintptr_t)fuse.x.data & 15))) return -2;
-    if ((long long)max(g.Cin, g.Cout) * g.H * g.W >= (1LL << 29)) return -2;
+    if (g.ks != 3 || g.stride != 1 || ((g.W & 63) && g.W != 32 && g.W != 16) || (g.H & 3) || g.H < 4 || (g.Cin & 3) || (g.Cout & 3) || (g.w_off & 3) || g.Cout > MFVI_MAX_C || g.Cin > MFVI_MAX_C) return CONV_NOT_SERVED;
+    if (!fuse.ga || (fuse.ga_sstride & 3) || ((uintptr_t)fuse.ga & 15) || g.Cout < 16) return CONV_NOT_SERVED;      // the fold of a tile rides on stages 0..2 of the next one
+    if ((gy.gstride & 3) || ((uintptr_t)gy.ga & 15) || (gy.stats && ((gy.ystride & 3) || ((uintptr_t)gy.y & 15)))) return CONV_NOT_SERVED;
+    if (fuse.bsums && ((fuse.x.sstride & 3) || ((uintptr_t)fuse.x.data & 15))) return CONV_NOT_SERVED;
+    if ((long long)max(g.Cin, g.Cout) * g.H * g.W >= (1LL << 29)) return CONV_NOT_SERVED;
     RpArgs A{};
     A.xin = fuse.x; A.gin = gy; A.g = g; A.w = w; A.wstride = wstride;
     A.fga = fuse.ga; A.fga_sstride = fuse.ga_sstride; A.fbsums = fuse.bsums;
-    return dispatch_rp<1>(A, tune, n_samples, st);
+    return dispatch_rp<1>(A, tune, n_samples, L);
 }
 
 // Heuristic tiling when the plan holds none (mfvi_plan_autotune times the candidates on the real tensors).  MFVI_RP=0 keeps the round-2 kernels

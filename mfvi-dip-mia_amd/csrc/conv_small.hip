@@ -261,43 +261,43 @@ __global__ __launch_bounds__(512) void conv_sm_kernel(SmArgs A)
 }  // namespace
 
 // Return -2 when the shape is not served.
-static int sm_launch(int mode, SmArgs& A, int red, int n_samples, hipStream_t st)
+static int sm_launch(int mode, SmArgs& A, int red, int n_samples, Launch& L)
 {
     const ConvGeom& g = A.g;
     const int tr = 64 / g.W;
     const int NG = (red + 15) >> 4, WP = (tr + 2) * (g.W + 2);
     A.nx = g.H / tr; A.ny = ((mode == 0 ? g.Cout : g.Cin) + 15) / 16; A.nz = n_samples; A.tr = tr; A.wsh = g.W == 8 ? 3 : 4;
     const int WPL = mode == 0 ? WP : (tr + 3 + (A.nx == 1 ? 1 : 0)) * (g.W + 4);
-    if (WP > 128 || NG * 4 > SM_NXJ || NG * 64 > SM_NWJ * 512) return -2;
+    if (WP > 128 || NG * 4 > SM_NXJ || NG * 64 > SM_NWJ * 512) return CONV_NOT_SERVED;
     const size_t lds_bytes = sizeof(float) * ((size_t)NG * WPL * 16 + (size_t)9 * NG * 256);
-    if (lds_bytes > 152 * 1024) return -2;
+    if (lds_bytes > 152 * 1024) return CONV_NOT_SERVED;
     static const hipError_t attr0 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_sm_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
     static const hipError_t attr1 = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_sm_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
     if (attr0 != hipSuccess || attr1 != hipSuccess) return (int)(attr0 != hipSuccess ? attr0 : attr1);
-    mfvi_tl_family = 4;
-    if (mode == 0) mfvi_launch(conv_sm_kernel<0>, dim3(A.nx * A.ny * A.nz), dim3(512), lds_bytes, st, A);
-    else mfvi_launch(conv_sm_kernel<1>, dim3(A.nx * A.ny * A.nz), dim3(512), lds_bytes, st, A);
+    L.family = FAM_ONE_STAGE;
+    if (mode == 0) mfvi_launch(L, conv_sm_kernel<0>, dim3(A.nx * A.ny * A.nz), dim3(512), lds_bytes, A);
+    else mfvi_launch(L, conv_sm_kernel<1>, dim3(A.nx * A.ny * A.nz), dim3(512), lds_bytes, A);
     return (int)hipGetLastError();
 }
 
-int launch_conv_fwd_small(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int n_samples, hipStream_t st)
+int launch_conv_fwd_small(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int n_samples, Launch& L)
 {
-    if (g.ks != 3 || g.stride != 1 || (g.W != 8 && g.W != 16) || (g.Cin & 3) || g.Cin > SM_MAXC || (g.Cout & 15) || (g.w_off & 3)) return -2;
-    if (g.H % (64 / g.W) || g.H < 2) return -2;
-    if ((long long)max(g.Cin, g.Cout) * g.H * g.W >= (1LL << 30)) return -2;
+    if (g.ks != 3 || g.stride != 1 || (g.W != 8 && g.W != 16) || (g.Cin & 3) || g.Cin > SM_MAXC || (g.Cout & 15) || (g.w_off & 3)) return CONV_NOT_SERVED;
+    if (g.H % (64 / g.W) || g.H < 2) return CONV_NOT_SERVED;
+    if ((long long)max(g.Cin, g.Cout) * g.H * g.W >= (1LL << 30)) return CONV_NOT_SERVED;
     SmArgs A{};
     A.xin = in; A.g = g; A.w = w; A.wstride = wstride; A.out = out;
-    return sm_launch(0, A, g.Cin, n_samples, st);
+    return sm_launch(0, A, g.Cin, n_samples, L);
 }
 
 // Backward-data with the fold of the input tensor in the epilogue (fuse.ga required, as launch_conv_bwd_data_rp).
-int launch_conv_bwd_data_small(const GView& gy, const ConvGeom& g, const float* w, long long wstride, int n_samples, hipStream_t st, const FoldFuse& fuse)
+int launch_conv_bwd_data_small(const GView& gy, const ConvGeom& g, const float* w, long long wstride, int n_samples, Launch& L, const FoldFuse& fuse)
 {
-    if (g.ks != 3 || g.stride != 1 || (g.W != 8 && g.W != 16) || (g.Cin & 3) || (g.Cout & 3) || g.Cout > SM_MAXC || (g.w_off & 3) || !fuse.ga) return -2;
-    if (g.H % (64 / g.W) || g.H < 4) return -2;      // rows 1 and H-2 must be distinct interior rows
-    if ((long long)max(g.Cin, g.Cout) * g.H * g.W >= (1LL << 30)) return -2;
+    if (g.ks != 3 || g.stride != 1 || (g.W != 8 && g.W != 16) || (g.Cin & 3) || (g.Cout & 3) || g.Cout > SM_MAXC || (g.w_off & 3) || !fuse.ga) return CONV_NOT_SERVED;
+    if (g.H % (64 / g.W) || g.H < 4) return CONV_NOT_SERVED;      // rows 1 and H-2 must be distinct interior rows
+    if ((long long)max(g.Cin, g.Cout) * g.H * g.W >= (1LL << 30)) return CONV_NOT_SERVED;
     SmArgs A{};
     A.xin = fuse.x; A.gin = gy; A.g = g; A.w = w; A.wstride = wstride;
     A.fga = fuse.ga; A.fga_sstride = fuse.ga_sstride; A.fbsums = fuse.bsums;
-    return sm_launch(1, A, g.Cout, n_samples, st);
+    return sm_launch(1, A, g.Cout, n_samples, L);
 }

@@ -23,9 +23,6 @@
 #include <type_traits>
 #include <cstdlib>
 
-thread_local float* mfvi_tl_x6w = nullptr;      // scratch of the op being launched (plan.hip), nullptr: bf16x6 forward not available
-thread_local bool mfvi_tl_x6w_ready = false;    // the scratch already holds this pass's pieces (launch_x6_split_all ran behind the weight draw)
-
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -400,14 +397,14 @@ __global__ __launch_bounds__(512, 2) void conv_fwd_x6_kernel(X6FArgs A)
 }
 
 template <int MF, int SR, bool MRG = false>
-int launch_one(X6FArgs& A, hipStream_t st)
+int launch_one(X6FArgs& A, Launch& L)
 {
     using C = X6FCfg;
     constexpr size_t lds_bytes = (size_t)C::NSLOT * C::SLOT + (size_t)(MRG ? 36 : 27) * 16 * MF * 64;
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd_x6_kernel<MF, SR, MRG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (attr != hipSuccess) return (int)attr;
-    mfvi_tl_family = 3;
-    mfvi_launch((conv_fwd_x6_kernel<MF, SR, MRG>), dim3(A.nx * A.ny * A.nz), dim3(512), lds_bytes, st, A);
+    L.family = FAM_BF16X6;
+    mfvi_launch(L, (conv_fwd_x6_kernel<MF, SR, MRG>), dim3(A.nx * A.ny * A.nz), dim3(512), lds_bytes, A);
     return (int)hipGetLastError();
 }
 
@@ -438,25 +435,25 @@ long long x6_fwd_scratch_floats(const ConvGeom& g, int n_samples)
 }
 
 // tune: mf | sr << 8 | T << 16 (| MFVI_TUNE_X6 stripped by the caller; T = strips per block).  -2: shape not served / no scratch, -3: tiling not valid.
-int launch_conv_fwd_x6(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int tune, int n_samples, hipStream_t st)
+int launch_conv_fwd_x6(const TView& in, const ConvGeom& g, const float* w, long long wstride, OutDesc out, int tune, int n_samples, Launch& L)
 {
-    float* scratch = mfvi_tl_x6w;
-    if (!scratch) return -2;
-    if (g.ks != 3 || g.stride != 1 || (g.W & 63) || g.Cin < 32 || g.Cin > MFVI_MAX_C || (g.w_off & 3)) return -2;
+    float* scratch = L.x6_scratch;
+    if (!scratch) return CONV_NOT_SERVED;
+    if (g.ks != 3 || g.stride != 1 || (g.W & 63) || g.Cin < 32 || g.Cin > MFVI_MAX_C || (g.w_off & 3)) return CONV_NOT_SERVED;
     const int r32 = g.Cin & 31;
-    if (r32 != 0 && r32 != 4) return -2;
-    if (in.act & MFVI_ACT_SQUARE) return -2;
-    if ((out.sstride & 3) || ((uintptr_t)out.data & 15)) return -2;
-    if ((long long)max(g.Cin, g.Cout) * g.H * g.W >= (1LL << 31)) return -2;
+    if (r32 != 0 && r32 != 4) return CONV_NOT_SERVED;
+    if (in.act & MFVI_ACT_SQUARE) return CONV_NOT_SERVED;
+    if ((out.sstride & 3) || ((uintptr_t)out.data & 15)) return CONV_NOT_SERVED;
+    if ((long long)max(g.Cin, g.Cout) * g.H * g.W >= (1LL << 31)) return CONV_NOT_SERVED;
     const int mf = tune & 255, sr = (tune >> 8) & 15, mrg = (tune >> 12) & 1;      // bit 12: the remainder plane rides on the last group's pass (mf = 1, Cin = 32 n + 4)
-    if ((mf != 1 && mf != 2) || sr != 8 || (g.H % sr) || (mrg && (mf != 1 || r32 == 0))) return -3;
+    if ((mf != 1 && mf != 2) || sr != 8 || (g.H % sr) || (mrg && (mf != 1 || r32 == 0))) return CONV_BAD_TILING;
     const int ncg = g.Cin / 32, rem = r32 ? 1 : 0, COp = (g.Cout + 31) / 32 * 32;
     const int n_k = wstride ? n_samples : 1;
     const long long units = (long long)(ncg * 9 + (rem ? 3 : 0)) * COp * 4;          // threads of the split kernel per sample
     X6WArgs WA{};
     WA.w = w; WA.wstride = wstride; WA.dst = reinterpret_cast<unsigned*>(scratch); WA.dstride_u4 = units * 3;
     WA.Cin = g.Cin; WA.Cout = g.Cout; WA.COp = COp; WA.ncg = ncg; WA.rem = rem; WA.w_off = g.w_off; WA.units = (int)units;
-    if (!mfvi_tl_x6w_ready) hipLaunchKernelGGL(x6_split_weights_kernel, dim3((unsigned)((units + 255) / 256), n_k), dim3(256), 0, st, WA);
+    if (!L.x6_ready) hipLaunchKernelGGL(x6_split_weights_kernel, dim3((unsigned)((units + 255) / 256), n_k), dim3(256), 0, L.st, WA);
     X6FArgs A{};
     A.in = in; A.g = g; A.out = out; A.w = w; A.wstride = wstride;
     A.wsp = reinterpret_cast<const unsigned*>(scratch); A.wsp_stride_u4 = wstride ? units * 3 : 0;
@@ -464,7 +461,7 @@ int launch_conv_fwd_x6(const TView& in, const ConvGeom& g, const float* w, long 
     const int T = max(1, (tune >> 16) & 255);
     A.strips = g.H / sr; A.tpb = T;
     A.nx = A.bands * ((A.strips + T - 1) / T); A.ny = (g.Cout + 16 * mf - 1) / (16 * mf); A.nz = n_samples;
-    if (mf == 1 && mrg) return launch_one<1, 8, true>(A, st);
-    if (mf == 1) return launch_one<1, 8>(A, st);
-    return launch_one<2, 8>(A, st);
+    if (mf == 1 && mrg) return launch_one<1, 8, true>(A, L);
+    if (mf == 1) return launch_one<1, 8>(A, L);
+    return launch_one<2, 8>(A, L);
 }

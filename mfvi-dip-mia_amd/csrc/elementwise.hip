@@ -757,7 +757,7 @@ __global__ __launch_bounds__(256) void lrt_ds2_kernel(GView gy, const float* __r
 }  // namespace
 
 int launch_finalize_dx(const FoldSrc* srcs, int n_src, const TView& x, float* ga, long long ga_sstride, double* bsums,
-                       int n_samples, hipStream_t st)
+                       int n_samples, Launch& L)
 {
     if (n_src < 1 || n_src > MAX_FOLD_SRC) { set_error("finalize_dx: %d gradient sources (1..%d supported)", n_src, MAX_FOLD_SRC); return -1; }
     for (int i = 0; i < n_src; ++i)
@@ -771,27 +771,27 @@ int launch_finalize_dx(const FoldSrc* srcs, int n_src, const TView& x, float* ga
     for (int i = 0; i < n_src; ++i) { if (srcs[i].pad > maxpad) maxpad = srcs[i].pad; any_mul |= srcs[i].mul2v; }      // the float4 kernel folds pad <= 1
     if (n_src <= 2 && !any_mul && maxpad <= 1 && (x.W & 3) == 0 && x.H >= 2 && ((x.sstride | ga_sstride) & 3) == 0 && al16(x.data) && al16(ga)) {
         dim3 grid((unsigned)((HW / 4 + 256 * V_GROUPS - 1) / (256 * V_GROUPS)), x.C, n_samples);
-        mfvi_launch(finalize_dx_vec_kernel, grid, dim3(256), 0, st, s0, s1, n_src, x, ga, ga_sstride, bsums);
+        mfvi_launch(L, finalize_dx_vec_kernel, grid, dim3(256), 0, s0, s1, n_src, x, ga, ga_sstride, bsums);
         return (int)hipGetLastError();
     }
     dim3 grid((unsigned)((HW + 256 * EW_ITEMS - 1) / (256 * EW_ITEMS)), x.C, n_samples);
     FoldSrcs S; S.n = n_src;
     for (int i = 0; i < MAX_FOLD_SRC; ++i) S.s[i] = srcs[i < n_src ? i : 0];
-    mfvi_launch(finalize_dx_kernel, grid, dim3(256), 0, st, S, x, ga, ga_sstride, bsums);
+    mfvi_launch(L, finalize_dx_kernel, grid, dim3(256), 0, S, x, ga, ga_sstride, bsums);
     return (int)hipGetLastError();
 }
 
 // One padded source + the backward-data of a 1x1 consumer with cs1 <= 8 output channels in place (finalize_dx_vec1_kernel).  -2: shape not served
 int launch_finalize_dx_inline1x1(const FoldSrc& s0, const GView& g1, const float* w1, long long w1_sstride, int cs1, const TView& x, float* ga,
-                                 long long ga_sstride, double* bsums, int n_samples, hipStream_t st)
+                                 long long ga_sstride, double* bsums, int n_samples, Launch& L)
 {
     const auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
     if (cs1 < 1 || cs1 > 8 || s0.mul2v || s0.pad > 1 || (x.W & 3) || x.H < 2 || ((x.sstride | ga_sstride | g1.gstride) & 3) || !al16(x.data) || !al16(ga) ||
-        !al16(g1.ga) || (g1.stats && (!al16(g1.y) || (g1.ystride & 3))) || g1.H != x.H || g1.W != x.W) return -2;
+        !al16(g1.ga) || (g1.stats && (!al16(g1.y) || (g1.ystride & 3))) || g1.H != x.H || g1.W != x.W) return CONV_NOT_SERVED;
     const long long HW = (long long)x.H * x.W;
     dim3 grid((unsigned)((HW / 4 + 256 * V1_GROUPS - 1) / (256 * V1_GROUPS)), x.C, n_samples);
-    if (cs1 <= 4) mfvi_launch(finalize_dx_vec1_kernel<4>, grid, dim3(256), 0, st, s0, g1, w1, w1_sstride, cs1, x, ga, ga_sstride, bsums);
-    else mfvi_launch(finalize_dx_vec1_kernel<8>, grid, dim3(256), 0, st, s0, g1, w1, w1_sstride, cs1, x, ga, ga_sstride, bsums);
+    if (cs1 <= 4) mfvi_launch(L, finalize_dx_vec1_kernel<4>, grid, dim3(256), 0, s0, g1, w1, w1_sstride, cs1, x, ga, ga_sstride, bsums);
+    else mfvi_launch(L, finalize_dx_vec1_kernel<8>, grid, dim3(256), 0, s0, g1, w1, w1_sstride, cs1, x, ga, ga_sstride, bsums);
     return (int)hipGetLastError();
 }
 
@@ -851,7 +851,7 @@ int launch_concat_up_fwd(const TView* a, const TView& b, OutDesc out, int neares
 }
 
 int launch_concat_up_bwd(const GView& gc, const TView* a, float* ga_a, long long ga_a_sstride, double* bsums_a,
-                         const TView& b, float* ga_b, long long ga_b_sstride, double* bsums_b, int nearest, int n_samples, hipStream_t st)
+                         const TView& b, float* ga_b, long long ga_b_sstride, double* bsums_b, int nearest, int n_samples, Launch& L)
 {
     const int Ct = (a ? a->C : 0) + b.C;
     // aligned pairs (float2) when every row starts on an even element; odd widths (Concat's crop) / odd strides take element loads
@@ -864,7 +864,7 @@ int launch_concat_up_bwd(const GView& gc, const TView* a, float* ga_a, long long
 #define CB_GO(TH_, TW_) { \
         const int tiles_x = (b.W + TW_ - 1) / TW_, tiles_y = (b.H + TH_ - 1) / TH_; \
         dim3 grid((unsigned)(tiles_x * tiles_y), Ct, n_samples); \
-        mfvi_launch((concat_up_bwd_kernel<TH_, TW_>), grid, dim3(256), 0, st, gc, av, a ? 1 : 0, ga_a, ga_a_sstride, bsums_a, b, ga_b, \
+        mfvi_launch(L, (concat_up_bwd_kernel<TH_, TW_>), grid, dim3(256), 0, gc, av, a ? 1 : 0, ga_a, ga_a_sstride, bsums_a, b, ga_b, \
                     ga_b_sstride, bsums_b, tiles_x, nearest, pairs); }
     if (tw == 64) CB_GO(16, 64) else if (tw == 32) CB_GO(32, 32) else CB_GO(16, 16)
 #undef CB_GO

@@ -19,9 +19,6 @@ void set_error(const char* fmt, ...)
     va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof(g_err), fmt, ap); va_end(ap);
 }
 
-thread_local hipEvent_t mfvi_tl_stop_event = nullptr;      // see mfvi_launch (common.h)
-thread_local int mfvi_tl_family = 0;
-
 namespace {
 
 struct TensorInfo {
@@ -345,13 +342,6 @@ bool check_call(const mfvi_plan* p, int n_samples, const void* ws)
     return true;
 }
 
-// MFVI_DISABLE_MFMA=1 forces the generic fp32 VALU kernels (A/B timing and parity cross-checks)
-bool use_mfma()
-{
-    static const bool on = [] { const char* e = getenv("MFVI_DISABLE_MFMA"); return !(e && e[0] == '1'); }();
-    return on;
-}
-
 // MFVI_GRAD_FROM_SLAB=1: grad_finalize reads eps * softplus(rho) as W_k - mu from the sampled-weight slab instead of re-deriving eps
 // from the counter RNG.  Measured slower on MI355X (87 vs 72 us: the extra 66 MB of loads cost more than the Philox work they save),
 // kept as an A/B switch.
@@ -377,24 +367,13 @@ bool grad_from_slab()
 
 // conv2d(reflection_pad(view), w, b) with EXPLICIT float32 weights (w_base + g.w_off, bias at w_base + g.b_off), no sampling: the two
 // convolutions of a local-reparameterisation layer.  MFMA kernel when the shape is served, else the generic one (w = "mu", eval branch).
-int conv_fwd_plain(const TView& v, const ConvGeom& g, const float* w_base, OutDesc od, int n, hipStream_t st)
-{
-    int rc = use_mfma() ? launch_conv_fwd_mfma(v, g, w_base, 0, od, n, st) : -2;
-    if (rc == -2 || rc == -3) { RngKey none{}; rc = launch_conv_fwd(v, g, w_base, w_base, none, 0, od, n, st); }
-    return rc;
-}
-int conv_bwd_data_plain(const GView& gy, const ConvGeom& g, const float* w_base, float* dxp, long long per, int n, hipStream_t st)
-{
-    int rc = use_mfma() ? launch_conv_bwd_data_mfma(gy, g, w_base, 0, dxp, per, n, st) : -2;
-    if (rc == -2 || rc == -3) { RngKey none{}; rc = launch_conv_bwd_data(gy, g, w_base, w_base, none, 0, dxp, per, n, st); }
-    return rc;
-}
+ConvWeights plain_weights(const float* w_base) { return ConvWeights{w_base, 0, w_base, w_base, RngKey{}, 0}; }
 
 // Gradient wrt tensor `tid` once every consumer has written its padded input gradient: reflection-pad adjoint fold, sum over the
 // consumers (an LRT consumer contributes two sources, the variance branch with the factor 2 * view(x)), LeakyReLU', BN-backward sums.
 // inline_op >= 0: that consumer (a narrow 1x1 convolution) wrote no padded gradient — its backward-data is formed inside the fold from its
 // output gradient gy1 and its weights w1 (launch_finalize_dx_inline1x1); -2 from there: the caller launches the consumer after all
-int fold_consumers(mfvi_plan* plan, const Ctx& c, int tid, const TView& xin, float* dz, int sample_weights, int op_index, int n_samples, hipStream_t st,
+int fold_consumers(mfvi_plan* plan, const Ctx& c, int tid, const TView& xin, float* dz, int sample_weights, int op_index, int n_samples, Launch& L,
                    int inline_op = -1, const GView* gy1 = nullptr, const float* w1 = nullptr, long long w1_sstride = 0)
 {
     const TensorInfo& x = plan->t[tid];
@@ -407,13 +386,40 @@ int fold_consumers(mfvi_plan* plan, const Ctx& c, int tid, const TView& xin, flo
         if (co.d.type == MFVI_OP_CONV_LRT && sample_weights) srcs[ns++] = FoldSrc{c.farena() + co.scratch2_off, per, Pc, 1};
     }
     float* ga = (tid == plan->input) ? dz : c.farena() + x.ga_off;
-    ProfScope ps(plan, op_index, PASS_FINALIZE, st);
+    ProfScope ps(plan, op_index, PASS_FINALIZE, L.st);
     if (inline_op >= 0) {
-        if (ns != 1) return -2;
+        if (ns != 1) return CONV_NOT_SERVED;
         const OpInfo& io = plan->ops[inline_op];
-        return launch_finalize_dx_inline1x1(srcs[0], *gy1, w1 + io.g.w_off, w1_sstride, io.g.Cout, xin, ga, x.numel, x.d.has_bn ? c.bsums() + x.stats_off : nullptr, n_samples, st);
+        return launch_finalize_dx_inline1x1(srcs[0], *gy1, w1 + io.g.w_off, w1_sstride, io.g.Cout, xin, ga, x.numel, x.d.has_bn ? c.bsums() + x.stats_off : nullptr, n_samples, L);
     }
-    return launch_finalize_dx(srcs, ns, xin, ga, x.numel, x.d.has_bn ? c.bsums() + x.stats_off : nullptr, n_samples, st);
+    return launch_finalize_dx(srcs, ns, xin, ga, x.numel, x.d.has_bn ? c.bsums() + x.stats_off : nullptr, n_samples, L);
+}
+
+// Weight pieces of the layers of `tab` (their forward / backward-data runs on a bf16x6 kernel in this pass): one launch behind the draw for all of
+// them.  The device table is uploaded when it differs from the plan's copy of the last upload (tilings change only when the plan is retuned).
+template <typename E, typename F>
+int x6_split_pass(const std::vector<E>& tab, E** dev, std::vector<E>* uploaded, size_t capacity, hipStream_t st, const char* pass, F split_all)
+{
+    if (tab.empty()) return 0;
+    hipError_t e = hipSuccess;
+    if (!*dev) e = hipMalloc((void**)dev, sizeof(E) * capacity);
+    const bool same = tab.size() == uploaded->size() && memcmp(tab.data(), uploaded->data(), sizeof(E) * tab.size()) == 0;
+    if (e == hipSuccess && !same) {      // (copied from the plan's own vector: it outlives the asynchronous copy)
+        if (!uploaded->empty()) (void)hipStreamSynchronize(st);      // a previous upload may still be reading the vector
+        *uploaded = tab;
+        e = hipMemcpyAsync(*dev, uploaded->data(), sizeof(E) * tab.size(), hipMemcpyHostToDevice, st);
+    }
+    if (e != hipSuccess) { set_error("%s: weight-piece table setup failed: %s", pass, hipGetErrorString(e)); return (int)e; }
+    const int rc = split_all(*dev);
+    if (rc) set_error("%s: weight-piece launch failed: %s", pass, hipGetErrorString((hipError_t)rc));
+    return rc;
+}
+
+// The conv's input feeds nothing else: backward-data with the fold in its epilogue (no scratch round trip, no finalize_dx launch; 3x3 stride-1
+// layers compute on the un-padded domain with the reflection adjoint on the pixel operand).  One predicate for mfvi_backward and the autotuner
+bool fused_fold(const mfvi_plan& p, const OpInfo& o, bool need_dx)
+{
+    return need_dx && (o.g.ks == 1 || (o.g.ks == 3 && o.g.stride == 1 && fold_fusion3_on())) && p.t[o.d.in0].consumers.size() == 1 && use_mfma() && fold_fusion_on();
 }
 
 RngKey base_key(uint64_t seed, uint32_t step, uint32_t k0, const int32_t* step_dev = nullptr)
@@ -609,21 +615,12 @@ int mfvi_forward(mfvi_plan* plan, const void* mu_v, const void* rho_v, const flo
                 X6SplitEntry e; if (!x6_split_entry(o.g, o.x6w_off, &e)) continue;
                 e.first_block = nb; nb += (e.units + 255) / 256; tab.push_back(e);
             }
-        if (!tab.empty()) {
-            hipError_t e = hipSuccess;
-            if (!plan->x6_dev) e = hipMalloc((void**)&plan->x6_dev, sizeof(X6SplitEntry) * plan->ops.size());
-            const bool same = tab.size() == plan->x6_uploaded.size() && memcmp(tab.data(), plan->x6_uploaded.data(), sizeof(X6SplitEntry) * tab.size()) == 0;
-            if (e == hipSuccess && !same) {      // (copied from the plan's own vector: it outlives the asynchronous copy)
-                plan->x6_uploaded = tab;
-                e = hipMemcpyAsync(plan->x6_dev, plan->x6_uploaded.data(), sizeof(X6SplitEntry) * tab.size(), hipMemcpyHostToDevice, st);
-            }
-            if (e != hipSuccess) { set_error("forward: weight-piece table setup failed: %s", hipGetErrorString(e)); return (int)e; }
-            const int rc = launch_x6_split_all(plan->x6_dev, (int)tab.size(), nb, c.wsamp(), sample_weights ? plan->n_vi : 0, sample_weights ? n_samples : 1, c.farena(), st);
-            if (rc) { set_error("forward: weight-piece launch failed: %s", hipGetErrorString((hipError_t)rc)); return rc; }
-            x6_ready = true;
-        }
+        const int rc = x6_split_pass(tab, &plan->x6_dev, &plan->x6_uploaded, plan->ops.size(), st, "forward", [&](const X6SplitEntry* dev) {
+            return launch_x6_split_all(dev, (int)tab.size(), nb, c.wsamp(), sample_weights ? plan->n_vi : 0, sample_weights ? n_samples : 1, c.farena(), st); });
+        if (rc) return rc;
+        x6_ready = !tab.empty();
     }
-    const float* wsrc = presample ? c.wsamp() : mu; const long long wstride = (presample && sample_weights) ? plan->n_vi : 0;
+    const ConvWeights W{presample ? c.wsamp() : mu, (presample && sample_weights) ? plan->n_vi : 0, mu, rho, key, sample_weights};
     // A skip-branch convolution (its only consumer is a later concat) on a map of up to MFVI_FWD_FORK pixels (default 128 x 128; 0 = never)
     // runs on the plan's side stream beside the down path of its scale and is joined in front of that concat: at those sizes both are
     // latency-bound launches that leave most of the chip idle (with the events on the kernels' packets: 3.306 ms per iteration without,
@@ -644,7 +641,7 @@ int mfvi_forward(mfvi_plan* plan, const void* mu_v, const void* rho_v, const flo
     // launch, the join event on the forked launch itself
     static const bool on_packet_env = [] { const char* e = getenv("MFVI_FORK_ON_PACKET"); return !(e && e[0] == '0'); }();
     const bool on_packet = on_packet_env && !plan->capture_mode;
-    hipEvent_t pre_ev = nullptr; size_t pre_for = (size_t)-1; bool pre_done = false; int pre_idx = -1;
+    hipEvent_t pre_ev = nullptr; size_t pre_for = (size_t)-1; bool pre_done = false;
     for (size_t i = 0; i < plan->ops.size(); ++i) {
         const OpInfo& o = plan->ops[i];
         const TensorInfo& y = plan->t[o.d.out];
@@ -668,52 +665,46 @@ int mfvi_forward(mfvi_plan* plan, const void* mu_v, const void* rho_v, const flo
         }
         pre_for = (size_t)-1;
         hipEvent_t ej = nullptr; int ej_idx = -1; bool armed = false;
+        Launch L{stc};      // this op's launches: its stream, the event riding on them, its bf16x6 weight pieces
         if (stc != st) {           // forked: its completion event rides on its own launch
             const hipError_t e = fwd_event(&ej);
             if (e != hipSuccess) { set_error("forward: fork failed: %s", hipGetErrorString(e)); return (int)e; }
             ej_idx = (int)n_fev - 1;
-            if (on_packet && plan->prof_mode != 1) { mfvi_tl_stop_event = ej; armed = true; }
+            if (on_packet && plan->prof_mode != 1) { L.stop = ej; armed = true; }
         } else if (on_packet && plan->prof_mode != 1 && o.d.type != MFVI_OP_CONV_LRT && forks(i + 1)) {
             const hipError_t e = fwd_event(&pre_ev);
             if (e != hipSuccess) { set_error("forward: fork failed: %s", hipGetErrorString(e)); return (int)e; }
-            pre_for = i + 1; pre_idx = (int)n_fev - 1; (void)pre_idx;
-            mfvi_tl_stop_event = pre_ev; armed = true;
+            pre_for = i + 1;
+            L.stop = pre_ev; armed = true;
         }
-        hipStream_t st_main = st; (void)st_main;
         {
-        hipStream_t st = stc;      // (shadows the caller's stream for this op's launches)
-        ProfScope ps(plan, (int)i, PASS_FWD, st);
+        ProfScope ps(plan, (int)i, PASS_FWD, stc);
         if (o.d.type == MFVI_OP_CONV_LRT) {
             // LRTLayer.forward (reparam_layers.py:59-72): act_mu = conv(v, mu, mu_b); training: + sqrt(1e-16 + conv(v^2, sigma^2, sigma_b^2)) * eps
             if (!mu) { set_error("forward: local-reparameterisation layers take float32 parameters"); return -1; }
-            if (!sample_weights) rc = conv_fwd_plain(c.view(o.d.in0), o.g, mu, od, n_samples, st);
+            if (!sample_weights) rc = conv_forward(L, c.view(o.d.in0), o.g, plain_weights(mu), od, n_samples);
             else {
                 OutDesc oa; oa.data = c.farena() + plan->lrt_tmp_off; oa.sstride = y.numel; oa.stats = nullptr;
                 OutDesc os; os.data = c.farena() + o.s2_off; os.sstride = y.numel; os.stats = nullptr;
                 TView v2 = c.view(o.d.in0); v2.act |= MFVI_ACT_SQUARE;
-                rc = conv_fwd_plain(c.view(o.d.in0), o.g, mu, oa, n_samples, st);
-                if (!rc) rc = conv_fwd_plain(v2, o.g, c.farena() + plan->sig2_off, os, n_samples, st);
-                if (!rc) rc = launch_lrt_combine(oa.data, os.data, y.numel, y.d.C, (long long)y.d.H * y.d.W, key, o.g.layer_id, od, n_samples, st);
+                rc = conv_forward(L, c.view(o.d.in0), o.g, plain_weights(mu), oa, n_samples);
+                if (!rc) rc = conv_forward(L, v2, o.g, plain_weights(c.farena() + plan->sig2_off), os, n_samples);
+                if (!rc) rc = launch_lrt_combine(oa.data, os.data, y.numel, y.d.C, (long long)y.d.H * y.d.W, key, o.g.layer_id, od, n_samples, stc);
             }
         } else if (o.d.type == MFVI_OP_CONV) {
-            mfvi_tl_x6w = (presample && o.x6w_off >= 0) ? c.farena() + o.x6w_off : nullptr; mfvi_tl_x6w_ready = x6_ready;
-            mfvi_tl_family = 1;
-            rc = use_mfma() ? launch_conv_fwd_mfma(c.view(o.d.in0), o.g, wsrc, wstride, od, n_samples, st) : -2;
-            mfvi_tl_x6w = nullptr; mfvi_tl_x6w_ready = false;
-            o.family[0] = (rc == -2 || rc == -3) ? 0 : mfvi_tl_family;
-            if ((rc == -2 || rc == -3) && !mu) { set_error("forward: op %d needs the generic fp32 kernels, which bf16 parameters reach only for layers outside the sampling table (use H, W multiples of 4)", (int)i); if (plan->side) (void)hipStreamSynchronize(plan->side); return -1; }
-            if (rc == -2 || rc == -3) rc = launch_conv_fwd(c.view(o.d.in0), o.g, mu, rho, key, sample_weights, od, n_samples, st);
+            if (presample && o.x6w_off >= 0) { L.x6_scratch = c.farena() + o.x6w_off; L.x6_ready = x6_ready; }
+            rc = conv_forward(L, c.view(o.d.in0), o.g, W, od, n_samples);
+            o.family[0] = L.family;
         } else {
             TView a; if (o.d.in0 >= 0) a = c.view(o.d.in0);
-            rc = launch_concat_up_fwd(o.d.in0 >= 0 ? &a : nullptr, c.view(o.d.in1), od, o.d.up_mode == MFVI_UP_NEAREST, n_samples, st);
+            rc = launch_concat_up_fwd(o.d.in0 >= 0 ? &a : nullptr, c.view(o.d.in1), od, o.d.up_mode == MFVI_UP_NEAREST, n_samples, stc);
         }
         if (rc) {      // forked skip-branch work may still be writing activations / BN statistics: join it before handing the buffers back
-            mfvi_tl_stop_event = nullptr; if (rc > 0) set_error("forward: op %d launch failed: %s", (int)i, hipGetErrorString((hipError_t)rc));
+            if (rc > 0) set_error("forward: op %d launch failed: %s", (int)i, hipGetErrorString((hipError_t)rc));
             if (plan->side) (void)hipStreamSynchronize(plan->side);
             return rc; }
         }
-        const bool consumed = armed && mfvi_tl_stop_event == nullptr;      // the event went out on the launch's packet
-        mfvi_tl_stop_event = nullptr;
+        const bool consumed = armed && L.stop == nullptr;      // the event went out on the launch's packet
         if (stc != st) {           // forked: its completion event, waited for in front of the consumer
             if (!consumed) {
                 const hipError_t e = hipEventRecord(ej, stc);
@@ -764,7 +755,7 @@ int mfvi_backward(mfvi_plan* plan, const void* mu_v, const void* rho_v, const fl
     // one use per draw: the parameters are updated in place in the same buffers, so a later backward with the same counters (a second
     // backward through a retained graph, a caller re-using a step index after an optimizer step) must re-draw from what mu / rho hold now
     plan->samp_n = 0;
-    const float* wsrc = presample ? c.wsamp() : mu; const long long wstride = (presample && sample_weights) ? plan->n_vi : 0;
+    const ConvWeights W{presample ? c.wsamp() : mu, (presample && sample_weights) ? plan->n_vi : 0, mu, rho, key, sample_weights};
     bool x6b_ready = false;
     if (presample) {      // weight pieces of the layers whose backward-data runs on the bf16x6 kernel: one launch in front of the pass
         std::vector<X6BSplitEntry> tab; int nb = 0;
@@ -773,20 +764,10 @@ int mfvi_backward(mfvi_plan* plan, const void* mu_v, const void* rho_v, const fl
                 X6BSplitEntry e; if (!x6b_split_entry(o.g, o.x6bw_off, &e)) continue;
                 e.first_block = nb; nb += (e.units + e.rem_units + 255) / 256; tab.push_back(e);
             }
-        if (!tab.empty()) {
-            hipError_t e = hipSuccess;
-            if (!plan->x6b_dev) e = hipMalloc((void**)&plan->x6b_dev, sizeof(X6BSplitEntry) * plan->ops.size());
-            const bool same = tab.size() == plan->x6b_uploaded.size() && memcmp(tab.data(), plan->x6b_uploaded.data(), sizeof(X6BSplitEntry) * tab.size()) == 0;
-            if (e == hipSuccess && !same) {
-                if (!plan->x6b_uploaded.empty()) (void)hipStreamSynchronize(st);      // a previous upload may still be reading the vector
-                plan->x6b_uploaded = tab;
-                e = hipMemcpyAsync(plan->x6b_dev, plan->x6b_uploaded.data(), sizeof(X6BSplitEntry) * tab.size(), hipMemcpyHostToDevice, st);
-            }
-            if (e != hipSuccess) { set_error("backward: weight-piece table setup failed: %s", hipGetErrorString(e)); return (int)e; }
-            const int rc = launch_x6b_split_all(plan->x6b_dev, (int)tab.size(), nb, c.wsamp(), sample_weights ? plan->n_vi : 0, sample_weights ? n_samples : 1, c.farena(), st);
-            if (rc) { set_error("backward: weight-piece launch failed: %s", hipGetErrorString((hipError_t)rc)); return rc; }
-            x6b_ready = true;
-        }
+        const int rc = x6_split_pass(tab, &plan->x6b_dev, &plan->x6b_uploaded, plan->ops.size(), st, "backward", [&](const X6BSplitEntry* dev) {
+            return launch_x6b_split_all(dev, (int)tab.size(), nb, c.wsamp(), sample_weights ? plan->n_vi : 0, sample_weights ? n_samples : 1, c.farena(), st); });
+        if (rc) return rc;
+        x6b_ready = !tab.empty();
     }
     std::vector<GradFinEntry> fin; int fin_blocks = 0;      // layers whose dW went to partial slabs in this pass
     // side stream for the backward-weight kernels (MFVI_SIDE_STREAM=0: everything on the caller's stream)
@@ -808,7 +789,7 @@ int mfvi_backward(mfvi_plan* plan, const void* mu_v, const void* rho_v, const fl
         side = plan->side;
     }
     // The fork event of the NEXT op's backward-weight kernel rides on the packet of this op's last launch on the caller's stream when that
-    // launch goes through mfvi_launch (armed right before it; a launcher that takes another path leaves it armed and the fork falls back to
+    // launch goes through mfvi_launch (armed on the op's Launch right before it; a launcher that takes another path leaves it armed and the fork falls back to
     // hipEventRecord).  MFVI_FORK_ON_PACKET=0: always hipEventRecord.
     static const bool fork_on_packet_env = [] { const char* e = getenv("MFVI_FORK_ON_PACKET"); return !(e && e[0] == '0'); }();
     const bool fork_on_packet = fork_on_packet_env && !plan->capture_mode;
@@ -819,19 +800,19 @@ int mfvi_backward(mfvi_plan* plan, const void* mu_v, const void* rho_v, const fl
         const bool bww_only_j = (oj.d.in0 == plan->input) && dz == nullptr;
         return !bww_only_j && (long long)oj.g.Ho * oj.g.Wo <= side_maxpix;
     };
-    auto arm = [&](int i_cur) -> int {       // call right before the LAST launch of op i_cur on `st`
-        armed_idx = -1; mfvi_tl_stop_event = nullptr;
+    auto arm = [&](Launch& L, int i_cur) -> int {       // call right before the LAST launch of op i_cur on `st`
+        armed_idx = -1; L.stop = nullptr;
         if (!fork_on_packet || plan->prof_mode == 1 || !will_fork(i_cur - 1)) return 0;      // (mode 1 brackets every launch with its own events)
         if (n_fork == plan->fork_events.size()) {
             hipEvent_t ev; const hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
             if (e != hipSuccess) { set_error("backward: event creation failed: %s", hipGetErrorString(e)); return (int)e; }
             plan->fork_events.push_back(ev);
         }
-        mfvi_tl_stop_event = plan->fork_events[n_fork]; armed_idx = (int)n_fork;
+        L.stop = plan->fork_events[n_fork]; armed_idx = (int)n_fork;
         return 0;
     };
-    auto settle = [&]() {                     // after that launch: consumed (the event is on the kernel's packet) or not
-        if (mfvi_tl_stop_event) { mfvi_tl_stop_event = nullptr; armed_idx = -1; }
+    auto settle = [&](Launch& L) {            // after that launch: consumed (the event is on the kernel's packet) or not
+        if (L.stop) { L.stop = nullptr; armed_idx = -1; }
     };
     // reduction of the partial dW slabs of the layers collected in `fin` into dmu / drho, on stream fs from the device table tab
     bool bn_done = false;      // the BatchNorm parameter gradients went out with the last grad_finalize launch
@@ -867,6 +848,7 @@ int mfvi_backward(mfvi_plan* plan, const void* mu_v, const void* rho_v, const fl
     for (int i = (int)plan->ops.size() - 1; i >= 0; --i) {
         const OpInfo& o = plan->ops[i];
         int rc = 0;
+        Launch L{st};      // this op's launches on the caller's stream
         if (o.d.type == MFVI_OP_CONV_LRT) {
             // autograd of LRTLayer.forward: d act_mu = dy, d act_var = dy * eps / (2 std); the two convolutions' weight gradients go to
             // d mu and (through sigma^2 = softplus(rho)^2) to d rho; their input gradients meet in the fold, the variance branch with
@@ -883,7 +865,7 @@ int mfvi_backward(mfvi_plan* plan, const void* mu_v, const void* rho_v, const fl
             { ProfScope ps(plan, i, PASS_BWD_WEIGHT, st);
               rc = launch_conv_bwd_weight(xin, gy, o.g, rho, none, 0, dmu, drho, n_samples, st); }          // d mu, d mu_b
             if (!rc && need_dx) { ProfScope ps(plan, i, PASS_BWD_DATA, st);
-              rc = conv_bwd_data_plain(gy, o.g, mu, c.farena() + o.scratch_off, per, n_samples, st); }
+              rc = conv_backward_data(L, gy, o.g, plain_weights(mu), c.farena() + o.scratch_off, per, n_samples); }
             if (!rc && sample_weights) {
                 float* ds2 = c.farena() + plan->lrt_tmp_off;
                 rc = launch_lrt_ds2(gy, c.farena() + o.s2_off, yt.numel, key, o.g.layer_id, ds2, n_samples, st);
@@ -894,9 +876,9 @@ int mfvi_backward(mfvi_plan* plan, const void* mu_v, const void* rho_v, const fl
                 if (!rc) { ProfScope ps(plan, i, PASS_BWD_WEIGHT, st);
                   rc = launch_conv_bwd_weight(v2, g2, o.g, rho, none, 0, dsig2, dsig2, n_samples, st); }    // d sigma^2 (weights and bias variance)
                 if (!rc && need_dx) { ProfScope ps(plan, i, PASS_BWD_DATA, st);
-                  rc = conv_bwd_data_plain(g2, o.g, c.farena() + plan->sig2_off, c.farena() + o.scratch2_off, per, n_samples, st); }
+                  rc = conv_backward_data(L, g2, o.g, plain_weights(c.farena() + plan->sig2_off), c.farena() + o.scratch2_off, per, n_samples); }
             }
-            if (!rc && need_dx && x.consumers.front() == i) rc = fold_consumers(plan, c, o.d.in0, xin, dz, sample_weights, i, n_samples, st);
+            if (!rc && need_dx && x.consumers.front() == i) rc = fold_consumers(plan, c, o.d.in0, xin, dz, sample_weights, i, n_samples, L);
         } else
         if (o.d.type == MFVI_OP_CONV) {
             const GView gy = c.gview(o.d.out, dout);
@@ -921,42 +903,36 @@ int mfvi_backward(mfvi_plan* plan, const void* mu_v, const void* rho_v, const fl
             armed_idx = -1;
             { ProfScope ps(plan, i, PASS_BWD_WEIGHT, sw);
               int strips = 0;
+              Launch Lw{sw};
               const bool arm_join = fork_on_packet && plan->prof_mode != 1 && sw != st && i == last_fork_op;
-              if (arm_join) mfvi_tl_stop_event = plan->join_event;
-              mfvi_tl_family = 1;
-              rc = use_mfma() ? launch_conv_bwd_weight_mfma(xin, gy, o.g, BwwPart{c.farena() + o.part_off, o.part_stride, o.max_strips}, &strips, n_samples, sw) : -2;
-              o.family[2] = (rc == -2 || rc == -3) ? 0 : mfvi_tl_family;
-              if (arm_join) { join_on_packet = mfvi_tl_stop_event == nullptr; mfvi_tl_stop_event = nullptr; }
-              if (rc == 0) {
+              if (arm_join) Lw.stop = plan->join_event;
+              rc = conv_backward_weight(Lw, xin, gy, o.g, W, BwwPart{c.farena() + o.part_off, o.part_stride, o.max_strips}, &strips, dmu, drho, n_samples);
+              o.family[2] = Lw.family;
+              if (arm_join) join_on_packet = Lw.stop == nullptr;
+              if (rc == 0 && Lw.family != FAM_GENERIC) {      // the gradient went to partial slabs: grad_finalize reduces them
                   GradFinEntry e{};
                   e.w_off = o.g.w_off; e.b_off = o.g.b_off; e.part_off = o.part_off; e.stride = o.part_stride;
                   e.n_w = o.g.Cout * o.g.Cin * o.g.ks * o.g.ks; e.n_b = o.g.b_off >= 0 ? o.g.Cout : 0; e.strips = strips; e.layer_id = o.g.layer_id;
                   e.first_block = fin_blocks;
                   fin_blocks += ((e.n_w >> 2) + ((e.n_b + 3) >> 2) + GRAD_FIN_QUADS - 1) / GRAD_FIN_QUADS;
                   fin.push_back(e);
-              }
-              if ((rc == -2 || rc == -3) && !mu) { set_error("backward: op %d needs the generic fp32 kernels, which bf16 parameters reach only for layers outside the sampling table", i); rc = -1; }
-              if (rc == -2 || rc == -3) rc = launch_conv_bwd_weight(xin, gy, o.g, rho, key, sample_weights, dmu, drho, n_samples, sw); }
+              } }
             const bool need_dx = (o.d.in0 != plan->input) || dz != nullptr;
             if (!rc && need_dx) {
                 const int P = o.g.ks / 2;
                 const long long per = (long long)o.g.Cin * (o.g.H + 2 * P) * (o.g.W + 2 * P);
                 const TensorInfo& x = plan->t[o.d.in0];
                 bool folded = false;
-                if ((o.g.ks == 1 || (o.g.ks == 3 && o.g.stride == 1 && fold_fusion3_on())) && x.consumers.size() == 1 && use_mfma() && fold_fusion_on()) {
-                    // the conv's input feeds nothing else: backward-data with the fold in its epilogue (no scratch round trip, no finalize_dx
-                    // launch); 3x3 stride-1 layers compute on the un-padded domain with the reflection adjoint on the pixel operand
+                if (fused_fold(*plan, o, need_dx)) {
                     FoldFuse ff; ff.x = xin; ff.ga = (o.d.in0 == plan->input) ? dz : c.farena() + x.ga_off; ff.ga_sstride = x.numel;
                     ff.bsums = x.d.has_bn ? c.bsums() + x.stats_off : nullptr;
                     ProfScope ps(plan, i, PASS_BWD_DATA, st);
-                    { const int ra = arm(i); if (ra) return ra; }
-                    mfvi_tl_family = 1;
-                    mfvi_tl_x6bw = (presample && o.x6bw_off >= 0) ? c.farena() + o.x6bw_off : nullptr; mfvi_tl_x6bw_ready = x6b_ready;
-                    const int r2 = launch_conv_bwd_data_mfma(gy, o.g, wsrc, wstride, nullptr, 0, n_samples, st, &ff);
-                    mfvi_tl_x6bw = nullptr; mfvi_tl_x6bw_ready = false;
-                    settle();
-                    if (r2 == 0) o.family[1] = mfvi_tl_family;
-                    if (r2 == 0) folded = true; else { armed_idx = -1; if (r2 != -2 && r2 != -3) rc = r2; }
+                    { const int ra = arm(L, i); if (ra) return ra; }
+                    if (presample && o.x6bw_off >= 0) { L.x6_scratch = c.farena() + o.x6bw_off; L.x6_ready = x6b_ready; }
+                    const int r2 = conv_backward_data(L, gy, o.g, W, nullptr, 0, n_samples, &ff);
+                    settle(L);
+                    if (r2 == 0) { folded = true; o.family[1] = L.family; }
+                    else { armed_idx = -1; if (!conv_declined(r2)) rc = r2; }
                 }
                 const bool fold_here = x.consumers.front() == i;
                 // The tensor's other consumer has written its padded gradient and this one is a narrow 1x1 convolution (the 4-channel skip
@@ -967,25 +943,22 @@ int mfvi_backward(mfvi_plan* plan, const void* mu_v, const void* rho_v, const fl
                     plan->ops[x.consumers.back()].d.type == MFVI_OP_CONV && use_mfma() &&
                     (presample ? (!(o.g.Cin & 3) && !(o.g.w_off & 3) && o.g.Cin <= MFVI_MAX_C) : (!sample_weights && mu != nullptr))) {      // (its weights are in the slab, or w = mu)
                     ProfScope ps(plan, i, PASS_BWD_DATA, st);      // (booked on the op's backward-data slot: the fold now holds both)
-                    { const int ra = arm(i); if (ra) return ra; }
-                    const int r2 = fold_consumers(plan, c, o.d.in0, xin, dz, sample_weights, i, n_samples, st, i, &gy, wsrc, wstride);
-                    settle();
-                    if (r2 == 0) { folded = true; o.family[1] = 5; }
-                    else { armed_idx = -1; if (r2 != -2) rc = r2; }
+                    { const int ra = arm(L, i); if (ra) return ra; }
+                    const int r2 = fold_consumers(plan, c, o.d.in0, xin, dz, sample_weights, i, n_samples, L, i, &gy, W.w, W.wstride);
+                    settle(L);
+                    if (r2 == 0) { folded = true; o.family[1] = FAM_FOLD_SKIP; }
+                    else { armed_idx = -1; if (r2 != CONV_NOT_SERVED) rc = r2; }
                 }
                 if (!rc && !folded) {
                   ProfScope ps(plan, i, PASS_BWD_DATA, st);
-                  if (!fold_here) { const int ra = arm(i); if (ra) return ra; }      // no fold behind it: this is the op's last launch on `st`
-                  mfvi_tl_family = 1;
-                  rc = use_mfma() ? launch_conv_bwd_data_mfma(gy, o.g, wsrc, wstride, c.farena() + o.scratch_off, per, n_samples, st) : -2;
-                  o.family[1] = (rc == -2 || rc == -3) ? 0 : mfvi_tl_family;
-                  if (!fold_here) { settle(); if (rc) armed_idx = -1; }
-                  if ((rc == -2 || rc == -3) && !mu) { set_error("backward: op %d needs the generic fp32 kernels, which bf16 parameters reach only for layers outside the sampling table", i); rc = -1; }
-                  if (rc == -2 || rc == -3) rc = launch_conv_bwd_data(gy, o.g, mu, rho, key, sample_weights, c.farena() + o.scratch_off, per, n_samples, st); }
+                  if (!fold_here) { const int ra = arm(L, i); if (ra) return ra; }      // no fold behind it: this is the op's last launch on `st`
+                  rc = conv_backward_data(L, gy, o.g, W, c.farena() + o.scratch_off, per, n_samples);
+                  o.family[1] = L.family;
+                  if (!fold_here) { settle(L); if (rc) armed_idx = -1; } }
                 if (!rc && !folded && fold_here) {         // all consumers of in0 have run: fold + act' + BN sums
-                    { const int ra = arm(i); if (ra) return ra; }
-                    rc = fold_consumers(plan, c, o.d.in0, xin, dz, sample_weights, i, n_samples, st);
-                    settle();
+                    { const int ra = arm(L, i); if (ra) return ra; }
+                    rc = fold_consumers(plan, c, o.d.in0, xin, dz, sample_weights, i, n_samples, L);
+                    settle(L);
                 }
             }
         } else {
@@ -997,13 +970,12 @@ int mfvi_backward(mfvi_plan* plan, const void* mu_v, const void* rho_v, const fl
                 a = c.view(o.d.in0); ga_a = c.farena() + ta.ga_off; sa = ta.numel; bs_a = ta.d.has_bn ? c.bsums() + ta.stats_off : nullptr;
             }
             ProfScope ps(plan, i, PASS_CONCAT_BWD, st);
-            { const int ra = arm(i); if (ra) return ra; }
+            { const int ra = arm(L, i); if (ra) return ra; }
             rc = launch_concat_up_bwd(gc, o.d.in0 >= 0 ? &a : nullptr, ga_a, sa, bs_a, c.view(o.d.in1), c.farena() + b.ga_off, b.numel,
-                                      b.d.has_bn ? c.bsums() + b.stats_off : nullptr, o.d.up_mode == MFVI_UP_NEAREST, n_samples, st);
-            settle();
+                                      b.d.has_bn ? c.bsums() + b.stats_off : nullptr, o.d.up_mode == MFVI_UP_NEAREST, n_samples, L);
+            settle(L);
         }
         if (rc) {
-            mfvi_tl_stop_event = nullptr;
             if (rc > 0) set_error("backward: op %d launch failed: %s", i, hipGetErrorString((hipError_t)rc));
             if (side != st) (void)hipStreamSynchronize(side);   // leave no side-stream work behind a failed call
             return rc;
@@ -1155,32 +1127,27 @@ int mfvi_plan_autotune(mfvi_plan* plan, const void* mu, const void* rho, const f
             const float* mu32 = plan->param_dtype == MFVI_PARAM_F32 ? static_cast<const float*>(mu) : nullptr;
             const float* rho32 = plan->param_dtype == MFVI_PARAM_F32 ? static_cast<const float*>(rho) : nullptr;
             const bool tiny = mu32 && (long long)o.g.Cout * o.g.Cin * o.g.ks * o.g.ks <= MFVI_INKERNEL_MAX_W;
+            const ConvWeights W{c.wsamp(), plan->n_vi, mu32, rho32, key, 1};
+            // What mfvi_forward / mfvi_backward launch for the tiling in o.g.tune[which], through the same dispatch, except: the layer splits its own bf16x6
+            // weight pieces (x6_ready stays false: timed with the layer), and only an in-kernel-eps candidate reaches the generic kernels
             auto launch = [&]() {
-                if (o.g.tune[which] & MFVI_TUNE_GENERIC) {      // in-kernel eps: the generic kernels, exactly as mfvi_forward / mfvi_backward reach them
-                    if (which == 0) return launch_conv_fwd(xin, o.g, mu32, rho32, key, 1, od, n_samples, st);
-                    if (which == 1) return launch_conv_bwd_data(gy, o.g, mu32, rho32, key, 1, c.farena() + o.scratch_off, per, n_samples, st);
-                    return launch_conv_bwd_weight(xin, gy, o.g, rho32, key, 1, dmu, drho, n_samples, st);
-                }
+                Launch L{st};
+                const bool generic = (o.g.tune[which] & MFVI_TUNE_GENERIC) != 0;
                 if (which == 0) {
-                    mfvi_tl_x6w = o.x6w_off >= 0 ? c.farena() + o.x6w_off : nullptr;
-                    const int r0 = launch_conv_fwd_mfma(xin, o.g, c.wsamp(), plan->n_vi, od, n_samples, st);
-                    mfvi_tl_x6w = nullptr;
-                    return r0;
+                    if (o.x6w_off >= 0) L.x6_scratch = c.farena() + o.x6w_off;
+                    return conv_forward(L, xin, o.g, W, od, n_samples, generic);
                 }
-                if (which == 1) {
+                if (which == 2)
+                    return conv_backward_weight(L, xin, gy, o.g, W, BwwPart{c.farena() + o.part_off, o.part_stride, o.max_strips}, &strips_used, dmu, drho, n_samples, generic);
+                if (fused_fold(*plan, o, o.d.in0 != plan->input)) {      // (it accumulates into the BN-backward sums: contents undefined afterwards)
                     const TensorInfo& x = plan->t[o.d.in0];
-                    if ((o.g.ks == 1 || (o.g.ks == 3 && o.g.stride == 1 && fold_fusion3_on())) && x.consumers.size() == 1 && fold_fusion_on() && o.d.in0 != plan->input) {
-                        // the fused-fold variant mfvi_backward will launch (it accumulates into the BN-backward sums: contents undefined afterwards)
-                        FoldFuse ff; ff.x = xin; ff.ga = c.farena() + x.ga_off; ff.ga_sstride = x.numel;
-                        ff.bsums = x.d.has_bn ? c.bsums() + x.stats_off : nullptr;
-                        mfvi_tl_x6bw = o.x6bw_off >= 0 ? c.farena() + o.x6bw_off : nullptr; mfvi_tl_x6bw_ready = false;      // (the launcher splits this layer's weights itself)
-                        const int r2 = launch_conv_bwd_data_mfma(gy, o.g, c.wsamp(), plan->n_vi, nullptr, 0, n_samples, st, &ff);
-                        mfvi_tl_x6bw = nullptr;
-                        if (r2 != -2) return r2;
-                    }
-                    return launch_conv_bwd_data_mfma(gy, o.g, c.wsamp(), plan->n_vi, c.farena() + o.scratch_off, per, n_samples, st);
+                    FoldFuse ff; ff.x = xin; ff.ga = c.farena() + x.ga_off; ff.ga_sstride = x.numel;
+                    ff.bsums = x.d.has_bn ? c.bsums() + x.stats_off : nullptr;
+                    if (o.x6bw_off >= 0) L.x6_scratch = c.farena() + o.x6bw_off;
+                    const int r2 = conv_backward_data(L, gy, o.g, W, nullptr, 0, n_samples, &ff);
+                    if (r2 != CONV_NOT_SERVED) return r2;
                 }
-                return launch_conv_bwd_weight_mfma(xin, gy, o.g, BwwPart{c.farena() + o.part_off, o.part_stride, o.max_strips}, &strips_used, n_samples, st);
+                return conv_backward_data(L, gy, o.g, W, c.farena() + o.scratch_off, per, n_samples, nullptr, generic);
             };
             // candidate tilings: fwd / bwd-data (mf, th, T) = fragments x tile rows x tiles per block;
             //                    bwd-weight (nb, waves, target/256) = input tiles per block x waves x block-count target
@@ -1222,9 +1189,9 @@ int mfvi_plan_autotune(mfvi_plan* plan, const void* mu, const void* rho, const f
             int best = 0; float best_ms = 1e30f;
             for (int cand : cands) {
                 o.g.tune[which] = cand;
-                rc = launch();                                   // warm-up; -2/-3: shape or tiling not served
-                if (rc == -2) break;
-                if (rc == -3) continue;
+                rc = launch();                                   // warm-up
+                if (rc == CONV_NOT_SERVED) break;                // no candidate will serve this op and pass
+                if (rc == CONV_BAD_TILING) continue;
                 if (rc) { set_error("autotune: op %d launch failed: %s", (int)i, rc > 0 ? hipGetErrorString((hipError_t)rc) : "bad arguments"); goto done; }
                 float ms = 1e30f;
                 for (int trial = 0; trial < 3 && !rc; ++trial) {      // best of three timings of `reps` launches: the choice must not flip on noise

@@ -85,6 +85,6 @@ rep('''                              s_red[0][q][which] + s_red[1][q][which] + s
 rep("    A.vec_out = MODE == 0 &&",
     "    static long long* prof = [] { long long* p = nullptr; if (getenv(\"MFVI_PROF\")) { (void)hipMalloc((void**)&p, 64 * 8); (void)hipMemset(p, 0, 64 * 8); } return p; }();\n    A.prof = prof;\n    A.vec_out = MODE == 0 &&")
 rep("        return (int)hipGetLastError();                                                                                     \\\n    }\n#define GO(MF_, TH_)",
-    "        if (prof) { long long h[64]; (void)hipStreamSynchronize(st); (void)hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost); fprintf(stderr, \"MODE %d KS %d mf %d th %d flat %d ff %d T %d tiles %d my %d chunks/tile %d\\n\", MODE, KS, MF_, TH_, (int)(FL_), (int)ff, A.tiles_per_block, A.n_tiles, my, (RED + Cfg::CC - 1) / Cfg::CC); for (int w = 0; w < 8; ++w) { fprintf(stderr, \"wave %d:\", w); for (int i = 0; i < 8; ++i) fprintf(stderr, \" %lld\", h[w * 8 + i]); fprintf(stderr, \"\\n\"); } } \\\n        return (int)hipGetLastError();                                                                                     \\\n    }\n#define GO(MF_, TH_)")
+    "        if (prof) { long long h[64]; (void)hipStreamSynchronize(L.st); (void)hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost); fprintf(stderr, \"MODE %d KS %d mf %d th %d flat %d ff %d T %d tiles %d my %d chunks/tile %d\\n\", MODE, KS, MF_, TH_, (int)(FL_), (int)ff, A.tiles_per_block, A.n_tiles, my, (RED + Cfg::CC - 1) / Cfg::CC); for (int w = 0; w < 8; ++w) { fprintf(stderr, \"wave %d:\", w); for (int i = 0; i < 8; ++i) fprintf(stderr, \" %lld\", h[w * 8 + i]); fprintf(stderr, \"\\n\"); } } \\\n        return (int)hipGetLastError();                                                                                     \\\n    }\n#define GO(MF_, TH_)")
 rep("#include <cstdlib>", "#include <cstdlib>\n#include <cstdio>")
 open(p, 'w').write(s)
