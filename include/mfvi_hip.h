@@ -370,6 +370,30 @@ int mfvi_predictive_accumulate(const float* out, int n, int C, int H, int W, int
 int mfvi_predictive_finalize(double* acc, int n_total, int C, int H, int W, int mode, const float* ref, float* mean, float* epi, float* ale,
                              float* total, float* err2, float* mse_mc, double* sums, void* stream);
 
+/* ---- uncertainty calibration (utils/uce.py uceloss, the evaluation notebooks' "UCE" cells) ------------------ */
+/* Bin k of the n_bins bins given by the n_bins + 1 device floats bounds[] (used as given, non-decreasing) holds the elements with
+ * unc > bounds[k] && unc <= bounds[k+1], decided by comparisons only.  An element equal to bounds[0], outside the range or NaN is in no
+ * bin but counts in n (uceloss's behaviour).  No floating-point atomics; results are bit-identical from call to call. */
+#define MFVI_UCE_MAX_BINS 256
+/* bytes of the scratch region of mfvi_uce_bins / mfvi_uce_minmax for n elements; -1 (and mfvi_last_error) for n < 1 or n_bins outside
+ * 1..MFVI_UCE_MAX_BINS */
+int64_t mfvi_uce_scratch_bytes(int64_t n, int n_bins);
+/* minmax[0], minmax[1] = exact fp32 min and max of unc[n], NaN ignored (per-block partials in scratch, then one block) */
+int mfvi_uce_minmax(const float* unc, int64_t n, float* minmax, void* scratch, void* stream);
+/* Per bin, over err[n] / unc[n] (fp32): count[k] (exact; count[n_bins] = n, so count holds n_bins + 1 words), sums = [n_bins] sum err |
+ * [n_bins] sum unc | sum unc over ALL elements (2 n_bins + 1 doubles), and in fp64 rounded once to fp32 prop = count / n,
+ * err_in_bin = sum err / count, unc_in_bin = sum unc / count (NaN where count == 0), unc_mean[0] = sum unc / n.
+ * Returns -2 for n_bins outside 1..MFVI_UCE_MAX_BINS. */
+int mfvi_uce_bins(const float* err, const float* unc, int64_t n, const float* bounds, int n_bins, void* scratch, int64_t* count, double* sums,
+                  float* prop, float* err_in_bin, float* unc_in_bin, float* unc_mean, void* stream);
+/* uce[0] = sum over the bins with prop > outlier (the fp32 prop against the double, as uceloss compares prop.item()) of
+ * |unc_in_bin - err_in_bin| * prop, in bin order */
+int mfvi_uce_value(const float* prop, const float* err_in_bin, const float* unc_in_bin, int n_bins, double outlier, float* uce, void* stream);
+/* The notebooks' uceloss inputs from a run's arrays: err[i] = mean over the S snapshots rec[S][n] of (rec[s][i] - gt[i])^2 (fp64, rounded
+ * once), times mask[i % mask_len] (mask may be NULL); unc[i] = epi[i] + ale[i % ale_len] (fp32; ale may be NULL). */
+int mfvi_uce_ring_inputs(const float* rec, int S, int64_t n, const float* gt, const float* mask, int64_t mask_len, const float* epi,
+                         const float* ale, int64_t ale_len, float* err, float* unc, void* stream);
+
 const char* mfvi_last_error(void);
 int mfvi_abi_version(void);
 

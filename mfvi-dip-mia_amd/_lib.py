@@ -10,6 +10,7 @@ OP_CONV, OP_CONCAT_UP, OP_CONV_LRT = 1, 2, 3
 DOMAIN_EPS, DOMAIN_INPUT, DOMAIN_INIT, DOMAIN_UNIFORM, DOMAIN_SGLD, DOMAIN_DROPOUT, DOMAIN_ROUND, DOMAIN_LRT = 0, 1, 2, 3, 4, 5, 6, 7
 PARAM_F32, PARAM_BF16 = 0, 1
 PRED_RAW, PRED_LOGPREC, PRED_INP, PRED_MEAN_ONLY = 0, 1, 2, 3             # MFVI_PRED_* (posterior predictive statistics)
+UCE_MAX_BINS = 256                                                        # MFVI_UCE_MAX_BINS (uncertainty calibration)
 
 
 class TensorDesc(C.Structure):
@@ -29,7 +30,7 @@ class MfviError(RuntimeError):
 _lib = None
 
 # name -> (restype, argtypes); every symbol declared in include/mfvi_hip.h
-_P, _I, _I64, _U32, _U64, _F = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float
+_P, _I, _I64, _U32, _U64, _F, _D = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_float, C.c_double
 SIGNATURES = {
     "mfvi_plan_create": (_I, [_P, _I, _P, _I, _I, _I, _I64, _I64, _I, _P]),
     "mfvi_plan_destroy": (None, [_P]),
@@ -89,6 +90,11 @@ SIGNATURES = {
     "mfvi_predictive_acc_doubles": (_I64, [_I, _I, _I, _I]),
     "mfvi_predictive_accumulate": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "mfvi_predictive_finalize": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfvi_uce_scratch_bytes": (_I64, [_I64, _I]),
+    "mfvi_uce_minmax": (_I, [_P, _I64, _P, _P, _P]),
+    "mfvi_uce_bins": (_I, [_P, _P, _I64, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfvi_uce_value": (_I, [_P, _P, _P, _I, _D, _P, _P]),
+    "mfvi_uce_ring_inputs": (_I, [_P, _I, _I64, _P, _P, _I64, _P, _P, _I64, _P, _P, _P]),
     "mfvi_last_error": (C.c_char_p, []),
     "mfvi_abi_version": (_I, []),
 }

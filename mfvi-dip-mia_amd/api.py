@@ -7,11 +7,14 @@ from . import runner
 from .nets import Concat, get_net, skip
 
 __all__ = ["build", "Plan", "Program", "skip_program", "_lib", "engine", "sharding", "runner", "Concat", "get_net", "skip", "MeanFieldVI", "FusedNet", "Conv2dRT", "Conv2dLRT",
-           "gaussian_nll", "gaussian_nll_inpainting", "uncert_regression_gal"]
+           "gaussian_nll", "gaussian_nll_inpainting", "uncert_regression_gal", "uceloss"]
 
 
 def __getattr__(name):          # bayes.py needs torch.nn at import: keep `import mfvi_dip_mia_amd` light
     if name in ("MeanFieldVI", "FusedNet", "Conv2dRT", "Conv2dLRT", "gaussian_nll", "gaussian_nll_inpainting", "uncert_regression_gal"):
         from . import bayes
         return getattr(bayes, name)
+    if name == "uceloss":
+        from .calibration import uceloss
+        return uceloss
     raise AttributeError(name)

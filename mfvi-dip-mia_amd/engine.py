@@ -150,7 +150,7 @@ class ElboEngine:
             self._pred_plans[chunk] = (plan, out)
         return self._pred_plans[chunk]
 
-    def predict(self, n_samples, target=None, clip=False, step=None, chunk=None, z=None):
+    def predict(self, n_samples, target=None, clip=False, step=None, chunk=None, z=None, calibration=None):
         """Posterior predictive sampling (BayTorch/inference/utils.py:11-24 uncert_regression_gal over N draws of the fit, DESIGN.md
         section 11): N forwards y_k = net_k(z) with the current mu / rho / BN, eps keyed by the GLOBAL sample index k at RNG step
         `step` (default 2**31: no training iteration's draw is reused), reduced on the device into
@@ -159,10 +159,20 @@ class ElboEngine:
         target: the clean image ([H,W]; inp [3,H,W]; sr at the high resolution) for err2 = mean_c (mean - g)^2 and
         mse_mc = err2 + (N-1)/N epi.  clip: clip m_k, a_k to [0,1] per draw (what the runner's ring stores).  z: the input (default z0,
         no perturbation).  With world_size > 1 the N draws are sharded like K and the fp64 sums all-reduced once.  Leaves the fit's
-        state (params, Adam moments, counters, self.out) untouched."""
+        state (params, Adam moments, counters, self.out) untouched.
+        calibration: True, or dict(n_bins=15, range=None): adds r["calibration"], the per-bin calibration statistics of the returned
+        mse_mc map against the returned total map (calibration.calibration; needs target; every rank computes it
+        from the all-reduced maps, no further communication)."""
         from .predictive import Accumulator, DEFAULT_STEP
         torch = self.torch
         N = int(n_samples)
+        cal = None
+        if calibration is not None and calibration is not False:
+            cal = {} if calibration is True else dict(calibration)
+            if set(cal) - {"n_bins", "range"}:
+                raise ValueError("calibration=%r: True or a dict with n_bins and range" % (calibration,))
+            if target is None:
+                raise ValueError("calibration compares the uncertainty with the error against a ground truth: pass target")
         if N < 2:
             raise ValueError("posterior predictive statistics need at least 2 samples, got n_samples=%d" % N)
         k0, n_local = shard_samples(N, self.rank, self.world)
@@ -187,6 +197,9 @@ class ElboEngine:
         r = acc.finalize(N, target)
         r.pop("sums")
         r.update(n=N, step=step)
+        if cal is not None:
+            from .calibration import calibration as _calibration
+            r["calibration"] = _calibration(r["mse_mc"], r["total"], n_bins=cal.get("n_bins", 15), range=cal.get("range"))
         return r
 
     def _perturb(self, step):

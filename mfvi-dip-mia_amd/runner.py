@@ -24,6 +24,7 @@ from .engine import ElboEngine, SiblingEngine
 
 MC_ITER = 25            # ring-buffer length (bayesian_optimization.py:1314)
 PREDICT_METHODS = ("mfvi", "mcd")      # methods whose fit is a posterior predict_samples can draw from (engine.ElboEngine.predict)
+CALIBRATION_METHODS = ("mfvi", "mcd", "sgld")      # methods whose run carries uncertainty maps to calibrate (dip has none)
 EXP_WEIGHT = 0.99       # EMA weight (:1292)
 
 
@@ -227,21 +228,50 @@ def _check_predict(method, predict_samples):
         raise ValueError("predict_samples=%d: at least 2 draws" % predict_samples)
 
 
-def _predict(eng, n, gt, run_dir, drop_ale=False):
-    """After the last iteration: eng.predict(n, target=gt) -> predictive.npz in the run directory (when saving); returns the arrays."""
+def _check_calibration(method, calibration, n_bins=15):
+    if calibration and method not in CALIBRATION_METHODS:
+        raise ValueError("calibration: the uncertainty calibration error needs uncertainty maps (mfvi, mcd, sgld), not %r" % (method,))
+    if calibration and not 1 <= int(n_bins) <= L.UCE_MAX_BINS:
+        raise ValueError("calibration_bins=%r outside 1..%d" % (n_bins, L.UCE_MAX_BINS))
+
+
+def _calibrate(run_dir, gt, recons, uncerts_epi, uncerts_ale, pred_cal, n_bins, mask=None):
+    """calibration.npz.  Source ring_: the "UCE" cell of the task's evaluation notebook on the run's own arrays, on
+    the GPU: errvar = mean over the last min(25, n_snap) `recons` snapshots of (recon - gt)^2 (times the mask for inpainting) against
+    uncerts[-1] + uncerts_ale[-1].  Source pred_ (with predict_samples): mse_mc against total of the posterior predictive maps."""
+    from . import calibration as Cb
+    S = min(MC_ITER, recons.shape[0])
+    err, unc = Cb.ring_inputs(recons[-S:], gt, uncerts_epi[-1], uncerts_ale[-1], mask)
+    arrs = Cb.npz_block(Cb.calibration(err, unc, n_bins=n_bins), "ring_")
+    if pred_cal is not None:
+        arrs.update(Cb.npz_block(pred_cal, "pred_"))
+    arrs["n_bins"] = np.int64(n_bins)
+    if run_dir is not None:
+        np.savez(os.path.join(run_dir, "calibration.npz"), **arrs)
+    return arrs
+
+
+def _predict(eng, n, gt, run_dir, drop_ale=False, calibration_bins=0):
+    """After the last iteration: eng.predict(n, target=gt) -> predictive.npz in the run directory (when saving); returns the arrays
+    (and the maps' Calibration under "_calibration" when calibration_bins > 0; popped by the caller)."""
     import torch
-    r = eng.predict(n, target=torch.from_numpy(np.ascontiguousarray(gt, np.float32)))
+    r = eng.predict(n, target=torch.from_numpy(np.ascontiguousarray(gt, np.float32)),
+                    calibration=dict(n_bins=calibration_bins) if calibration_bins else None)
     arrs = {k: r[k].cpu().numpy() for k in ("mean", "epi", "ale", "total", "err2", "mse_mc") if r[k] is not None and not (drop_ale and k == "ale")}
     arrs.update(n_samples=np.int64(r["n"]), step=np.int64(r["step"]))
     if run_dir is not None:
         np.savez(os.path.join(run_dir, "predictive.npz"), **arrs)
+    if calibration_bins:
+        arrs["_calibration"] = r["calibration"]
     return arrs
 
 
 def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, seed, show_every, plot, save, save_path, K, factor=4,
-         theta_step=4.0, verbose=False, net_kwargs=None, method="mfvi", weight_decay=0.0, dropout_p=0.3, gamma=0.996, param_dtype="f32", predict_samples=0, **unused):
+         theta_step=4.0, verbose=False, net_kwargs=None, method="mfvi", weight_decay=0.0, dropout_p=0.3, gamma=0.996, param_dtype="f32", predict_samples=0,
+         calibration=False, calibration_bins=15, **unused):
     import torch
     _check_predict(method, predict_samples)
+    _check_calibration(method, calibration, calibration_bins)
     sib = dict(weight_decay=weight_decay, dropout_p=dropout_p, gamma=gamma)
     timestamp = str(time.time())
     run_dir = os.path.join(save_path, timestamp)
@@ -296,7 +326,10 @@ def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, see
                 mn, mg, ps_, _ = book.results()
                 A.snapshot_pngs(run_dir, method, i, mn, mg, ps_, recon[None], None if method == "dip" else var[None],
                                 None if (method == "dip" or task == "ct") else ale[None])
-    pred = _predict(eng, predict_samples, img_np, run_dir if save else None, drop_ale=task == "ct") if predict_samples else None
+    pred = _predict(eng, predict_samples, img_np, run_dir if save else None, drop_ale=task == "ct",
+                    calibration_bins=calibration_bins if calibration else 0) if predict_samples else None
+    cal = _calibrate(run_dir if save else None, img_np, recons, uncerts_epi, uncerts_ale, pred.pop("_calibration") if pred else None,
+                     calibration_bins) if calibration else None
     torch.cuda.synchronize()
     mse_noisy, mse_gt, psnrs, ssims = book.results()
     if save:
@@ -315,6 +348,8 @@ def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, see
                recons=recons, uncerts=uncerts_epi, uncerts_ale=uncerts_ale, seconds=time.perf_counter() - t0, engine=eng)
     if pred is not None:
         res["predictive"] = pred
+    if cal is not None:
+        res["calibration"] = cal
     return res
 
 
@@ -370,13 +405,14 @@ run_ct_sgld = _sibling("ct", "sgld", dict(gamma=0.996, weight_decay=5e-8))
 
 def run_inp_mfvi(img="phantom", mask=None, imsize=(256, 256), num_iter=5000, lr=2e-3, temp=4e-6, sigma=0.01, input_depth=32, seed=42,
                  show_every=100, plot=False, save=True, save_path="../logs", K=1, net_kwargs=None, verbose=False, method="mfvi",
-                 weight_decay=1e-4, dropout_p=0.2, gamma=0.996, predict_samples=0, **unused):
+                 weight_decay=1e-4, dropout_p=0.2, gamma=0.996, predict_samples=0, calibration=False, calibration_bins=15, **unused):
     """bayesian_optimization.py:2892-3114: inpainting with the 6-scale no-skip net (5x5 down filters, nearest up-sampling), sigmoid on
     the colour channels, masked Gaussian NLL.  img: (3, H, W) array in [0, 1] or 'phantom' (three synthetic planes); mask: (1|3, H, W),
     1 = known pixel (the reference ships its masks in data/inpainting/).  save.npz carries the reference's keys for this task
     (img_inpainting, img_mask, mse_corrupted, mse_gt, recons, uncerts, uncerts_ale, psnrs, ssims)."""
     import torch
     _check_predict(method, predict_samples)
+    _check_calibration(method, calibration, calibration_bins)
     timestamp = str(time.time())
     run_dir = os.path.join(save_path, timestamp)
     if save:
@@ -416,7 +452,10 @@ def run_inp_mfvi(img="phantom", mask=None, imsize=(256, 256), num_iter=5000, lr=
             if verbose:
                 nll, kl, loss = eng.losses()
                 print("iter %6d  loss %.5f  nll %.5f  kl %.4e  (%.1f it/s)" % (i, loss, nll, kl, (i + 1) / (time.perf_counter() - t0)))
-    pred = _predict(eng, predict_samples, img_np, run_dir if save else None) if predict_samples else None
+    pred = _predict(eng, predict_samples, img_np, run_dir if save else None,
+                    calibration_bins=calibration_bins if calibration else 0) if predict_samples else None
+    cal = _calibrate(run_dir if save else None, img_np, recons, uncerts_epi, uncerts_ale, pred.pop("_calibration") if pred else None,
+                     calibration_bins, mask=mask_np) if calibration else None
     torch.cuda.synchronize()
     mse_corrupted, mse_gt, psnrs, ssims = book.results()
     if save:
@@ -432,6 +471,8 @@ def run_inp_mfvi(img="phantom", mask=None, imsize=(256, 256), num_iter=5000, lr=
                recons=recons, uncerts=uncerts_epi, uncerts_ale=uncerts_ale, seconds=time.perf_counter() - t0, engine=eng)
     if pred is not None:
         res["predictive"] = pred
+    if cal is not None:
+        res["calibration"] = cal
     return res
 
 
@@ -481,7 +522,15 @@ def main(argv=None):
                                                              "run as independent fits (bo.py; parity unpinned: gpytorch is not available here)")
     ap.add_argument("--predict-samples", type=int, default=0, help="> 0: after the last iteration draw N posterior samples of the fit (mfvi, mcd) "
                                                                  "and write predictive.npz (mean, epi, ale, total, err2, mse_mc) beside save.npz")
+    ap.add_argument("--calibration", action="store_true", help="write calibration.npz beside save.npz: per-bin calibration statistics and the "
+                                                                "UCE of the run's uncertainty maps (mfvi, mcd, sgld), and of the posterior "
+                                                                "predictive maps with --predict-samples")
+    ap.add_argument("--calibration-bins", type=int, default=15)
     a = ap.parse_args(argv)
+    if a.calibration and a.bayes not in CALIBRATION_METHODS:
+        ap.error("--calibration needs uncertainty maps (--bayes mfvi, mcd or sgld), not %s" % a.bayes)
+    if a.calibration and not 1 <= a.calibration_bins <= L.UCE_MAX_BINS:
+        ap.error("--calibration-bins %d outside 1..%d" % (a.calibration_bins, L.UCE_MAX_BINS))
     if a.predict_samples and a.bayes not in PREDICT_METHODS:
         ap.error("--predict-samples needs a posterior to draw from (--bayes mfvi or mcd), not %s" % a.bayes)
     if a.predict_samples < 0 or a.predict_samples == 1:
@@ -503,6 +552,9 @@ def main(argv=None):
         rp["param_dtype"] = a.param_dtype
     if a.predict_samples:
         rp["predict_samples"] = a.predict_samples
+    if a.calibration:
+        rp["calibration"] = True
+        rp["calibration_bins"] = a.calibration_bins
     imgs = a.img.split(",") if a.img else [rp.pop("img", "phantom")]
     rp.pop("img", None)
     jobs = [dict(cand, img=im) for im in imgs for cand in cands]
