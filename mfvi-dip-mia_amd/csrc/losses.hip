@@ -653,7 +653,7 @@ __global__ __launch_bounds__(256) void sample_weights_kernel(const SampleEntry* 
                                                              double* __restrict__ zero, long long n_zero, int n_k)
 {
     key = key_now(key);
-    // the pass's statistics buffers, cleared by the draw's own threads (plan.hip, mfvi_forward)
+    // the pass's statistics buffers, cleared by the draw's own threads (plan_forward.hip, begin_forward)
     for (long long i = ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x; i < n_zero; i += (long long)gridDim.x * gridDim.y * 256) zero[i] = 0.0;
     typedef typename std::conditional<BF16, bf16_t, float>::type PT;
     const PT* __restrict__ mu = static_cast<const PT*>(mu_v); const PT* __restrict__ rho = static_cast<const PT*>(rho_v);

@@ -1,5 +1,5 @@
 """The backward-data of the 4-channel 1x1 skip convolution formed inside the fold of the tensor it shares with the scale's stride-2 convolution
-(csrc/elementwise.hip finalize_dx_vec1_kernel; plan.hip books it as kernel family 5 on the skip op's backward-data slot): hour-glass nets
+(csrc/elementwise.hip finalize_dx_vec1_kernel; plan_backward.hip books it as kernel family 5 on the skip op's backward-data slot): hour-glass nets
 against the oracle's tape, every gradient.  Reference: models/skip.py:60-66 (skip branch: conv 1x1 -> bn -> act beside the deeper branch),
 autograd of BayTorch/modules/reparam_layers.py:37 for both consumers, summed at the shared input."""
 import numpy as np
