@@ -157,6 +157,20 @@ int mfvi_plan_set_bn_eval(mfvi_plan* plan, const float* running);
  * exactly as with float32 storage of the same (bf16-representable) numbers.  Gradients, Adam moments and the BatchNorm block stay
  * float32.  The update rule is mfvi_elbo_update_bf16: no float32 master copy, stochastic rounding.  mu and rho must be 8-byte aligned. */
 int mfvi_plan_set_param_dtype(mfvi_plan* plan, int dtype);
+/* Fits mode: one call of mfvi_forward / mfvi_backward advances MANY independent fits.  With S = samples_per_fit > 0
+ * the n_samples of a call (a multiple of S) are n_samples / S fits of S samples each: sample i belongs to fit i / S and still uses eps of
+ * global sample index k0 + i (the RNG is unchanged).  mu / rho / bn point at fit 0, fit j's blocks lie j * param_stride floats further on
+ * (one flat row [MU | RHO | BN] per fit works with a single stride); dmu / drho / dbn
+ * likewise with grad_stride.  z is [n_fits][Cin][H][W], one input per fit; out / dout / dz stay [n_samples][C][H][W].  Every weight gradient is
+ * summed over the samples of its fit only, in a fixed order, no atomics.  S = 0 (the default) switches the mode off: one fit, as before.
+ * S > 1 grows the workspace by one copy of the net input per sample: ask mfvi_plan_workspace_bytes again afterwards.
+ * Not served, and refused with MFVI_ERR_FITS_UNSUPPORTED and a message (never run with fit 0's parameters): bf16 parameter storage, plans
+ * with local-reparameterisation layers, sample_weights = 0, BatchNorm eval mode and mfvi_plan_bn_update_running, a gradient split, a device
+ * step source, layers outside the sampled-weight slab (input channels / weight offsets not multiples of 4) and MFVI_DISABLE_MFMA.
+ * mfvi_plan_autotune runs BEFORE the mode is switched on (tilings do not depend on it); in-kernel-eps tilings (tune bit 27) fall back to the
+ * heuristic when it is. */
+#define MFVI_ERR_FITS_UNSUPPORTED (-5)
+int mfvi_plan_set_fits(mfvi_plan* plan, int samples_per_fit, int64_t param_stride, int64_t grad_stride);
 /* bytes of caller-provided device workspace (activations, gradients, BN statistics) for max_samples */
 int64_t mfvi_plan_workspace_bytes(const mfvi_plan* plan);
 
@@ -393,6 +407,32 @@ int mfvi_uce_value(const float* prop, const float* err_in_bin, const float* unc_
  * once), times mask[i % mask_len] (mask may be NULL); unc[i] = epi[i] + ale[i % ale_len] (fp32; ale may be NULL). */
 int mfvi_uce_ring_inputs(const float* rec, int S, int64_t n, const float* gt, const float* mask, int64_t mask_len, const float* epi,
                          const float* ale, int64_t ale_len, float* err, float* unc, void* stream);
+
+/* ---- many independent fits per launch (the plan side is mfvi_plan_set_fits) --------------------------------- */
+/* The reference runs its (temp, sigma) candidates and its slices as one process per fit (bayesian_optimization.py:3760-3775, 1328-1372).
+ * These entry points run the element-wise passes of one iteration for n_fits fits in ONE launch each, whatever n_fits is; per fit they
+ * compute what the single-fit entry point named below computes (the kernels share its per-element code).  n_fits (and n_fits * S) < 65536. */
+/* z[f] = z0[f] + std * N(0,1), f < n_fits, n_per_fit floats each: RNG domain 1, stream 0, sample fit0 + f — the numbers of
+ * mfvi_normal_fill(seed, 1, 0, fit0 + f, step, ...); fit 0 with fit0 = 0 is mfvi_perturb_input. */
+int mfvi_perturb_input_fits(const float* z0, uint64_t seed, uint32_t step, int64_t n_per_fit, int n_fits, uint32_t fit0, float std, float* z,
+                            void* stream);
+/* mfvi_gaussian_nll per fit: out / dout [n_fits * S][2][H][W], fit f against targets + f * target_stride ([H/factor][W/factor]);
+ * nll[f] (device doubles) += sum over the fit's S samples. */
+int mfvi_gaussian_nll_fits(const float* out, const float* targets, int64_t target_stride, int n_fits, int S, int H, int W, int factor,
+                           float grad_scale, float* dout, double* nll, void* stream);
+/* mfvi_elbo_update per fit on rows of params / m / v (param_stride floats apart) and grads (grad_stride), each laid out [MU | RHO | BN],
+ * with the fit's own prior, temperature and learning rate read from DEVICE memory.  kl_out[f] (overwritten) is reduced in a fixed order
+ * (bit-reproducible; the order of mfvi_elbo_update).  NaN isolation: a fit whose nll[f] is not finite, or whose dead[f] is already set,
+ * keeps parameters and moments untouched; a non-finite nll[f] sets dead[f] = 1 (sticky; the caller clears it).  The other fits are unaffected.
+ * scratch: mfvi_elbo_update_fits_scratch_bytes(n_fits) bytes. */
+typedef struct { float prior_mu, prior_sigma, temp, lr; } mfvi_fit_hyper;
+int64_t mfvi_elbo_update_fits_scratch_bytes(int n_fits);
+int mfvi_elbo_update_fits(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, int64_t param_stride, int64_t grad_stride,
+                          int n_fits, const mfvi_fit_hyper* hyper_dev, float beta1, float beta2, float eps, int t, const double* nll, int32_t* dead,
+                          double* kl_out, void* scratch, void* stream);
+/* The EMA part of mfvi_bookkeep per fit: sample means of out[:, 0] and exp(-out[:, 1]) over the fit's S samples (out [n_fits * S][C][H][W],
+ * C = 1 or 2) and ema[f] = first ? mean : ema[f] * weight + mean * (1 - weight); ema [n_fits][C][H][W]. */
+int mfvi_ema_fits(const float* out, int n_fits, int S, int C, int H, int W, float* ema, float weight, int first, void* stream);
 
 const char* mfvi_last_error(void);
 int mfvi_abi_version(void);

@@ -39,6 +39,7 @@ SIGNATURES = {
     "mfvi_plan_set_param_dtype": (_I, [_P, _I]),
     "mfvi_plan_bn_update_running": (_I, [_P, _P, _I, _F, _P, _P]),
     "mfvi_plan_set_bn_eval": (_I, [_P, _P]),
+    "mfvi_plan_set_fits": (_I, [_P, _I, _I64, _I64]),
     "mfvi_plan_set_side_stream": (_I, [_P, _I]),
     "mfvi_plan_set_step_source": (_I, [_P, _P]),
     "mfvi_plan_set_capture_mode": (_I, [_P, _I]),
@@ -95,6 +96,11 @@ SIGNATURES = {
     "mfvi_uce_bins": (_I, [_P, _P, _I64, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfvi_uce_value": (_I, [_P, _P, _P, _I, _D, _P, _P]),
     "mfvi_uce_ring_inputs": (_I, [_P, _I, _I64, _P, _P, _I64, _P, _P, _I64, _P, _P, _P]),
+    "mfvi_perturb_input_fits": (_I, [_P, _U64, _U32, _I64, _I, _U32, _F, _P, _P]),
+    "mfvi_gaussian_nll_fits": (_I, [_P, _P, _I64, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "mfvi_elbo_update_fits_scratch_bytes": (_I64, [_I]),
+    "mfvi_elbo_update_fits": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _F, _F, _F, _I, _P, _P, _P, _P, _P]),
+    "mfvi_ema_fits": (_I, [_P, _I, _I, _I, _I, _I, _P, _F, _I, _P]),
     "mfvi_last_error": (C.c_char_p, []),
     "mfvi_abi_version": (_I, []),
 }
@@ -115,7 +121,12 @@ def lib():
     return _lib
 
 
+ERR_FITS_UNSUPPORTED = -5                                                 # MFVI_ERR_FITS_UNSUPPORTED (mfvi_plan_set_fits)
+
+
 def check(rc):
+    if rc == ERR_FITS_UNSUPPORTED:
+        raise NotImplementedError(lib().mfvi_last_error().decode())
     if rc != 0:
         raise MfviError("libmfvi_hip error %d: %s" % (rc, lib().mfvi_last_error().decode()))
 

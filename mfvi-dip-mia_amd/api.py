@@ -3,10 +3,11 @@ from . import _lib
 from ._build import build
 from .program import Plan, Program, skip_program
 from . import engine, sharding
+from .fitbatch import FitBatch
 from . import runner
 from .nets import Concat, get_net, skip
 
-__all__ = ["build", "Plan", "Program", "skip_program", "_lib", "engine", "sharding", "runner", "Concat", "get_net", "skip", "MeanFieldVI", "FusedNet", "Conv2dRT", "Conv2dLRT",
+__all__ = ["build", "FitBatch", "Plan", "Program", "skip_program", "_lib", "engine", "sharding", "runner", "Concat", "get_net", "skip", "MeanFieldVI", "FusedNet", "Conv2dRT", "Conv2dLRT",
            "gaussian_nll", "gaussian_nll_inpainting", "uncert_regression_gal", "uceloss"]
 
 

@@ -214,6 +214,9 @@ struct TView {
     float eps, slope;
     int act;
     const float* drop;       // [n_samples][C] Dropout2d factors (0 or 1/(1-p)) applied between the raw data and the BN; nullptr: none
+    // fits mode (mfvi_plan_set_fits): sample k belongs to fit k / fit_s and reads that fit's gamma / beta, gamma_fstride floats per fit
+    // further on; fit_s = 0: one fit, every sample reads gamma as given
+    int fit_s = 0; long long gamma_fstride = 0;
 };
 
 // Gradient wrt a raw tensor y, formed on load from ga = dL/d(BN output) (or dL/dy when no BN):
@@ -227,6 +230,7 @@ struct GView {
     const float* gamma;
     float eps;
     const float* drop;       // as TView::drop
+    int fit_s = 0; long long gamma_fstride = 0;      // as TView::fit_s
 };
 
 // per-channel constants of a view, computed once per block into LDS/registers
@@ -244,7 +248,8 @@ __device__ __forceinline__ ChanFwd chan_fwd(const TView& v, int k, int c)
     // Dropout2d factor d between y and the BN: BN(d*y) = (y - m) * (d*rstd_d) * gamma + beta with rstd_d = 1/sqrt(d^2 var + eps)
     const double d = v.drop ? (double)v.drop[(long long)k * v.C + c] : 1.0;
     const double rstd = d / sqrt(d * d * var + (double)v.eps);
-    r.mean = (float)m; r.scale = (float)(rstd * (double)v.gamma[c]); r.beta = v.gamma[v.C + c]; r.rstd = (float)rstd;
+    const float* gm = v.fit_s ? v.gamma + (long long)(k / v.fit_s) * v.gamma_fstride : v.gamma;      // the sample's fit
+    r.mean = (float)m; r.scale = (float)(rstd * (double)gm[c]); r.beta = gm[v.C + c]; r.rstd = (float)rstd;
     return r;
 }
 // act: bit 0 = LeakyReLU(slope) after the BN; bit 1 (MFVI_ACT_SQUARE) = square the result — the x**2 operand of the local-reparameterisation
@@ -284,7 +289,8 @@ __device__ __forceinline__ ChanBwd chan_bwd(const GView& g, int k, int c)
     double var = s[1] / n - m * m; if (var < 0) var = 0;
     const double d = g.drop ? (double)g.drop[(long long)k * g.C + c] : 1.0;
     const double rstd = d / sqrt(d * d * var + (double)g.eps);          // xhat = (y - m) * rstd, dy = d * gamma * rstd_d * (...)
-    r.mean = (float)m; r.rstd = (float)rstd; r.c1 = (float)(rstd * (double)g.gamma[c]);
+    const float* gm = g.fit_s ? g.gamma + (long long)(k / g.fit_s) * g.gamma_fstride : g.gamma;
+    r.mean = (float)m; r.rstd = (float)rstd; r.c1 = (float)(rstd * (double)gm[c]);
     r.c2 = (float)(b[0] / n); r.c3 = (float)(b[1] / n);
     return r;
 }
@@ -389,7 +395,8 @@ int launch_conv_bwd_weight(const TView& in, const GView& gy, const ConvGeom& g, 
 // Weights as the kernels want them: the slab for the matrix-core families (w: sample 0, sample k at w + k*wstride — the buffer filled by
 // launch_sample_weights, or mu with stride 0) and mu / rho / key for the generic kernels, which draw eps themselves (mu == nullptr: bf16
 // parameters, which reach those only through the plan's float32 expansion of the layers outside the sampling table).
-struct ConvWeights { const float* w; long long wstride; const float* mu; const float* rho; RngKey key; int sample_weights; };
+struct ConvWeights { const float* w; long long wstride; const float* mu; const float* rho; RngKey key; int sample_weights;
+                     int fits = 0; };      // fits mode: mu == rho == nullptr (the generic kernels read ONE mu / rho: a layer that lands there is an error)
 // fuse (1x1 / 3x3 stride-1 layers whose input has no other consumer): the epilogue does the fold of that input tensor itself — multiplies by
 // LeakyReLU'(view(x)), accumulates the BN-backward sums of x (bsums, nullptr when x carries no BatchNorm) and writes ga directly; no
 // padded-gradient scratch, no finalize_dx launch.
@@ -468,7 +475,8 @@ int launch_conv_bwd_weight_x6(const TView& in, const GView& gy, const ConvGeom& 
 struct SampleEntry { long long w_off, b_off; int n_w, n_b, layer_id, first_block; };
 // bf16: mu / rho point to bf16_t arrays; sample = 0 writes W = mu (RTLayer's eval branch) — callers then launch it for ONE sample
 int launch_sample_weights(const SampleEntry* table_dev, int n_entries, int n_blocks, const void* mu, const void* rho, RngKey key,
-                          int n_samples, float* wsamp, long long wstride, hipStream_t st, int bf16 = 0, int sample = 1, double* zero = nullptr, long long n_zero = 0);      // zero: n_zero doubles cleared by the same launch
+                          int n_samples, float* wsamp, long long wstride, hipStream_t st, int bf16 = 0, int sample = 1, double* zero = nullptr, long long n_zero = 0,      // zero: n_zero doubles cleared by the same launch
+                          int fit_s = 0, long long param_fstride = 0);      // fits mode: sample k draws from mu / rho + (k / fit_s) * param_fstride
 // bf16 -> float32 expansion (the generic fp32 kernels of shapes the MFMA path does not serve read float32 mu / rho)
 int launch_expand_bf16(const void* src, long long n, float* dst, hipStream_t st);
 constexpr int SAMPLE_QUADS = 256;       // weight quads per block of the sampling kernel
@@ -477,11 +485,12 @@ struct GradFinEntry { long long w_off, b_off, part_off, stride; int n_w, n_b, st
 struct BnGradEntry { long long bsums_off; long long bn_off; int C; int hw; };      // hw = H * W of the normalised tensor
 // BatchNorm parameter gradients of ONE table entry from the accumulated BN-backward sums: d gamma = sum ga * xhat, d beta = sum ga
 // (a block's worth of work: bn_param_grads_kernel, or an extra block of grad_finalize_kernel)
-__device__ __forceinline__ void bn_param_grads_entry(const BnGradEntry e, const double* __restrict__ bsums_base, int n_samples, float* __restrict__ dbn)
+// (the samples k_lo .. k_lo + n_samples - 1 of the pass: in fits mode one fit's, into that fit's dbn)
+__device__ __forceinline__ void bn_param_grads_entry(const BnGradEntry e, const double* __restrict__ bsums_base, int n_samples, float* __restrict__ dbn, int k_lo = 0)
 {
     for (int c = threadIdx.x; c < e.C; c += blockDim.x) {
         double sb = 0, sg = 0;
-        for (int k = 0; k < n_samples; ++k) {
+        for (int k = k_lo; k < k_lo + n_samples; ++k) {
             const double* s = bsums_base + e.bsums_off + ((long long)k * e.C + c) * 2;
             sb += s[0]; sg += s[1];
         }
@@ -492,7 +501,8 @@ __device__ __forceinline__ void bn_param_grads_entry(const BnGradEntry e, const 
 // bn_table / n_bn / bsums_base / dbn (optional): the BatchNorm parameter gradients as n_bn extra blocks of the same launch
 int launch_grad_finalize(const GradFinEntry* table_dev, int n_entries, int n_blocks, const float* part_base, const void* rho, RngKey key,
                          int sample_weights, int n_samples, float* dmu, float* drho, const float* wsamp, long long wstride, const void* mu,
-                         hipStream_t st, int bf16 = 0, const BnGradEntry* bn_table = nullptr, int n_bn = 0, const double* bsums_base = nullptr, float* dbn = nullptr);
+                         hipStream_t st, int bf16 = 0, const BnGradEntry* bn_table = nullptr, int n_bn = 0, const double* bsums_base = nullptr, float* dbn = nullptr,
+                         int fit_s = 0, long long param_fstride = 0, long long grad_fstride = 0);      // fits mode: one grid row per fit
 constexpr int GRAD_FIN_QUADS = 64;      // weight quads per block of the finalize kernel
 // mul2v: the source is the gradient wrt view(X)**2 (variance convolution of an LRT layer): it enters with the factor 2 * view(X)
 struct FoldSrc { const float* d; long long sstride; int pad; int mul2v; };
@@ -525,4 +535,6 @@ int launch_bn_update_running(const BnGradEntry* table_dev, int n_entries, int ma
                              float* running, hipStream_t st);
 int launch_bn_eval_fill(const BnGradEntry* table_dev, int n_entries, int max_c, double* fstats_base, int n_samples, const float* running, hipStream_t st);
 int launch_bn_param_grads(const BnGradEntry* table_dev, int n_entries, int max_c, const double* bsums_base, int n_samples,
-                          float* dbn, hipStream_t st);
+                          float* dbn, hipStream_t st, int fit_s = 0, long long grad_fstride = 0);
+// fits mode with more than one sample per fit: dst[k] = z[k / fit_s], n floats each (the kernels address the net input by sample)
+int launch_replicate_input(const float* z, long long n, int fit_s, int n_samples, float* dst, hipStream_t st);

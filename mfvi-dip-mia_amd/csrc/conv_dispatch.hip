@@ -1,6 +1,7 @@
 // The one path from the plan to a convolution kernel (common.h: conv_forward, conv_backward_data, conv_backward_weight): picks the kernel family
 // of a (layer, pass) from the layer's tiling word and the shape, for mfvi_forward / mfvi_backward and for mfvi_plan_autotune's candidates alike.
 #include "common.h"
+#include "../../include/mfvi_hip.h"
 #include <cstdlib>
 
 bool use_mfma()
@@ -101,6 +102,7 @@ bool to_generic(Launch& L, const ConvGeom& g, const ConvWeights& W, const char* 
 {
     if (!conv_declined(*rc) || !generic_fallback) return false;
     if (W.mu) { L.family = FAM_GENERIC; return true; }
+    if (W.fits) { set_error("%s: conv layer %d needs the generic fp32 kernels, which read one mu / rho for all samples: fits mode (mfvi_plan_set_fits) does not serve it", pass, g.layer_id); *rc = MFVI_ERR_FITS_UNSUPPORTED; return false; }
     set_error("%s: conv layer %d needs the generic fp32 kernels, which bf16 parameters reach only for layers outside the sampling table (use H, W multiples of 4)", pass, g.layer_id);
     *rc = -1; return false;
 }

@@ -644,9 +644,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void c
 
 // ---------------------------------------------------------------------------------------------
 __global__ void bn_param_grads_kernel(const BnGradEntry* __restrict__ table, const double* __restrict__ bsums_base,
-                                      int n_samples, float* __restrict__ dbn)
+                                      int n_samples, float* __restrict__ dbn, int fit_s, long long grad_fstride)
 {
-    bn_param_grads_entry(table[blockIdx.x], bsums_base, n_samples, dbn);
+    if (fit_s) bn_param_grads_entry(table[blockIdx.x], bsums_base, fit_s, dbn + (long long)blockIdx.y * grad_fstride, (int)blockIdx.y * fit_s);      // grid y = fit
+    else bn_param_grads_entry(table[blockIdx.x], bsums_base, n_samples, dbn);
+}
+__global__ __launch_bounds__(256) void replicate_input_kernel(const float4* __restrict__ z, long long n4, int fit_s, float4* __restrict__ dst)
+{
+    const int k = blockIdx.y;
+    const float4* __restrict__ src = z + (long long)(k / fit_s) * n4;
+    float4* __restrict__ d = dst + (long long)k * n4;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) d[i] = src[i];
 }
 
 // nn.BatchNorm2d(momentum = 0.1) in training mode (models/common.py:96-97) after each of the n_samples batch-1 forwards, in order:
@@ -889,10 +897,18 @@ int launch_bn_eval_fill(const BnGradEntry* table_dev, int n_entries, int max_c, 
 }
 
 int launch_bn_param_grads(const BnGradEntry* table_dev, int n_entries, int max_c, const double* bsums_base, int n_samples,
-                          float* dbn, hipStream_t st)
+                          float* dbn, hipStream_t st, int fit_s, long long grad_fstride)
 {
     if (n_entries == 0) return 0;
-    hipLaunchKernelGGL(bn_param_grads_kernel, dim3(n_entries), dim3(max_c < 64 ? 64 : (max_c > 256 ? 256 : ((max_c + 63) / 64) * 64)), 0, st,
-                       table_dev, bsums_base, n_samples, dbn);
+    hipLaunchKernelGGL(bn_param_grads_kernel, dim3(n_entries, fit_s ? n_samples / fit_s : 1), dim3(max_c < 64 ? 64 : (max_c > 256 ? 256 : ((max_c + 63) / 64) * 64)), 0, st,
+                       table_dev, bsums_base, n_samples, dbn, fit_s, grad_fstride);
+    return (int)hipGetLastError();
+}
+
+int launch_replicate_input(const float* z, long long n, int fit_s, int n_samples, float* dst, hipStream_t st)
+{
+    if (n <= 0 || (n & 3) || fit_s < 1 || n_samples < 1 || (((uintptr_t)z | (uintptr_t)dst) & 15)) return (int)hipErrorInvalidValue;
+    const long long n4 = n >> 2, nb = (n4 + 255) / 256;
+    hipLaunchKernelGGL(replicate_input_kernel, dim3((unsigned)(nb > 256 ? 256 : nb), n_samples), dim3(256), 0, st, (const float4*)z, n4, fit_s, (float4*)dst);
     return (int)hipGetLastError();
 }

@@ -1,0 +1,131 @@
+// The element-wise passes of one ELBO iteration for MANY independent fits in one launch each (mfvi_plan_set_fits is
+// the plan side): input perturbation, Gaussian NLL, KL + AdamW, smoothed outputs.  Grid y = fit (or sample); the per-thread bodies are the
+// single-fit kernels' own (iter_ops.h), so a fit of a batch computes what mfvi_perturb_input / mfvi_gaussian_nll / mfvi_elbo_update /
+// mfvi_bookkeep compute for it alone.  The reference runs one process per fit instead (bayesian_optimization.py:3760-3775).
+#include "common.h"
+#include "iter_ops.h"
+#include "../../include/mfvi_hip.h"
+
+namespace {
+
+constexpr int UPDATE_MAX_BLOCKS = 2048;      // as mfvi_elbo_update: the same blocks per fit, so the same KL partial sums in the same order
+inline int nblocks(long long n, int cap = 2048) { long long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > cap ? cap : b)); }
+
+__global__ __launch_bounds__(256) void perturb_fits_kernel(RngKey key, long long n, float std, const float* __restrict__ z0, float* __restrict__ z)
+{
+    key.sample += blockIdx.y;      // fit f: sample fit0 + f of RNG domain INPUT
+    normal_fill_share(key, n, 0.f, std, z0 + (long long)blockIdx.y * n, z + (long long)blockIdx.y * n);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void gaussian_nll_fits_kernel(const float* __restrict__ out, const float* __restrict__ targets, long long target_stride,
+                                                                int S, int H, int W, int f, float grad_scale, float* __restrict__ dout,
+                                                                double* __restrict__ nll)
+{
+    __shared__ double s_red[8];
+    const int k = blockIdx.y, fit = k / S;
+    const long long HW = (long long)H * W;
+    const float* __restrict__ o = out + (long long)k * 2 * HW;
+    const float* __restrict__ t = targets + (long long)fit * target_stride;
+    float* __restrict__ d = dout ? dout + (long long)k * 2 * HW : nullptr;
+    const double v = VEC ? gnll_sample_vec(o, t, HW, grad_scale, d) : gnll_sample(o, t, H, W, f, grad_scale, d);
+    block_atomic_add(v, nll + fit, s_red);
+}
+
+__global__ __launch_bounds__(256) void elbo_update_fits_kernel(float* __restrict__ params, float* __restrict__ grads, float* __restrict__ m, float* __restrict__ v,
+                                                               long long n_vi, long long n_bn, long long param_stride, long long grad_stride,
+                                                               const mfvi_fit_hyper* __restrict__ hyper, float b1, float b2, float eps, double bc1,
+                                                               float inv_sqrt_bc2, const double* __restrict__ nll, const int32_t* __restrict__ dead,
+                                                               double* __restrict__ partial)
+{
+    __shared__ double s_red[8];
+    const int fit = blockIdx.y;
+    const mfvi_fit_hyper h = hyper[fit];
+    // a fit whose data term is not finite (or that died earlier) keeps parameters and moments; its KL is still reported
+    const bool skip = dead[fit] != 0 || !isfinite(nll[fit]);
+    const float step_size = (float)((double)h.lr / bc1);
+    const long long po = (long long)fit * param_stride;
+    const double acc = elbo_update_share(params + po, grads + (long long)fit * grad_stride, m + po, v + po, n_vi, n_bn, h.prior_mu, h.prior_sigma, h.temp,
+                                         b1, b2, eps, step_size, inv_sqrt_bc2, skip);
+    const double tot = block_sum_d(acc, s_red);
+    if (threadIdx.x == 0) partial[(long long)fit * UPDATE_MAX_BLOCKS + blockIdx.x] = tot;
+}
+// one block per fit: its partials in block order (the order of elbo_update_finish_kernel), and the sticky dead flag
+__global__ __launch_bounds__(256) void elbo_update_fits_finish_kernel(const double* __restrict__ partial, int n_blocks, const double* __restrict__ nll,
+                                                                      int32_t* __restrict__ dead, double* __restrict__ kl_out)
+{
+    __shared__ double s_red[8];
+    const int fit = blockIdx.x;
+    double t = 0;
+    for (int b = threadIdx.x; b < n_blocks; b += 256) t += partial[(long long)fit * UPDATE_MAX_BLOCKS + b];
+    t = block_sum_d(t, s_red);
+    if (threadIdx.x == 0) { kl_out[fit] = t; if (!isfinite(nll[fit])) dead[fit] = 1; }
+}
+
+__global__ __launch_bounds__(256) void ema_fits_kernel(const float* __restrict__ out, int S, int C, long long HW, float* __restrict__ ema, float w, int first)
+{
+    const float* __restrict__ o = out + (long long)blockIdx.y * S * C * HW;
+    float* __restrict__ e = ema + (long long)blockIdx.y * C * HW;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < HW; i += (long long)gridDim.x * 256) {
+        float mean, ale;
+        (void)sample_means_ema(o, S, C, HW, i, e, w, first, mean, ale);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int mfvi_perturb_input_fits(const float* z0, uint64_t seed, uint32_t step, int64_t n_per_fit, int n_fits, uint32_t fit0, float std, float* z, void* stream)
+{
+    if (!z0 || !z || n_per_fit < 1 || n_fits < 1 || n_fits > 65535) { set_error("perturb_input_fits: bad arguments (n_per_fit=%lld n_fits=%d)", (long long)n_per_fit, n_fits); return -1; }
+    RngKey key; key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32); key.stream = (uint32_t)DOMAIN_INPUT << 24; key.sample = fit0; key.step = step; key.step_dev = nullptr;
+    hipLaunchKernelGGL(perturb_fits_kernel, dim3(nblocks((n_per_fit + 3) / 4), n_fits), dim3(256), 0, (hipStream_t)stream, key, (long long)n_per_fit, std, z0, z);
+    return (int)hipGetLastError();
+}
+
+int mfvi_gaussian_nll_fits(const float* out, const float* targets, int64_t target_stride, int n_fits, int S, int H, int W, int factor, float grad_scale,
+                           float* dout, double* nll, void* stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (!out || !targets || !nll || n_fits < 1 || S < 1 || (long long)n_fits * S > 65535 || factor < 1 || H < 1 || W < 1 || H % factor || W % factor ||
+        target_stride < (int64_t)(H / factor) * (W / factor)) {
+        set_error("gaussian_nll_fits: bad arguments (n_fits=%d S=%d H=%d W=%d factor=%d target_stride=%lld)", n_fits, S, H, W, factor, (long long)target_stride); return -1; }
+    const int n = n_fits * S;
+    if (dout && factor > 1) { hipError_t e = hipMemsetAsync(dout, 0, sizeof(float) * (size_t)n * 2 * H * W, st); if (e) return (int)e; }
+    const long long npix = (long long)(H / factor) * (W / factor);
+    if (factor == 1 && (W & 3) == 0 && !(target_stride & 3) && !(((uintptr_t)out | (uintptr_t)targets | (uintptr_t)dout) & 15))
+        hipLaunchKernelGGL(gaussian_nll_fits_kernel<true>, dim3(nblocks(npix / 4, 16), n), dim3(256), 0, st, out, targets, (long long)target_stride, S, H, W, 1, grad_scale, dout, nll);
+    else
+        hipLaunchKernelGGL(gaussian_nll_fits_kernel<false>, dim3(nblocks(npix, 16), n), dim3(256), 0, st, out, targets, (long long)target_stride, S, H, W, factor, grad_scale, dout, nll);
+    return (int)hipGetLastError();
+}
+
+int64_t mfvi_elbo_update_fits_scratch_bytes(int n_fits) { return n_fits < 1 ? -1 : (int64_t)n_fits * UPDATE_MAX_BLOCKS * (int64_t)sizeof(double); }
+
+int mfvi_elbo_update_fits(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, int64_t param_stride, int64_t grad_stride, int n_fits,
+                          const mfvi_fit_hyper* hyper_dev, float beta1, float beta2, float eps, int t, const double* nll, int32_t* dead, double* kl_out,
+                          void* scratch, void* stream)
+{
+    if (!params || !grads || !m || !v || !hyper_dev || !nll || !dead || !kl_out || !scratch || n_vi < 0 || n_bn < 0 || t < 1 || n_fits < 1 || n_fits > 65535 ||
+        param_stride < 2 * n_vi + n_bn || grad_stride < 2 * n_vi + n_bn) {
+        set_error("elbo_update_fits: bad arguments (t is 1-based, strides >= 2 n_vi + n_bn, scratch of mfvi_elbo_update_fits_scratch_bytes(n_fits) bytes)"); return -1; }
+    const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
+    const long long work = n_vi > n_bn ? n_vi : n_bn;
+    const int nb = nblocks(work, UPDATE_MAX_BLOCKS);
+    hipLaunchKernelGGL(elbo_update_fits_kernel, dim3(nb, n_fits), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, (long long)n_vi, (long long)n_bn,
+                       (long long)param_stride, (long long)grad_stride, hyper_dev, beta1, beta2, eps, bc1, (float)(1.0 / sqrt(bc2)), nll, (const int32_t*)dead,
+                       (double*)scratch);
+    hipLaunchKernelGGL(elbo_update_fits_finish_kernel, dim3(n_fits), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, nb, nll, dead, kl_out);
+    return (int)hipGetLastError();
+}
+
+int mfvi_ema_fits(const float* out, int n_fits, int S, int C, int H, int W, float* ema, float weight, int first, void* stream)
+{
+    if (!out || !ema || n_fits < 1 || n_fits > 65535 || S < 1 || C < 1 || C > 2 || H < 1 || W < 1) { set_error("ema_fits: bad arguments"); return -1; }
+    const long long HW = (long long)H * W;
+    hipLaunchKernelGGL(ema_fits_kernel, dim3(nblocks(HW, 256), n_fits), dim3(256), 0, (hipStream_t)stream, out, S, C, HW, ema, weight, first);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -1,0 +1,134 @@
+// Per-thread bodies of the element-wise kernels of one ELBO iteration (losses.hip), shared with the kernels that run the same pass for
+// many independent fits in one launch (fits.hip): the arithmetic of a fit in a batch is the single-fit arithmetic by construction.
+#pragma once
+#include "common.h"
+
+__device__ __forceinline__ void block_atomic_add(double v, double* dst, double* red)
+{
+    const double s = block_sum_d(v, red);
+    if (threadIdx.x == 0) atomicAdd(dst, s);
+}
+
+// ---- gaussian_nll (utils/bayesian_utils.py:29-32) of ONE sample o[2][H][W] against target[H/f][W/f]: this thread's share of the sum over the
+// pixels (grid x strides over them) and, with d, the gradient d[2][H][W] ----
+__device__ __forceinline__ double gnll_sample(const float* __restrict__ o, const float* __restrict__ target, int H, int W, int f, float grad_scale,
+                                              float* __restrict__ d)
+{
+    const int h = H / f, w = W / f;
+    const long long n = (long long)h * w, HW = (long long)H * W;
+    double acc = 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const int y = (int)(i / w), x = (int)(i - (long long)y * w);
+        const long long p = (long long)(y * f) * W + (long long)x * f;
+        const float m = o[p], sraw = o[HW + p];
+        const float s = fminf(fmaxf(sraw, -20.f), 20.f);
+        const bool inside = (sraw >= -20.f) && (sraw <= 20.f);
+        const float df = target[i] - m, e = expf(s);
+        acc += (double)(e * df * df - s);
+        if (d) {
+            d[p] = grad_scale * (-2.f * e * df) / (float)n;
+            d[HW + p] = inside ? grad_scale * (e * df * df - 1.f) / (float)n : 0.f;
+        }
+    }
+    return acc / (double)n;
+}
+// factor 1, W % 4 == 0, 16-byte aligned rows: float4 lanes, a thread's four groups requested before any is used (round 4: the scalar form was
+// a chain of 16 dependent-latency iterations per thread, 15 us for 24 MB).  Same per-element arithmetic, float partial sums per group folded
+// into the thread's fp64 sum.
+__device__ __forceinline__ double gnll_sample_vec(const float* __restrict__ o, const float* __restrict__ target, long long HW, float grad_scale,
+                                                  float* __restrict__ d)
+{
+    const long long ng = HW >> 2;
+    const float nf = (float)HW;
+    double acc = 0;
+    for (long long g0 = (long long)blockIdx.x * 256 + threadIdx.x; g0 < ng; g0 += (long long)gridDim.x * 256 * 4) {
+        float4 m4[4], s4[4], t4[4]; long long gi[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            gi[u] = g0 + (long long)u * gridDim.x * 256;
+            const long long gc = gi[u] < ng ? gi[u] : ng - 1;
+            m4[u] = *reinterpret_cast<const float4*>(o + 4 * gc); s4[u] = *reinterpret_cast<const float4*>(o + HW + 4 * gc); t4[u] = *reinterpret_cast<const float4*>(target + 4 * gc);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (gi[u] >= ng) continue;
+            const float mm[4] = {m4[u].x, m4[u].y, m4[u].z, m4[u].w}, ss[4] = {s4[u].x, s4[u].y, s4[u].z, s4[u].w}, tt[4] = {t4[u].x, t4[u].y, t4[u].z, t4[u].w};
+            float dm[4], ds[4];
+#pragma unroll
+            for (int l = 0; l < 4; ++l) {
+                const float sraw = ss[l];
+                const float s_ = fminf(fmaxf(sraw, -20.f), 20.f);
+                const bool inside = (sraw >= -20.f) && (sraw <= 20.f);
+                const float df = tt[l] - mm[l], e = expf(s_);
+                acc += (double)(e * df * df - s_);
+                dm[l] = grad_scale * (-2.f * e * df) / nf;
+                ds[l] = inside ? grad_scale * (e * df * df - 1.f) / nf : 0.f;
+            }
+            if (d) {
+                *reinterpret_cast<float4*>(d + 4 * gi[u]) = make_float4(dm[0], dm[1], dm[2], dm[3]);
+                *reinterpret_cast<float4*>(d + HW + 4 * gi[u]) = make_float4(ds[0], ds[1], ds[2], ds[3]);
+            }
+        }
+    }
+    return acc / (double)HW;
+}
+
+// ---- fused tail of an ELBO iteration on ONE flat block [MU | RHO | BN]: this thread's share (grid x strides over the elements) of the KL sum;
+// unless `skip`, grads += temp * dKL (written back) and AdamW(weight_decay = 0) on p / m / v ----
+__device__ __forceinline__ double elbo_update_share(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                    long long n_vi, long long n_bn, float m0, float s0, float temp, float b1, float b2, float eps,
+                                                    float step_size, float inv_sqrt_bc2, bool skip)
+{
+    const float log_s0 = logf(s0), s0sq = s0 * s0;
+    auto adam = [&](long long i, float gi) {
+        const float mi = b1 * m[i] + (1.f - b1) * gi;
+        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        m[i] = mi; v[i] = vi;
+        p[i] = p[i] - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
+    };
+    double acc = 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_vi; i += (long long)gridDim.x * 256) {
+        const float mu = p[i], r = p[n_vi + i];
+        const float s = softplus_f(r), d = mu - m0, inv = 1.f / s;
+        acc += (double)(logf(s) - log_s0) + (double)((s0sq + d * d) / (2.f * s * s)) - 0.5;
+        if (skip) continue;
+        const float gmu = g[i] + temp * d * inv * inv;
+        const float grho = g[n_vi + i] + temp * (inv - (s0sq + d * d) * inv * inv * inv) * sigmoid_f(r);
+        g[i] = gmu; g[n_vi + i] = grho;
+        adam(i, gmu); adam(n_vi + i, grho);
+    }
+    if (!skip)
+        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_bn; i += (long long)gridDim.x * 256) adam(2 * n_vi + i, g[2 * n_vi + i]);
+    return acc;
+}
+
+// ---- out[j] = (base ? base[j] : a) + b * N(0,1), element j = lane j & 3 of Philox block j >> 2 of the key's stream (grid x strides over the blocks) ----
+__device__ __forceinline__ void normal_fill_share(const RngKey& key, long long n, float a, float b, const float* __restrict__ base, float* __restrict__ out)
+{
+    const long long nblk = (n + 3) >> 2;
+    for (long long blk = (long long)blockIdx.x * 256 + threadIdx.x; blk < nblk; blk += (long long)gridDim.x * 256) {
+        float z[4]; spec_normal4(key, (uint32_t)blk, z);
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            const long long j = blk * 4 + l;
+            if (j < n) out[j] = (base ? base[j] : a) + b * z[l];
+        }
+    }
+}
+
+// ---- the runner's smoothed outputs (bayesian_optimization.py:1376-1381) at pixel i: m = mean_k out[k][0], a = mean_k exp(-out[k][1]) over the
+// n samples out[n][C][HW]; ema[c] = first ? value : ema[c] * w + value * (1 - w).  Returns the new ema[0][i] ----
+__device__ __forceinline__ float sample_means_ema(const float* __restrict__ out, int n, int C, long long HW, long long i, float* __restrict__ ema, float w,
+                                                  int first, float& m, float& a)
+{
+    m = 0.f; a = 0.f;
+    for (int k = 0; k < n; ++k) {
+        m += out[(long long)k * C * HW + i];
+        if (C > 1) a += expf(-out[(long long)k * C * HW + HW + i]);
+    }
+    m /= (float)n; a /= (float)n;
+    const float e0 = first ? m : ema[i] * w + m * (1.f - w);
+    ema[i] = e0;
+    if (C > 1) ema[HW + i] = first ? a : ema[HW + i] * w + a * (1.f - w);
+    return e0;
+}

@@ -3,89 +3,30 @@
 // AdamW(wd=0) (bayesian_optimization.py:1356-1357), RNG fills, per-iteration bookkeeping
 // (bayesian_optimization.py:1374-1406, utils/common_utils.py:297-353).
 #include "common.h"
+#include "iter_ops.h"
 #include <algorithm>
 #include <type_traits>
 #include "../../include/mfvi_hip.h"
 
 namespace {
 
-__device__ __forceinline__ void block_atomic_add(double v, double* dst, double* red)
-{
-    const double s = block_sum_d(v, red);
-    if (threadIdx.x == 0) atomicAdd(dst, s);
-}
-
-// ---- gaussian_nll ---------------------------------------------------------------------------
+// ---- gaussian_nll (bodies: iter_ops.h) ------------------------------------------------------------
 __global__ __launch_bounds__(256) void gaussian_nll_kernel(const float* __restrict__ out, const float* __restrict__ target,
                                                            int H, int W, int f, float grad_scale, float* __restrict__ dout,
                                                            double* __restrict__ nll_sum)
 {
     __shared__ double s_red[8];
     const int k = blockIdx.y;
-    const int h = H / f, w = W / f;
-    const long long n = (long long)h * w, HW = (long long)H * W;
-    const float* __restrict__ o = out + (long long)k * 2 * HW;
-    float* __restrict__ d = dout ? dout + (long long)k * 2 * HW : nullptr;
-    double acc = 0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const int y = (int)(i / w), x = (int)(i - (long long)y * w);
-        const long long p = (long long)(y * f) * W + (long long)x * f;
-        const float m = o[p], sraw = o[HW + p];
-        const float s = fminf(fmaxf(sraw, -20.f), 20.f);
-        const bool inside = (sraw >= -20.f) && (sraw <= 20.f);
-        const float df = target[i] - m, e = expf(s);
-        acc += (double)(e * df * df - s);
-        if (d) {
-            d[p] = grad_scale * (-2.f * e * df) / (float)n;
-            d[HW + p] = inside ? grad_scale * (e * df * df - 1.f) / (float)n : 0.f;
-        }
-    }
-    block_atomic_add(acc / (double)n, nll_sum, s_red);
+    const long long HW = (long long)H * W;
+    block_atomic_add(gnll_sample(out + (long long)k * 2 * HW, target, H, W, f, grad_scale, dout ? dout + (long long)k * 2 * HW : nullptr), nll_sum, s_red);
 }
 
-// factor 1, W % 4 == 0, 16-byte aligned rows: float4 lanes, a thread's four groups requested before any is used (round 4: the scalar form was
-// a chain of 16 dependent-latency iterations per thread, 15 us for 24 MB).  Same per-element arithmetic, float partial sums per group folded
-// into the thread's fp64 sum.
 __global__ __launch_bounds__(256) void gaussian_nll_vec_kernel(const float* __restrict__ out, const float* __restrict__ target, long long HW,
                                                                float grad_scale, float* __restrict__ dout, double* __restrict__ nll_sum)
 {
     __shared__ double s_red[8];
     const int k = blockIdx.y;
-    const long long ng = HW >> 2;
-    const float* __restrict__ o = out + (long long)k * 2 * HW;
-    float* __restrict__ d = dout ? dout + (long long)k * 2 * HW : nullptr;
-    const float nf = (float)HW;
-    double acc = 0;
-    for (long long g0 = (long long)blockIdx.x * 256 + threadIdx.x; g0 < ng; g0 += (long long)gridDim.x * 256 * 4) {
-        float4 m4[4], s4[4], t4[4]; long long gi[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            gi[u] = g0 + (long long)u * gridDim.x * 256;
-            const long long gc = gi[u] < ng ? gi[u] : ng - 1;
-            m4[u] = *reinterpret_cast<const float4*>(o + 4 * gc); s4[u] = *reinterpret_cast<const float4*>(o + HW + 4 * gc); t4[u] = *reinterpret_cast<const float4*>(target + 4 * gc);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (gi[u] >= ng) continue;
-            const float mm[4] = {m4[u].x, m4[u].y, m4[u].z, m4[u].w}, ss[4] = {s4[u].x, s4[u].y, s4[u].z, s4[u].w}, tt[4] = {t4[u].x, t4[u].y, t4[u].z, t4[u].w};
-            float dm[4], ds[4];
-#pragma unroll
-            for (int l = 0; l < 4; ++l) {
-                const float sraw = ss[l];
-                const float s_ = fminf(fmaxf(sraw, -20.f), 20.f);
-                const bool inside = (sraw >= -20.f) && (sraw <= 20.f);
-                const float df = tt[l] - mm[l], e = expf(s_);
-                acc += (double)(e * df * df - s_);
-                dm[l] = grad_scale * (-2.f * e * df) / nf;
-                ds[l] = inside ? grad_scale * (e * df * df - 1.f) / nf : 0.f;
-            }
-            if (d) {
-                *reinterpret_cast<float4*>(d + 4 * gi[u]) = make_float4(dm[0], dm[1], dm[2], dm[3]);
-                *reinterpret_cast<float4*>(d + HW + 4 * gi[u]) = make_float4(ds[0], ds[1], ds[2], ds[3]);
-            }
-        }
-    }
-    block_atomic_add(acc / (double)HW, nll_sum, s_red);
+    block_atomic_add(gnll_sample_vec(out + (long long)k * 2 * HW, target, HW, grad_scale, dout ? dout + (long long)k * 2 * HW : nullptr), nll_sum, s_red);
 }
 
 // ---- gaussian_nll_inpainting: sigmoid on the 3 colour channels, one shared log-precision channel, mask ----
@@ -313,26 +254,7 @@ __global__ __launch_bounds__(256) void elbo_update_kernel(float* __restrict__ p,
     __shared__ float s_bc[2];
     const bool skip = guard_skip(guard);             // NaN data term: KL is still reported, nothing is written
     adam_bias(guard, lr, b1, b2, s_bc, step_size, inv_sqrt_bc2);
-    const float log_s0 = logf(s0), s0sq = s0 * s0;
-    auto adam = [&](long long i, float gi) {
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        p[i] = p[i] - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
-    };
-    double acc = 0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_vi; i += (long long)gridDim.x * 256) {
-        const float mu = p[i], r = p[n_vi + i];
-        const float s = softplus_f(r), d = mu - m0, inv = 1.f / s;
-        acc += (double)(logf(s) - log_s0) + (double)((s0sq + d * d) / (2.f * s * s)) - 0.5;
-        if (skip) continue;
-        const float gmu = g[i] + temp * d * inv * inv;
-        const float grho = g[n_vi + i] + temp * (inv - (s0sq + d * d) * inv * inv * inv) * sigmoid_f(r);
-        g[i] = gmu; g[n_vi + i] = grho;
-        adam(i, gmu); adam(n_vi + i, grho);
-    }
-    if (!skip)
-        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_bn; i += (long long)gridDim.x * 256) adam(2 * n_vi + i, g[2 * n_vi + i]);
+    const double acc = elbo_update_share(p, g, m, v, n_vi, n_bn, m0, s0, temp, b1, b2, eps, step_size, inv_sqrt_bc2, skip);
     const double tot = block_sum_d(acc, s_red);
     if (threadIdx.x == 0) sc->partial[blockIdx.x] = tot;
 }
@@ -360,16 +282,7 @@ __global__ __launch_bounds__(256) void decimate_kernel(const float* __restrict__
 __global__ __launch_bounds__(256) void normal_fill_kernel(RngKey key, long long n, float a, float b, const float* __restrict__ base,
                                                           float* __restrict__ out)
 {
-    key = key_now(key);
-    const long long nblk = (n + 3) >> 2;
-    for (long long blk = (long long)blockIdx.x * 256 + threadIdx.x; blk < nblk; blk += (long long)gridDim.x * 256) {
-        float z[4]; spec_normal4(key, (uint32_t)blk, z);
-#pragma unroll
-        for (int l = 0; l < 4; ++l) {
-            const long long j = blk * 4 + l;
-            if (j < n) out[j] = (base ? base[j] : a) + b * z[l];
-        }
-    }
+    normal_fill_share(key_now(key), n, a, b, base, out);
 }
 __global__ __launch_bounds__(256) void uniform_fill_kernel(RngKey key, long long n, float scale, float* __restrict__ out, float lo = 0.f)
 {
@@ -444,15 +357,8 @@ __global__ __launch_bounds__(256) void bookkeep_kernel(const float* __restrict__
                                                        float* __restrict__ avg_clip, float* __restrict__ ring_epi, float* __restrict__ ring_ale)
 {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < HW; i += (long long)gridDim.x * 256) {
-        float m = 0.f, a = 0.f;
-        for (int k = 0; k < n; ++k) {
-            m += out[(long long)k * C * HW + i];
-            if (C > 1) a += expf(-out[(long long)k * C * HW + HW + i]);
-        }
-        m /= (float)n; a /= (float)n;
-        const float e0 = first ? m : ema[i] * w + m * (1.f - w);
-        ema[i] = e0;
-        if (C > 1) ema[HW + i] = first ? a : ema[HW + i] * w + a * (1.f - w);
+        float m, a;
+        const float e0 = sample_means_ema(out, n, C, HW, i, ema, w, first, m, a);
         const float mc = fminf(fmaxf(m, 0.f), 1.f), ac = fminf(fmaxf(a, 0.f), 1.f);
         out_clip[i] = mc; avg_clip[i] = fminf(fmaxf(e0, 0.f), 1.f);
         if (ring_epi) ring_epi[i] = mc;
@@ -544,14 +450,19 @@ __global__ __launch_bounds__(256) void grad_finalize_kernel(const GradFinEntry* 
                                                             float* __restrict__ dmu, float* __restrict__ drho,
                                                             const float* __restrict__ wsamp, long long wstride, const void* __restrict__ mu_v,
                                                             int n_main_blocks, const BnGradEntry* __restrict__ bn_table, const double* __restrict__ bsums_base,
-                                                            float* __restrict__ dbn)
+                                                            float* __restrict__ dbn, int fit_s, long long param_fstride, long long grad_fstride)
 {
+    // fits mode (fit_s > 0, grid y = fit): this block reduces the fit's samples k_lo .. k_lo + fit_s - 1 only, with the fit's rho (and mu), into
+    // the fit's dmu / drho / dbn.  One fit (fit_s = 0): k_lo = 0, every sample, the pointers as given.
+    const int k_lo = (int)blockIdx.y * fit_s, n_total = n_samples;
+    if (fit_s) { n_samples = fit_s; dmu += (long long)blockIdx.y * grad_fstride; drho += (long long)blockIdx.y * grad_fstride; if (dbn) dbn += (long long)blockIdx.y * grad_fstride; }
     // blocks behind the weight-gradient blocks: the BatchNorm parameter gradients, one table entry each (round 4: bn_param_grads_kernel was a
     // dependent launch of its own at the tail of every iteration)
-    if ((int)blockIdx.x >= n_main_blocks) { bn_param_grads_entry(bn_table[(int)blockIdx.x - n_main_blocks], bsums_base, n_samples, dbn); return; }
+    if ((int)blockIdx.x >= n_main_blocks) { bn_param_grads_entry(bn_table[(int)blockIdx.x - n_main_blocks], bsums_base, n_samples, dbn, k_lo); return; }
     key = key_now(key);
     typedef typename std::conditional<BF16, bf16_t, float>::type PT;
-    const PT* __restrict__ rho = static_cast<const PT*>(rho_v); const PT* __restrict__ mu = static_cast<const PT*>(mu_v);
+    const PT* __restrict__ rho = static_cast<const PT*>(rho_v) + (long long)blockIdx.y * param_fstride;
+    const PT* __restrict__ mu = mu_v ? static_cast<const PT*>(mu_v) + (long long)blockIdx.y * param_fstride : nullptr;
     auto ld = [](const PT* q) -> float { if constexpr (BF16) return bf16_to_f32(*q); else return *q; };
     __shared__ float s_mu[3][GRAD_FIN_QUADS][4], s_rh[3][GRAD_FIN_QUADS][4];
     __shared__ int s_first[TABLE_LDS];
@@ -579,8 +490,8 @@ __global__ __launch_bounds__(256) void grad_finalize_kernel(const GradFinEntry* 
             const int k = kb + 4 * ku;
             if (k >= n_samples) break;
             float sk[4] = {0.f, 0.f, 0.f, 0.f};
-            const float* __restrict__ q0 = P + (long long)k * e.stride;
-            const long long sstep = (long long)n_samples * e.stride;          // next pixel strip of the same sample
+            const float* __restrict__ q0 = P + (long long)(k_lo + k) * e.stride;
+            const long long sstep = (long long)n_total * e.stride;            // next pixel strip of the same sample
             // weights and biases alike: the bias columns start at n_w (a multiple of 4) and the slab row is padded to a multiple of 4,
             // so a bias quad is one aligned float4 too.  (A scalar loop over strips x elements for the bias quads was a chain of up to
             // 4 x 64 x 4 dependent loads in a handful of lanes and set the duration of the whole launch: 120 us.)
@@ -602,7 +513,7 @@ __global__ __launch_bounds__(256) void grad_finalize_kernel(const GradFinEntry* 
 #pragma unroll
             for (int l = 0; l < 4; ++l) am[l] += sk[l];
             if (from_slab) {
-                const float* __restrict__ wk = wsamp + (long long)k * wstride + jq;
+                const float* __restrict__ wk = wsamp + (long long)(k_lo + k) * wstride + jq;
                 if (is_w) {          // w_off % 4 == 0 for every layer of the slab: aligned float4
                     const float4 w = *reinterpret_cast<const float4*>(wk);
                     ar[0] = __builtin_fmaf(sk[0], w.x - mq[0], ar[0]); ar[1] = __builtin_fmaf(sk[1], w.y - mq[1], ar[1]);
@@ -610,7 +521,7 @@ __global__ __launch_bounds__(256) void grad_finalize_kernel(const GradFinEntry* 
                 } else
                     for (int l = 0; l < nv; ++l) ar[l] = __builtin_fmaf(sk[l], wk[l] - mq[l], ar[l]);
             } else if (sample_weights) {
-                RngKey kw = key; kw.sample += (uint32_t)k;
+                RngKey kw = key; kw.sample += (uint32_t)(k_lo + k);
                 kw.stream = ((uint32_t)DOMAIN_EPS << 24) | (uint32_t)(2 * e.layer_id + (is_w ? 0 : 1));
                 float z[4]; spec_normal4(kw, (uint32_t)quad, z);
 #pragma unroll
@@ -650,7 +561,7 @@ template <bool BF16>
 __global__ __launch_bounds__(256) void sample_weights_kernel(const SampleEntry* __restrict__ table, int n_entries,
                                                              const void* __restrict__ mu_v, const void* __restrict__ rho_v,
                                                              RngKey key, float* __restrict__ wsamp, long long wstride, int sample,
-                                                             double* __restrict__ zero, long long n_zero, int n_k)
+                                                             double* __restrict__ zero, long long n_zero, int n_k, int fit_s, long long param_fstride)
 {
     key = key_now(key);
     // the pass's statistics buffers, cleared by the draw's own threads (plan_forward.hip, begin_forward)
@@ -672,7 +583,15 @@ __global__ __launch_bounds__(256) void sample_weights_kernel(const SampleEntry* 
         else { m = *reinterpret_cast<const float4*>(mu + j); r = *reinterpret_cast<const float4*>(rho + j); }
         float sp[4] = {0.f, 0.f, 0.f, 0.f};
         if (sample) { sp[0] = softplus_fast(r.x); sp[1] = softplus_fast(r.y); sp[2] = softplus_fast(r.z); sp[3] = softplus_fast(r.w); }
+        int fit = 0;
         for (int k = k0; k < k1; ++k) {
+            if (fit_s && k / fit_s != fit) {      // fits mode: the thread's samples may belong to different fits; mu, rho, softplus(rho) of the sample's fit
+                fit = k / fit_s;
+                const long long jf = j + (long long)fit * param_fstride;
+                if constexpr (BF16) { m = bf16x4_to_f32(mu + jf); r = bf16x4_to_f32(rho + jf); }
+                else { m = *reinterpret_cast<const float4*>(mu + jf); r = *reinterpret_cast<const float4*>(rho + jf); }
+                if (sample) { sp[0] = softplus_fast(r.x); sp[1] = softplus_fast(r.y); sp[2] = softplus_fast(r.z); sp[3] = softplus_fast(r.w); }
+            }
             RngKey kw = key; kw.sample += (uint32_t)k;
             kw.stream = ((uint32_t)DOMAIN_EPS << 24) | (uint32_t)(2 * e.layer_id);
             float z[4] = {0.f, 0.f, 0.f, 0.f};
@@ -689,10 +608,11 @@ __global__ __launch_bounds__(256) void sample_weights_kernel(const SampleEntry* 
             float z[4] = {0.f, 0.f, 0.f, 0.f};
             if (sample) spec_normal4(kw, (uint32_t)q, z);
             float* __restrict__ o = wsamp + (long long)k * wstride;
+            const long long pf = fit_s ? (long long)(k / fit_s) * param_fstride : 0;      // the sample's fit
             for (int l = 0; l < 4 && 4 * q + l < e.n_b; ++l) {
                 const long long j = e.b_off + 4 * q + l;
                 float mj, rj;
-                if constexpr (BF16) { mj = bf16_to_f32(mu[j]); rj = bf16_to_f32(rho[j]); } else { mj = mu[j]; rj = rho[j]; }
+                if constexpr (BF16) { mj = bf16_to_f32(mu[pf + j]); rj = bf16_to_f32(rho[pf + j]); } else { mj = mu[pf + j]; rj = rho[pf + j]; }
                 o[j] = sample ? mj + softplus_f(rj) * z[l] : mj;
             }
         }
@@ -763,12 +683,13 @@ int launch_dropout_masks(const DropEntry* table_dev, int n_entries, RngKey key, 
 }
 
 int launch_sample_weights(const SampleEntry* table_dev, int n_entries, int n_blocks, const void* mu, const void* rho, RngKey key,
-                          int n_samples, float* wsamp, long long wstride, hipStream_t st, int bf16, int sample, double* zero, long long n_zero)
+                          int n_samples, float* wsamp, long long wstride, hipStream_t st, int bf16, int sample, double* zero, long long n_zero,
+                          int fit_s, long long param_fstride)
 {
     if (n_entries < 1 || n_blocks < 1) { if (n_zero > 0) return (int)hipMemsetAsync(zero, 0, sizeof(double) * n_zero, st); return 0; }
     const dim3 grid(n_blocks, (n_samples + SAMPLE_KPT - 1) / SAMPLE_KPT);
-    if (bf16) hipLaunchKernelGGL(sample_weights_kernel<true>, grid, dim3(256), 0, st, table_dev, n_entries, mu, rho, key, wsamp, wstride, sample, zero, n_zero, n_samples);
-    else hipLaunchKernelGGL(sample_weights_kernel<false>, grid, dim3(256), 0, st, table_dev, n_entries, mu, rho, key, wsamp, wstride, sample, zero, n_zero, n_samples);
+    if (bf16) hipLaunchKernelGGL(sample_weights_kernel<true>, grid, dim3(256), 0, st, table_dev, n_entries, mu, rho, key, wsamp, wstride, sample, zero, n_zero, n_samples, fit_s, param_fstride);
+    else hipLaunchKernelGGL(sample_weights_kernel<false>, grid, dim3(256), 0, st, table_dev, n_entries, mu, rho, key, wsamp, wstride, sample, zero, n_zero, n_samples, fit_s, param_fstride);
     return (int)hipGetLastError();
 }
 
@@ -781,14 +702,16 @@ int launch_expand_bf16(const void* src, long long n, float* dst, hipStream_t st)
 
 int launch_grad_finalize(const GradFinEntry* table_dev, int n_entries, int n_blocks, const float* part_base, const void* rho, RngKey key,
                          int sample_weights, int n_samples, float* dmu, float* drho, const float* wsamp, long long wstride, const void* mu,
-                         hipStream_t st, int bf16, const BnGradEntry* bn_table, int n_bn, const double* bsums_base, float* dbn)
+                         hipStream_t st, int bf16, const BnGradEntry* bn_table, int n_bn, const double* bsums_base, float* dbn,
+                         int fit_s, long long param_fstride, long long grad_fstride)
 {
     if (n_entries < 1 || n_blocks < 1) return 0;      // (the caller launches bn_param_grads itself when there is nothing to reduce)
     if (!bn_table || !dbn) n_bn = 0;
-    if (bf16) hipLaunchKernelGGL(grad_finalize_kernel<true>, dim3(n_blocks + n_bn), dim3(256), 0, st, table_dev, n_entries, part_base, rho, key, sample_weights,
-                                 n_samples, dmu, drho, wsamp, wstride, mu, n_blocks, bn_table, bsums_base, dbn);
-    else hipLaunchKernelGGL(grad_finalize_kernel<false>, dim3(n_blocks + n_bn), dim3(256), 0, st, table_dev, n_entries, part_base, rho, key, sample_weights,
-                            n_samples, dmu, drho, wsamp, wstride, mu, n_blocks, bn_table, bsums_base, dbn);
+    const int n_fits = fit_s ? n_samples / fit_s : 1;
+    if (bf16) hipLaunchKernelGGL(grad_finalize_kernel<true>, dim3(n_blocks + n_bn, n_fits), dim3(256), 0, st, table_dev, n_entries, part_base, rho, key, sample_weights,
+                                 n_samples, dmu, drho, wsamp, wstride, mu, n_blocks, bn_table, bsums_base, dbn, fit_s, param_fstride, grad_fstride);
+    else hipLaunchKernelGGL(grad_finalize_kernel<false>, dim3(n_blocks + n_bn, n_fits), dim3(256), 0, st, table_dev, n_entries, part_base, rho, key, sample_weights,
+                            n_samples, dmu, drho, wsamp, wstride, mu, n_blocks, bn_table, bsums_base, dbn, fit_s, param_fstride, grad_fstride);
     return (int)hipGetLastError();
 }
 

@@ -39,6 +39,23 @@ bool check_call(const mfvi_plan* p, int n_samples, const void* ws)
     return true;
 }
 
+// Fits mode runs on the sampled-weight slab alone: whatever reads ONE mu / rho / bn for all samples, or reduces over all of them, is refused
+// rather than served with fit 0's parameters.
+int fits_refusal(const mfvi_plan* p, const char* who)
+{
+    const char* what = nullptr;
+    if (p->param_dtype == MFVI_PARAM_BF16) what = "bf16 parameter storage";
+    else if (p->n_lrt) what = "local-reparameterisation layers";
+    else if (p->bn_eval) what = "BatchNorm eval mode";
+    else if (p->split_op >= 0) what = "a gradient split";
+    else if (p->step_dev) what = "a device step source";
+    else if (p->n_generic > 0 || p->n_samp < 1) what = "layers outside the sampling table (input channels and weight offsets must be multiples of 4)";
+    else if (!use_mfma()) what = "MFVI_DISABLE_MFMA (the generic kernels read one mu / rho)";
+    if (!what) return 0;
+    set_error("%s: fits mode (mfvi_plan_set_fits) does not serve %s", who, what);
+    return MFVI_ERR_FITS_UNSUPPORTED;
+}
+
 namespace {
 
 inline long long align_up(long long v, long long a) { return (v + a - 1) / a * a; }
@@ -247,6 +264,22 @@ int pass_setup(PassSetup& S, bool expand, uint64_t seed, uint32_t step, uint32_t
     S.presample = use_mfma() && (S.sample_weights || S.bf16) && plan->n_samp > 0;
     S.key = base_key(seed, step, k0, plan->step_dev);
     S.W = ConvWeights{S.presample ? S.c.wsamp() : S.mu, (S.presample && S.sample_weights) ? plan->n_vi : 0, S.mu, S.rho, S.key, S.sample_weights};
+    if (plan->fit_s) {
+        // F = n_samples / fit_s fits in one pass: sample i is sample i % fit_s of fit i / fit_s and uses eps of global sample k0 + i
+        if (int rc = fits_refusal(plan, S.who)) return rc;
+        if (!S.sample_weights) { set_error("%s: fits mode (mfvi_plan_set_fits) does not serve sample_weights = 0", S.who); return MFVI_ERR_FITS_UNSUPPORTED; }
+        if (S.n_samples % plan->fit_s) { set_error("%s: n_samples %d is not a multiple of the %d samples per fit", S.who, S.n_samples, plan->fit_s); return -1; }
+        S.c.fit_s = plan->fit_s; S.c.gamma_fstride = plan->fit_pstride; S.c.z_sstride = plan->t[plan->input].numel;
+        if (plan->fit_s > 1) {      // z[n_fits][Cin][H][W] once per sample
+            float* zr = S.c.farena() + plan->zrep_off;
+            const int rc = launch_replicate_input(S.c.z, plan->t[plan->input].numel, plan->fit_s, S.n_samples, zr, S.st);
+            if (rc) { set_error("%s: fits mode: the copy of the net input per sample failed (its size must be a multiple of 4 floats, z 16-byte aligned): %s", S.who, hipGetErrorString((hipError_t)rc)); return rc > 0 ? rc : -1; }
+            S.c.z = zr;
+        }
+        // the generic kernels draw from ONE mu / rho: a layer that lands there is an error (conv_dispatch.hip, to_generic), never fit 0's parameters
+        S.mu = S.rho = nullptr;
+        S.W = ConvWeights{S.c.wsamp(), plan->n_vi, nullptr, nullptr, S.key, 1, 1};
+    }
     return 0;
 }
 
@@ -357,6 +390,28 @@ int mfvi_plan_set_grad_split(mfvi_plan* plan, int first_op, void* comm_stream)
     return 0;
 }
 
+int mfvi_plan_set_fits(mfvi_plan* plan, int samples_per_fit, int64_t param_stride, int64_t grad_stride)
+{
+    if (!plan) { set_error("set_fits: null plan"); return -1; }
+    plan->samp_n = 0;
+    if (samples_per_fit == 0) { plan->fit_s = 0; plan->fit_pstride = plan->fit_gstride = 0; return 0; }
+    const long long n_params = 2 * plan->n_vi + plan->n_bn;
+    if (samples_per_fit < 0 || samples_per_fit > plan->max_samples || param_stride < 0 || grad_stride < 0) {
+        set_error("set_fits: samples_per_fit %d outside 0..%d, or a negative stride (%lld, %lld; %lld parameters per fit)",
+                  samples_per_fit, plan->max_samples, (long long)param_stride, (long long)grad_stride, n_params); return -1; }
+    if (int rc = fits_refusal(plan, "set_fits")) return rc;
+    if (samples_per_fit > 1 && plan->zrep_off < 0) {      // room for the net input once per sample, behind everything laid out so far
+        const long long n = plan->t[plan->input].numel * plan->max_samples;
+        plan->zrep_off = (plan->total_bytes - plan->float_base) / (long long)sizeof(float);
+        plan->total_bytes += align_up(n, 64) * (long long)sizeof(float);
+    }
+    // in-kernel-eps tilings (bit 27) route a layer to the generic kernels, which read one mu / rho: back to the heuristic for those
+    for (auto& o : plan->ops)
+        if (o.d.type == MFVI_OP_CONV) for (int& t : o.g.tune) if (t & MFVI_TUNE_GENERIC) t = 0;
+    plan->fit_s = samples_per_fit; plan->fit_pstride = param_stride; plan->fit_gstride = grad_stride;
+    return 0;
+}
+
 int mfvi_plan_set_step_source(mfvi_plan* plan, const int32_t* step_dev)
 {
     if (!plan) { set_error("set_step_source: null plan"); return -1; }
@@ -390,6 +445,7 @@ int mfvi_plan_bn_update_running(const mfvi_plan* plan, const void* workspace, in
     if (!plan || !workspace || !running || n_samples < 1 || n_samples > plan->max_samples || !(momentum >= 0.f && momentum <= 1.f)) {
         set_error("bn_update_running: bad arguments"); return -1; }
     if (plan->bn_eval) { set_error("bn_update_running: the plan is in BatchNorm eval mode (no batch statistics were formed)"); return -1; }
+    if (plan->fit_s) { set_error("bn_update_running: fits mode (mfvi_plan_set_fits) does not serve running statistics (one block for all samples)"); return MFVI_ERR_FITS_UNSUPPORTED; }
     const int rc = launch_bn_update_running(plan->table_dev, plan->n_entries, plan->max_c, (const double*)workspace, n_samples, momentum, running, (hipStream_t)stream);
     if (rc) set_error("bn_update_running: %s", hipGetErrorString((hipError_t)rc));
     return rc;

@@ -80,6 +80,7 @@ extern "C" int mfvi_plan_autotune(mfvi_plan* plan, const void* mu, const void* r
 {
     if (!check_call(plan, n_samples, workspace)) return -1;
     if (!mu || !rho || !z || !out_scratch || !grad_scratch || (plan->n_bn > 0 && !bn)) { set_error("autotune: null pointer argument"); return -1; }
+    if (plan->fit_s) { set_error("autotune: run it before mfvi_plan_set_fits switches fits mode on (the tilings do not depend on the mode)"); return MFVI_ERR_FITS_UNSUPPORTED; }
     { const char* e = getenv("MFVI_AUTOTUNE"); if ((e && e[0] == '0') || !use_mfma()) return 0; }
     hipStream_t st = (hipStream_t)stream;
     const long long n_out = plan->t[plan->output].numel * n_samples;

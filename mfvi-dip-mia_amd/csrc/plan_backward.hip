@@ -58,7 +58,7 @@ int begin_backward(Backward& B, void* workspace, uint64_t seed, uint32_t step, u
     if (S.presample && !held) {
         ProfScope ps(plan, -1, PASS_SAMPLE, st);
         const int rc = launch_sample_weights(plan->samp_dev, plan->n_samp, plan->samp_blocks, S.mu_v, S.rho_v, S.key, S.sample_weights ? S.n_samples : 1, c.wsamp(),
-                                             plan->n_vi, st, S.bf16, S.sample_weights);
+                                             plan->n_vi, st, S.bf16, S.sample_weights, nullptr, 0, plan->fit_s, plan->fit_pstride);
         if (rc) { set_error("backward: sample_weights launch failed: %s", hipGetErrorString((hipError_t)rc)); return rc; }
     }
     // one use per draw: the parameters are updated in place in the same buffers, so a later backward with the same counters (a second
@@ -124,7 +124,8 @@ int finalize_grads(Backward& B, hipStream_t fs, int slot, bool with_bn = false)
     // every layer of `fin` (MFMA backward-weight) is also in the sampling table (same shape conditions), so its W_k sit in the slab
     const int rc = launch_grad_finalize(T.dev, (int)fin.size(), fin_blocks, S.c.farena(), S.rho_v, S.key, S.sample_weights, S.n_samples, B.dmu, B.drho,
                                         S.presample && S.sample_weights && switches().grad_from_slab ? S.c.wsamp() : nullptr, plan->n_vi, S.mu_v, fs, S.bf16,
-                                        with_bn ? plan->table_dev : nullptr, with_bn ? plan->n_entries : 0, S.c.bsums(), B.dbn);
+                                        with_bn ? plan->table_dev : nullptr, with_bn ? plan->n_entries : 0, S.c.bsums(), B.dbn, plan->fit_s, plan->fit_pstride,
+                                        plan->fit_gstride);
     if (rc) { set_error("backward: grad_finalize launch failed: %s", hipGetErrorString((hipError_t)rc)); return rc; }
     if (with_bn && plan->n_entries) B.bn_done = true;
     fin.clear();
@@ -323,7 +324,7 @@ extern "C" int mfvi_backward(mfvi_plan* plan, const void* mu_v, const void* rho_
         if (rc) { set_error("backward: lrt_drho launch failed: %s", hipGetErrorString((hipError_t)rc)); return rc; }
     }
     if (plan->n_entries && !B.bn_done) {
-        rc = launch_bn_param_grads(plan->table_dev, plan->n_entries, plan->max_c, B.S.c.bsums(), n_samples, dbn, st);
+        rc = launch_bn_param_grads(plan->table_dev, plan->n_entries, plan->max_c, B.S.c.bsums(), n_samples, dbn, st, plan->fit_s, plan->fit_gstride);
         if (rc) { set_error("backward: bn_param_grads launch failed: %s", hipGetErrorString((hipError_t)rc)); return rc; }
     }
     return 0;

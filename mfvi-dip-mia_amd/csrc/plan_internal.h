@@ -106,6 +106,10 @@ struct mfvi_plan {
     int n_generic = 0;                         // conv layers outside the sampling table (served by the generic fp32 kernels)
     long long p32_off = -1;                    // floats: [mu | rho] expanded to float32 for those kernels when mu / rho are bf16
     const float* bn_eval = nullptr;            // BatchNorm in eval mode: running statistics used by mfvi_forward (nullptr: batch statistics)
+    // fits mode (mfvi_plan_set_fits): the samples of a call are n_samples / fit_s independent fits of fit_s samples each;
+    // mu / rho / bn of fit j lie j * fit_pstride floats behind the pointers of the call, its gradients j * fit_gstride.  0: one fit (off)
+    int fit_s = 0; long long fit_pstride = 0, fit_gstride = 0;
+    long long zrep_off = -1;                   // floats: the net input once per SAMPLE [max_samples][Cin][H][W] (fit_s > 1: the kernels address it by sample)
     int n_lrt = 0;                             // local-reparameterisation layers
     long long sig2_off = -1, dsig2_off = -1;   // floats [n_vi] each: softplus(rho)^2 of this pass / gradient wrt it
     long long lrt_tmp_off = -1, lrt_tmp_n = 0; // floats: mean-convolution output (forward) / ds2 (backward) of the LRT layer in flight
@@ -169,6 +173,8 @@ const PlanSwitches& switches();
 
 bool fail(const char* fmt, ...);      // sets the error string, returns false
 bool check_call(const mfvi_plan* p, int n_samples, const void* ws);
+// fits mode: what it does not serve in the plan's current state (message set), else nullptr-equivalent 0.  One predicate for mfvi_plan_set_fits and every pass
+int fits_refusal(const mfvi_plan* p, const char* who);
 
 enum { PASS_FWD = 0, PASS_BWD_WEIGHT = 1, PASS_BWD_DATA = 2, PASS_FINALIZE = 3, PASS_CONCAT_BWD = 4, PASS_GRAD_FINALIZE = 5, PASS_SAMPLE = 6 };
 
@@ -187,6 +193,7 @@ struct ProfScope {
 
 struct Ctx {
     const mfvi_plan& p; char* ws; const float* bn; const float* z; int n;
+    int fit_s = 0; long long gamma_fstride = 0, z_sstride = 0;      // fits mode (set by pass_setup): per-fit BatchNorm parameters, one net input per sample
     double* fstats() const { return (double*)ws; }
     double* bsums() const { return (double*)ws + p.stats_doubles; }
     float* farena() const { return (float*)(ws + p.float_base); }
@@ -194,7 +201,7 @@ struct Ctx {
     TView view(int i, const float* out_ptr = nullptr) const
     {
         const TensorInfo& t = p.t[i]; TView v;
-        if (i == p.input) { v.data = z; v.sstride = 0; }
+        if (i == p.input) { v.data = z; v.sstride = z_sstride; }
         else if (i == p.output) { v.data = out_ptr; v.sstride = t.numel; }
         else { v.data = farena() + t.act_off; v.sstride = t.numel; }
         v.C = t.d.C; v.H = t.d.H; v.W = t.d.W;
@@ -202,6 +209,7 @@ struct Ctx {
         v.gamma = t.d.has_bn ? bn + t.d.bn_off : nullptr;
         v.eps = t.d.eps; v.slope = t.d.slope; v.act = t.d.has_act;
         v.drop = (t.drop_off >= 0 && p.dropout_on) ? farena() + t.drop_off : nullptr;
+        v.fit_s = fit_s; v.gamma_fstride = gamma_fstride;
         return v;
     }
     GView gview(int i, const float* dout) const
@@ -215,6 +223,7 @@ struct Ctx {
         g.gamma = t.d.has_bn ? bn + t.d.bn_off : nullptr;
         g.eps = t.d.eps;
         g.drop = (t.drop_off >= 0 && p.dropout_on) ? farena() + t.drop_off : nullptr;
+        g.fit_s = fit_s; g.gamma_fstride = gamma_fstride;
         return g;
     }
     double* bsums_of(int tid) const { return p.t[tid].d.has_bn ? bsums() + p.t[tid].stats_off : nullptr; }      // BN-backward sums of a tensor

@@ -26,6 +26,24 @@ def assign(n_jobs, devices):
     return per
 
 
+def group_jobs(keys, n):
+    """Batches of up to n jobs for one FitBatch each (runner --fits-per-launch): keys[i] is what job i must share with the others of its
+    batch (task, image size, input depth, iterations, K).  A job joins the open batch of its key; a batch closes when it holds n jobs.
+    Returns lists of job indices: increasing inside a batch, the batches ordered by their first job."""
+    if n < 1:
+        raise ValueError("fits per launch %r: at least 1" % (n,))
+    batches, open_of = [], {}
+    for i, k in enumerate(keys):
+        b = open_of.get(k)
+        if b is None:
+            b = open_of[k] = []
+            batches.append(b)
+        b.append(i)
+        if len(b) == n:
+            del open_of[k]
+    return batches
+
+
 def _resolve(fn):
     if callable(fn):
         return fn
@@ -50,7 +68,8 @@ def _worker(device, jobs, fn, run_params, queue):
         for idx, kw in jobs:
             try:
                 res = f(**kw, **run_params)
-                psnr = float(res["psnr"] if isinstance(res, dict) else res)
+                psnr = res["psnr"] if isinstance(res, dict) else res
+                psnr = [float(x) for x in psnr] if isinstance(psnr, (list, tuple)) else float(psnr)      # a batch of fits reports one value per fit
                 queue.put((idx, dev, os.getpid(), psnr, None))
             except Exception as e:                         # one failed fit must not take the other candidates of this device down
                 queue.put((idx, dev, os.getpid(), float("nan"), "%s: %s" % (type(e).__name__, e)))
@@ -112,7 +131,7 @@ def run_jobs(jobs, devices, fn, run_params=None, start_method="spawn", poll_seco
             d = devices[i % len(devices)]
             dropped.append((i, jobs[i], "worker on %s died (exit code %s)" % (d, died.get(d, procs[d].exitcode)))); continue
         _, dev, pid, psnr, err = got[i]
-        if err is not None or math.isnan(psnr):
+        if err is not None or (not isinstance(psnr, list) and math.isnan(psnr)):
             dropped.append((i, jobs[i], err or "nan"))
         else:
             results.append((i, jobs[i], psnr))

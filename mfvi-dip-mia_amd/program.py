@@ -106,7 +106,8 @@ class Plan:
         import torch
         if out is None:
             out = torch.empty((n_samples,) + self.out_shape, dtype=torch.float32, device="cuda")
-        assert z.is_contiguous() and z.dtype == torch.float32 and z.numel() == self.in_shape[0] * self.in_shape[1] * self.in_shape[2]
+        n_in = n_samples // self.samples_per_fit if getattr(self, "samples_per_fit", 0) else 1      # fits mode: one input per fit
+        assert z.is_contiguous() and z.dtype == torch.float32 and z.numel() == n_in * self.in_shape[0] * self.in_shape[1] * self.in_shape[2]
         self._check_params(mu, rho)
         L.check(L.lib().mfvi_forward(self.handle, L.ptr(mu), L.ptr(rho), L.ptr(bn), L.ptr(z), seed, step, k0, n_samples,
                                      int(bool(sample_weights)), L.ptr(self.workspace), L.ptr(out), L.stream_ptr()))
@@ -166,6 +167,18 @@ class Plan:
         lib = L.lib()
         return {i: tuple(dec(lib.mfvi_plan_get_tune(self.handle, i, w)) for w in range(3))
                 for i, o in enumerate(self.prog.ops) if o["type"] == L.OP_CONV}
+
+    def set_fits(self, samples_per_fit, param_stride=0, grad_stride=0):
+        """mfvi_plan_set_fits: the samples of a forward / backward call are n_samples / samples_per_fit independent fits, fit j's
+        mu / rho / bn param_stride floats (its gradients grad_stride floats) behind fit j - 1's; z is one input per fit.  0 switches the
+        mode off.  Raises NotImplementedError for what the mode does not serve.  Call autotune() first: tilings do not depend on the mode."""
+        import torch
+        L.check(L.lib().mfvi_plan_set_fits(self.handle, int(samples_per_fit), int(param_stride), int(grad_stride)))
+        self.samples_per_fit = int(samples_per_fit)
+        nb = L.lib().mfvi_plan_workspace_bytes(self.handle)
+        if nb > self.workspace_bytes:      # more than one sample per fit: room for the net input once per sample
+            self.workspace_bytes = nb
+            self.workspace = torch.empty(nb, dtype=torch.uint8, device="cuda")
 
     def side_stream(self, enabled):
         """Backward-weight kernels on the plan's side stream (default) or on the caller's stream."""

@@ -501,6 +501,94 @@ def load_config(path, bayes="mfvi", with_devices=False):
     return (cands, rp, devices) if with_devices else (cands, rp)
 
 
+def run_fit_batch(task, jobs, imsize=(256, 256), p_sigma=0.1, num_iter=5000, lr=3e-4, input_depth=16, seed=42, show_every=100, save=True,
+                  save_path="../logs", K=1, factor=4, net_kwargs=None, verbose=False, autotune=True, **unused):
+    """The (image, temp, sigma) jobs of one batch as ONE FitBatch (--fits-per-launch): the loop of run_den_mfvi /
+    run_sr_mfvi for every job at once, every fit with the noise of its own RNG samples.  jobs: dicts with img, temp, sigma (and optionally
+    lr).  Writes batch.npz (hyper-parameters; per fit psnr_gt_sm, nll and kl every show_every iterations, the final reconstruction, dead);
+    save.npz and the PNG artefacts stay with the single-fit runners.  Returns dict(psnr=[per fit, NaN for a dead fit], ...)."""
+    import torch
+    from .fitbatch import FitBatch
+    if task not in ("den", "sr"):
+        raise NotImplementedError("--fits-per-launch serves denoising and super-resolution, not %r" % (task,))
+    F = len(jobs)
+    imgs = [_load_image(j["img"], imsize, seed) for j in jobs]
+    H, W = imgs[0].shape
+    if any(im.shape != (H, W) for im in imgs):
+        raise ValueError("the images of one batch must share their size")
+    gt = np.stack(imgs)
+    if task == "den":      # every job's noise as the single-fit runner draws it (same image and seed: the same noisy image)
+        targets = np.stack([np.clip(im + np.random.default_rng(seed + 1).normal(scale=p_sigma, size=im.shape), 0, 1).astype(np.float32) for im in imgs])
+    else:
+        targets = np.ascontiguousarray(gt[:, ::factor, ::factor])
+    temps, sigmas, lrs = [j["temp"] for j in jobs], [j["sigma"] for j in jobs], [j.get("lr", lr) for j in jobs]
+    fb = FitBatch(H, W, F, task=task, K=K, input_depth=input_depth, temp=temps, sigma=sigmas, lr=lrs, seed=seed, sr_factor=factor,
+                  net_kwargs=net_kwargs, init="shared", autotune=autotune)      # the reference's candidates all start from one seed
+    fb.set_targets(torch.from_numpy(targets))
+    n_it = num_iter + 1                                               # bayesian_optimization.py:1291
+    at, psnrs, nlls, kls = [], [], [], []
+    t0 = time.perf_counter()
+    for i in range(n_it):
+        fb.step()
+        if i % show_every == 0 or i == n_it - 1:
+            nll, kl, _ = fb.losses()
+            at.append(i); psnrs.append(fb.psnr(gt)); nlls.append(nll); kls.append(kl)
+            if verbose:
+                print("iter %6d  psnr_gt_sm %s  (%.1f it/s x %d fits)" % (i, np.array2string(psnrs[-1], precision=2), (i + 1) / (time.perf_counter() - t0), F))
+    dead = fb.dead
+    final = np.where(dead != 0, np.nan, psnrs[-1])
+    run_dir = None
+    if save:
+        run_dir = os.path.join(save_path, "%s_batch" % time.time())
+        os.makedirs(run_dir, exist_ok=False)
+        np.savez(os.path.join(run_dir, "batch.npz"), task=task, temp=np.asarray(temps), sigma=np.asarray(sigmas), lr=np.asarray(lrs),
+                 prior_sigma=np.asarray(fb.prior_sigma), K=np.int64(K), seed=np.int64(seed), num_iter=np.int64(num_iter), iterations=np.asarray(at),
+                 psnr_gt_sm=np.stack(psnrs), nll=np.stack(nlls), kl=np.stack(kls), recon=fb.recon().cpu().numpy(), dead=dead)
+    return dict(psnr=[float(x) for x in final], run_dir=run_dir, seconds=time.perf_counter() - t0, batch=fb, dead=dead)
+
+
+def fit_batch_job(task, jobs, **kw):
+    """One batch of fits in a worker process of the fan-out -> the PSNR of every fit."""
+    return run_fit_batch(task, jobs, **kw)["psnr"]
+
+
+def _run_batches(task, jobs, n, rp, K, devices, verbose=False):
+    """jobs -> batches of up to n (fanout.group_jobs) -> one FitBatch each, here or dealt round-robin to one worker per device.
+    Returns (results [(job index, job, psnr)], dropped [(job index, job, why)], batches)."""
+    from .fanout import group_jobs, run_jobs
+    shapes = {}      # (the size of an image file is known once it is read; every distinct image once)
+    for j in jobs:
+        if isinstance(j["img"], str) and j["img"] not in shapes:
+            shapes[j["img"]] = _load_image(j["img"], rp.get("imsize", (256, 256)), rp.get("seed", 42)).shape
+    key = (task, rp.get("input_depth"), rp.get("num_iter"), K)
+    batches = group_jobs([key + (shapes[j["img"]] if isinstance(j["img"], str) else np.squeeze(j["img"]).shape,) for j in jobs], n)
+    bjobs = [dict(jobs=[jobs[i] for i in b]) for b in batches]
+    rp = {k: v for k, v in rp.items() if k not in ("plot",)}
+    per_batch = {}
+    if devices:
+        res, drop = run_jobs(bjobs, devices, "mfvi_dip_mia_amd.runner:fit_batch_job", dict(rp, task=task, K=K))
+        per_batch = {bi: (y, None) for bi, _, y in res}
+        per_batch.update({bi: (None, why) for bi, _, why in drop})
+    else:
+        for bi, bj in enumerate(bjobs):
+            try:
+                per_batch[bi] = (run_fit_batch(task, bj["jobs"], K=K, verbose=verbose, **rp)["psnr"], None)
+            except (RuntimeError, ValueError) as e:
+                per_batch[bi] = (None, "%s: %s" % (type(e).__name__, e))
+    results, dropped = [], []
+    for bi, b in enumerate(batches):
+        ys, why = per_batch[bi]
+        for pos, i in enumerate(b):
+            if ys is None:
+                dropped.append((i, jobs[i], why))
+            elif np.isnan(ys[pos]):
+                dropped.append((i, jobs[i], "dead fit (non-finite data term)"))
+            else:
+                results.append((i, jobs[i], ys[pos]))
+    results.sort(key=lambda r: r[0]); dropped.sort(key=lambda r: r[0])
+    return results, dropped, batches
+
+
 def fit_job(fn_name, **kw):
     """One independent fit in a worker process of the fan-out: run_<task>_<method>(**kw) -> PSNR (the reference's return value)."""
     return globals()[fn_name](**kw)["psnr"]
@@ -526,7 +614,23 @@ def main(argv=None):
                                                                 "UCE of the run's uncertainty maps (mfvi, mcd, sgld), and of the posterior "
                                                                 "predictive maps with --predict-samples")
     ap.add_argument("--calibration-bins", type=int, default=15)
+    ap.add_argument("--fits-per-launch", type=int, default=0, help="> 0: the independent (image, candidate) fits run in batches of up to N as ONE "
+                                                                   "set of launches per iteration (FitBatch; mfvi denoising / super-resolution); "
+                                                                   "writes batch.npz per batch instead of save.npz per fit")
     a = ap.parse_args(argv)
+    if a.fits_per_launch < 0:
+        ap.error("--fits-per-launch %d: 0 (off) or the number of fits per launch" % a.fits_per_launch)
+    if a.fits_per_launch:      # refused before anything loads the library
+        if a.bayes != "mfvi":
+            ap.error("--fits-per-launch batches mean-field VI fits (--bayes mfvi), not %s" % a.bayes)
+        if a.task not in ("denoising", "super-resolution"):
+            ap.error("--fits-per-launch serves denoising and super-resolution, not %s" % a.task)
+        if a.param_dtype != "f32":
+            ap.error("--fits-per-launch takes float32 parameters (--param-dtype f32)")
+        if a.predict_samples:
+            ap.error("--fits-per-launch does not combine with --predict-samples (FitBatch.to_engine(f).predict serves one fit of a batch)")
+        if a.calibration:
+            ap.error("--fits-per-launch does not combine with --calibration")
     if a.calibration and a.bayes not in CALIBRATION_METHODS:
         ap.error("--calibration needs uncertainty maps (--bayes mfvi, mcd or sgld), not %s" % a.bayes)
     if a.calibration and not 1 <= a.calibration_bins <= L.UCE_MAX_BINS:
@@ -569,12 +673,23 @@ def main(argv=None):
 
         def evaluate(cand_list):
             jb = [dict(zip(keys, c), img=imgs[0]) for c in cand_list]
+            if a.fits_per_launch:      # a round's candidates form batches
+                res, _, _ = _run_batches(short, jb, a.fits_per_launch, rp, a.k, devices)
+                return [(tuple(job[k] for k in keys), y) for _, job, y in res]
             if devices:
                 from .fanout import run_jobs
                 res, _ = run_jobs(jb, devices, "mfvi_dip_mia_amd.runner:fit_job", dict(rp, fn_name=fn_name, K=a.k))
                 return [(tuple(job[k] for k in keys), y) for _, job, y in res]
             return [(c, fn(K=a.k, verbose=False, **j, **rp)["psnr"]) for c, j in zip(cand_list, jb)]
         return _bo.bo(bo_params, evaluate, n_rounds=a.bo_rounds)
+    if a.fits_per_launch:
+        from .fanout import print_table
+        results, dropped, batches = _run_batches(short, jobs, a.fits_per_launch, rp, a.k, devices, verbose=True)
+        print("%d fits in %d batches of up to %d" % (len(jobs), len(batches), a.fits_per_launch))
+        print_table(results, list(BO_KEYS[a.bayes]))
+        for i, job, why in dropped:
+            print("dropped fit %d %s: %s" % (i, {k: v for k, v in job.items() if k != "img"}, why))
+        return results
     if devices:
         # independent fits over the node's GPUs (bayesian_optimization.py:3760-3781, eval_result.py:27-53): no per-step communication,
         # one final gather of (candidate, psnr), NaNs dropped
