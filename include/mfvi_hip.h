@@ -235,6 +235,13 @@ int mfvi_plan_last_kernel(const mfvi_plan* plan, int op, int which);
  * nll_sum (device double) += sum_i nll_i.  dout (optional) = grad_scale * d nll_i / d out_i. */
 int mfvi_gaussian_nll(const float* out, const float* target, int n, int H, int W, int factor,
                       float grad_scale, float* dout, double* nll_sum, void* stream);
+/* gaussian_nll(D(out)[:, :1], D(out)[:, 1:], target) (bayesian_optimization.py:2182-2185, utils/bayesian_utils.py:29-32) with D the
+ * downsampler of mfvi_downsample (models/downsampler.py:6-136) applied to BOTH channels of out[n][2][H][W]; target[H/factor][W/factor].
+ * Accumulation and gradient contract of mfvi_gaussian_nll: nll_sum += sum_i nll_i (mean over the low-resolution pixels);
+ * dout (optional) = grad_scale * d nll_i / d out_i, dense (every element written, fixed summation order).  scratch: n * 2 * (H/factor) *
+ * (W/factor) floats (the low-resolution gradient; needed with dout).  Two launches: filter + NLL + low-resolution gradient, the adjoint. */
+int mfvi_gaussian_nll_filtered(const float* out, const float* target, int n, int H, int W, int factor, const float* taps, int n_taps,
+                               float grad_scale, float* scratch, float* dout, double* nll_sum, void* stream);
 /* mse_loss(radon(out), sino) (bayesian_optimization.py:576, radon/radon.py:49-53): out[n][1][H][W],
  * theta_deg[T], sino[T][W]; scratch: n*T*W floats.  mse_sum += sum_i mse_i; dout = grad_scale * d mse_i/d out_i. */
 /* gaussian_nll_inpainting (utils/bayesian_utils.py:35-39) with the runner's sigmoid on the colour channels
@@ -340,6 +347,18 @@ int mfvi_ssim_sum(const float* a, const float* b, int H, int W, double* ssim_sum
 /* dst[h][w] = src[y*factor][x*factor]: the SR runner's nearest-neighbour downsampler (bayesian_optimization.py:2095-2099) applied to the
  * smoothed / clipped outputs for the low-resolution metrics (:2203, :2207, :2214-2217); h = H / factor, w = W / factor. */
 int mfvi_decimate(const float* src, int H, int W, int factor, float* dst, void* stream);
+/* The anti-aliasing downsampler of models/downsampler.py:6-136 — Downsampler(n_planes, factor, 'lanczos2' | 'lanczos3', phase=0.5,
+ * preserve_size=True): ReplicationPad2d(P) (:55-62) then the stride-`factor` convolution with the normalised 2-D kernel of get_kernel
+ * (:74-136), which is the outer product of its 1-D taps k1 — applied per plane as dst = A_H . src . A_W^T with
+ * A_N[y][clamp(y * factor + i - P, 0, N - 1)] += k1[i], P = (n_taps - factor) / 2.  src [n][C][H][W] -> dst [n][C][H/factor][W/factor];
+ * factor 2, 4 or 8 dividing H and W; taps: HOST pointer to the n_taps <= 48 values of k1 (passed to the kernel by value), n_taps - factor
+ * even; n, C <= 65535.  Used for the low-resolution target, the SR runner's low-resolution metrics (bayesian_optimization.py:2203, :2207,
+ * :2214-2217 with this operator as `downsampler`) and the drop-in module. */
+int mfvi_downsample(const float* src, int n, int C, int H, int W, int factor, const float* taps, int n_taps, float* dst, void* stream);
+/* Its adjoint (what autograd returns for the module's input, models/downsampler.py:66-72): dsrc [n][C][H][W] = A_H^T . ddst . A_W, every
+ * element written, the fold of the replication pad at the borders included.  A gather — no floating-point atomics, a fixed summation order:
+ * bit-identical from call to call. */
+int mfvi_downsample_adjoint(const float* ddst, int n, int C, int H, int W, int factor, const float* taps, int n_taps, float* dsrc, void* stream);
 /* One pass of the runner's per-iteration bookkeeping (bayesian_optimization.py:1374-1396) with no host sync: sample means of
  * out[:,0] and exp(-out[:,1]), EMA (weight w; first = 1 copies), clipped copies for the metrics, ring-buffer slot writes
  * (slot pointers may be NULL).  C = 2 (den/SR) or 1 (CT: no aleatoric channel). */

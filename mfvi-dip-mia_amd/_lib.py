@@ -70,6 +70,9 @@ SIGNATURES = {
     "mfvi_adamw_step_guarded": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _P, _P, _P, _F, _P]),
     "mfvi_step_advance": (_I, [_P, _P, _P, _P]),
     "mfvi_decimate": (_I, [_P, _I, _I, _I, _P, _P]),
+    "mfvi_downsample": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "mfvi_downsample_adjoint": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "mfvi_gaussian_nll_filtered": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _F, _P, _P, _P, _P]),
     "mfvi_elbo_update_bf16": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _F, _F, _F, _F, _F, _F, _F, _I, _U64, _P, _P, _P]),
     "mfvi_bf16_to_f32": (_I, [_P, _I64, _P, _P]),
     "mfvi_f32_to_bf16": (_I, [_P, _I64, _P, _P]),

@@ -27,7 +27,19 @@ INP_NET = dict(nd=(16, 32, 64, 128, 128, 128), nu=(16, 32, 64, 128, 128, 128), n
 class ElboEngine:
     def __init__(self, H, W, task=TASK_DEN, K=1, input_depth=16, temp=1.0, sigma=0.1, lr=1e-3, seed=1, sr_factor=4,
                  theta_deg=None, rank=0, world_size=1, process_group=None, samples_per_launch=None, net_kwargs=None,
-                 autotune=True, param_dtype="f32"):
+                 autotune=True, param_dtype="f32", downsampler="nearest"):
+        # the SR forward operator: "nearest" = out[..., ::f, ::f] (what the reference's MFVI runner uses), "lanczos2" / "lanczos3" = the
+        # anti-aliasing Downsampler of models/downsampler.py; refused before anything touches the library
+        if downsampler != "nearest":
+            from .downsampler import SUPPORT, check_geometry
+            if downsampler not in SUPPORT:
+                raise ValueError("downsampler=%r: 'nearest', 'lanczos2' or 'lanczos3'" % (downsampler,))
+            if task != TASK_SR:
+                raise ValueError("downsampler=%r belongs to the super-resolution data term (task='sr'), not task=%r" % (downsampler, task))
+            if type(self) is not ElboEngine:
+                raise ValueError("downsampler=%r is built for the MFVI engine; the siblings' data terms project with [::f, ::f]" % (downsampler,))
+            check_geometry(downsampler, sr_factor, H, W)
+        self.downsampler = downsampler
         import torch
         self.torch = torch
         self.task, self.K, self.H, self.W = task, int(K), H, W
@@ -76,6 +88,10 @@ class ElboEngine:
         self.upd_scratch = torch.zeros(L.lib().mfvi_elbo_update_scratch_bytes(), dtype=torch.uint8, device=dev)
         self.t_applied = torch.zeros(1, dtype=torch.int32, device=dev)    # CT: optimizer steps actually taken (the NaN guard skips some)
         self.sr_factor = sr_factor
+        if downsampler != "nearest":      # the taps (host, passed by value per launch) and the low-resolution gradient, allocated once
+            from .downsampler import c_taps
+            self._ds_taps, self._ds_ntaps = c_taps(downsampler, sr_factor)
+            self.ds_scratch = torch.empty(self.chunk * 2 * (H // sr_factor) * (W // sr_factor), dtype=torch.float32, device=dev)
         self.theta = None
         if task == TASK_CT:
             th = theta_deg if theta_deg is not None else list(range(0, 180, 4))        # bayesian_optimization.py:545
@@ -214,6 +230,9 @@ class ElboEngine:
         scale = 1.0 / self.K
         if self.task == TASK_DEN:
             L.check(lib.mfvi_gaussian_nll(L.ptr(self.out), L.ptr(self.target), n, self.H, self.W, 1, scale, L.ptr(self.dout), L.ptr(self.acc), sp))
+        elif self.task == TASK_SR and self.downsampler != "nearest":
+            L.check(lib.mfvi_gaussian_nll_filtered(L.ptr(self.out), L.ptr(self.target), n, self.H, self.W, self.sr_factor, self._ds_taps, self._ds_ntaps,
+                                                   scale, L.ptr(self.ds_scratch), L.ptr(self.dout), L.ptr(self.acc), sp))
         elif self.task == TASK_SR:
             L.check(lib.mfvi_gaussian_nll(L.ptr(self.out), L.ptr(self.target), n, self.H, self.W, self.sr_factor, scale, L.ptr(self.dout), L.ptr(self.acc), sp))
         elif self.task == TASK_INP:

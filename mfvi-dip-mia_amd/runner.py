@@ -97,7 +97,7 @@ class _Book(_AsyncBook):
     Column 0 of mse_noisy / psnrs / ssims is the 'corrupted' reference of the task: the noisy image (den), the low-resolution image
     against the [::f, ::f] projection of the output (sr: downsampler(out_avg) / out_lr, :2203-2218), the ground truth (ct)."""
 
-    def __init__(self, eng, num_iter, gt, noisy_or_none, task="den", factor=4):
+    def __init__(self, eng, num_iter, gt, noisy_or_none, task="den", factor=4, downsampler="nearest"):
         import torch
         self.t = torch
         H, W, C = eng.H, eng.W, eng.out.shape[1]
@@ -112,8 +112,23 @@ class _Book(_AsyncBook):
         self.var = torch.zeros((H, W), device=dev); self.ale_mean = torch.zeros((H, W), device=dev)
         if task == "sr":      # img_small_torch = downsampler(img_torch) and the projections of out_avg / out (:2101, :2203, :2207)
             h, w = H // self.f, W // self.f
-            self.gt_lr = self.gt[::self.f, ::self.f].contiguous()
+            self.taps = None
+            if downsampler != "nearest":      # the run's `downsampler` is the Lanczos operator: project with it throughout
+                from .downsampler import c_taps
+                self.taps = c_taps(downsampler, self.f)
+                self.gt_lr = torch.empty((h, w), device=dev)
+                self._project(self.gt, self.gt_lr)
+            else:
+                self.gt_lr = self.gt[::self.f, ::self.f].contiguous()
             self.avg_lr = torch.zeros((h, w), device=dev); self.out_lr_clip = torch.zeros((h, w), device=dev)
+
+    def _project(self, src, dst):
+        """dst = downsampler(src) for one [H][W] map: [::f, ::f] (mfvi_decimate) or the run's Lanczos operator (mfvi_downsample)."""
+        lib, sp, p = L.lib(), L.stream_ptr(), L.ptr
+        if self.taps is None:
+            L.check(lib.mfvi_decimate(p(src), self.H, self.W, self.f, p(dst), sp))
+        else:
+            L.check(lib.mfvi_downsample(p(src), 1, 1, self.H, self.W, self.f, self.taps[0], self.taps[1], p(dst), sp))
 
     def iteration(self, eng, i, n, lr_view=None):
         lib, sp, p = L.lib(), L.stream_ptr(), L.ptr
@@ -125,8 +140,8 @@ class _Book(_AsyncBook):
         avg0 = self.ema[0]
         if self.task == "sr":
             h, w = self.gt_lr.shape
-            L.check(lib.mfvi_decimate(p(avg0), self.H, self.W, self.f, p(self.avg_lr), sp))
-            L.check(lib.mfvi_decimate(p(self.out_clip), self.H, self.W, self.f, p(self.out_lr_clip), sp))     # clip and [::f, ::f] commute
+            self._project(avg0, self.avg_lr)
+            self._project(self.out_clip, self.out_lr_clip)      # nearest: clip and [::f, ::f] commute; Lanczos: downsampler(out) of the clipped output
             L.check(lib.mfvi_sq_err_sum(p(self.avg_lr), p(self.gt_lr), h * w, p(m[0:]), sp))         # mse(downsampler(out_avg)[:, :1], img_small)  :2203
             L.check(lib.mfvi_sq_err_sum(p(self.gt_lr), p(self.out_lr_clip), h * w, p(m[2:]), sp))    # psnr_lr                                       :2214
             L.check(lib.mfvi_ssim_sum(p(self.gt_lr), p(self.out_lr_clip), h, w, p(m[5:]), sp))       # ssim_lr                                       :2217
@@ -220,6 +235,19 @@ def _make_engine(method, H, W, task, K, input_depth, temp, sigma, lr, seed, net_
     return SiblingEngine(H, W, method=method, task=task, K=K, input_depth=input_depth, lr=lr, seed=seed, net_kwargs=net_kwargs, **sib, **kw)
 
 
+def _check_downsampler(task, method, downsampler, factor=4):
+    """The SR forward operator of a run: 'nearest' everywhere; 'lanczos2' / 'lanczos3' for run_sr_mfvi."""
+    if downsampler == "nearest":
+        return
+    from .downsampler import SUPPORT, check_geometry
+    if downsampler not in SUPPORT:
+        raise ValueError("downsampler=%r: 'nearest', 'lanczos2' or 'lanczos3'" % (downsampler,))
+    if task != "sr" or method != "mfvi":
+        raise ValueError("downsampler=%r is built for the MFVI super-resolution runner (run_sr_mfvi), not task %r / method %r"
+                         % (downsampler, task, method))
+    check_geometry(downsampler, factor)
+
+
 def _check_predict(method, predict_samples):
     if predict_samples and method not in PREDICT_METHODS:
         raise ValueError("predict_samples=%d: posterior predictive sampling needs a posterior to draw from (mfvi, mcd), not %r"
@@ -268,8 +296,9 @@ def _predict(eng, n, gt, run_dir, drop_ale=False, calibration_bins=0):
 
 def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, seed, show_every, plot, save, save_path, K, factor=4,
          theta_step=4.0, verbose=False, net_kwargs=None, method="mfvi", weight_decay=0.0, dropout_p=0.3, gamma=0.996, param_dtype="f32", predict_samples=0,
-         calibration=False, calibration_bins=15, **unused):
+         calibration=False, calibration_bins=15, downsampler="nearest", **unused):
     import torch
+    _check_downsampler(task, method, downsampler, factor)
     _check_predict(method, predict_samples)
     _check_calibration(method, calibration, calibration_bins)
     sib = dict(weight_decay=weight_decay, dropout_p=dropout_p, gamma=gamma)
@@ -282,7 +311,7 @@ def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, see
                                                                           "sgld": dict(gamma=gamma, weight_decay=weight_decay)}[method]
             for key, val in dict(task=task, method=method, img=img if not isinstance(img, np.ndarray) else "<array>", imsize=imsize, p_sigma=p_sigma,
                                  num_iter=num_iter, lr=lr, input_depth=input_depth, seed=seed, show_every=show_every,
-                                 K=K, save_path=save_path, **hyper).items():
+                                 K=K, save_path=save_path, **(dict(downsampler=downsampler) if task == "sr" else {}), **hyper).items():
                 print(key, "=", val, file=f)
     img_np = _load_image(img, imsize, seed)
     H, W = img_np.shape
@@ -295,9 +324,15 @@ def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, see
         target = noisy
         eng = _make_engine(method, H, W, "den", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, param_dtype=param_dtype)
     elif task == "sr":
-        target = np.ascontiguousarray(img_np[::factor, ::factor])    # nearest /factor decimation (:2095-2099)
         noisy = None
-        eng = _make_engine(method, H, W, "sr", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, sr_factor=factor, param_dtype=param_dtype)
+        if downsampler != "nearest":      # img_small = downsampler(img_hr) with the run's operator (models/downsampler.py)
+            from .downsampler import downsample
+            eng = _make_engine(method, H, W, "sr", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, sr_factor=factor, param_dtype=param_dtype,
+                               downsampler=downsampler)
+            target = downsample(torch.from_numpy(img_np).cuda(), downsampler, factor).cpu().numpy()
+        else:
+            target = np.ascontiguousarray(img_np[::factor, ::factor])    # nearest /factor decimation (:2095-2099)
+            eng = _make_engine(method, H, W, "sr", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, sr_factor=factor, param_dtype=param_dtype)
         extra["img_lr"] = target
     else:
         theta = np.arange(0, 180.0, theta_step, dtype=np.float32)     # :545
@@ -308,7 +343,7 @@ def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, see
         target = sino
         extra["img_radon"] = sino.cpu().numpy()[None, None]
     eng.set_target(torch.from_numpy(target) if isinstance(target, np.ndarray) else target)
-    book = _Book(eng, num_iter, img_np, noisy, task=task, factor=factor)
+    book = _Book(eng, num_iter, img_np, noisy, task=task, factor=factor, downsampler=downsampler)
     n_snap = num_iter // show_every + 1
     recons = np.zeros((n_snap, 1, H, W)); uncerts_epi = np.zeros((n_snap, 1, H, W)); uncerts_ale = np.zeros((n_snap, 1, H, W))
     t0 = time.perf_counter()
@@ -411,6 +446,7 @@ def run_inp_mfvi(img="phantom", mask=None, imsize=(256, 256), num_iter=5000, lr=
     1 = known pixel (the reference ships its masks in data/inpainting/).  save.npz carries the reference's keys for this task
     (img_inpainting, img_mask, mse_corrupted, mse_gt, recons, uncerts, uncerts_ale, psnrs, ssims)."""
     import torch
+    _check_downsampler("inp", method, unused.get("downsampler", "nearest"))
     _check_predict(method, predict_samples)
     _check_calibration(method, calibration, calibration_bins)
     timestamp = str(time.time())
@@ -511,6 +547,8 @@ def run_fit_batch(task, jobs, imsize=(256, 256), p_sigma=0.1, num_iter=5000, lr=
     from .fitbatch import FitBatch
     if task not in ("den", "sr"):
         raise NotImplementedError("--fits-per-launch serves denoising and super-resolution, not %r" % (task,))
+    if unused.get("downsampler", "nearest") != "nearest":
+        raise NotImplementedError("batched fits project with [::f, ::f] only (downsampler='nearest'), not %r" % (unused["downsampler"],))
     F = len(jobs)
     imgs = [_load_image(j["img"], imsize, seed) for j in jobs]
     H, W = imgs[0].shape
@@ -617,7 +655,16 @@ def main(argv=None):
     ap.add_argument("--fits-per-launch", type=int, default=0, help="> 0: the independent (image, candidate) fits run in batches of up to N as ONE "
                                                                    "set of launches per iteration (FitBatch; mfvi denoising / super-resolution); "
                                                                    "writes batch.npz per batch instead of save.npz per fit")
+    ap.add_argument("--sr-downsampler", default=None, choices=["nearest", "lanczos2", "lanczos3"],
+                    help="super-resolution (mfvi): the forward operator of the data term, the low-resolution target and the low-resolution "
+                         "metrics; nearest = [::f, ::f] (default, or the config's run_params.downsampler), lanczos2 / lanczos3 = the "
+                         "anti-aliasing Downsampler of the reference's models/downsampler.py")
     a = ap.parse_args(argv)
+    if a.sr_downsampler not in (None, "nearest"):      # refused before anything loads the library
+        if a.task != "super-resolution" or a.bayes != "mfvi":
+            ap.error("--sr-downsampler %s belongs to --task super-resolution --bayes mfvi" % a.sr_downsampler)
+        if a.fits_per_launch:
+            ap.error("--sr-downsampler %s does not combine with --fits-per-launch (batched fits project with [::f, ::f])" % a.sr_downsampler)
     if a.fits_per_launch < 0:
         ap.error("--fits-per-launch %d: 0 (off) or the number of fits per launch" % a.fits_per_launch)
     if a.fits_per_launch:      # refused before anything loads the library
@@ -654,6 +701,10 @@ def main(argv=None):
     rp["plot"] = False
     if a.param_dtype != "f32":
         rp["param_dtype"] = a.param_dtype
+    if a.sr_downsampler is not None:
+        rp["downsampler"] = a.sr_downsampler
+    if rp.get("downsampler", "nearest") != "nearest" and a.fits_per_launch:
+        ap.error("run_params.downsampler=%s does not combine with --fits-per-launch (batched fits project with [::f, ::f])" % rp["downsampler"])
     if a.predict_samples:
         rp["predict_samples"] = a.predict_samples
     if a.calibration:
