@@ -263,6 +263,12 @@ int mfvi_radon_mse(const float* out, const float* sino, const float* theta_deg, 
                    float grad_scale, float* scratch, float* dout, double* mse_sum, void* stream);
 int mfvi_radon_forward(const float* img, const float* theta_deg, int n, int H, int W, int T, float* sino, void* stream);
 int mfvi_radon_adjoint(const float* dsino, const float* theta_deg, int n, int H, int W, int T, float* dimg, void* stream);
+/* The same operator on n independent square planes, built for the drop-in FastRadonTransform (radon/radon.py:23-55 as the CT runners
+ * call it, bayesian_optimization.py:546, :576): the rows of a ray (project) and the angles of a pixel (backproject) are split over the
+ * waves of a block and combined through LDS in a fixed order, so one plane fills the device.  theta_deg[T] in degrees (device memory).
+ * Bit-identical from call to call.  Null pointers, n < 1 or > 65535, S or T < 1 or > 32768: -1 and mfvi_last_error(). */
+int mfvi_radon_project(const float* img, const float* theta_deg, int n, int S, int T, float* sino, void* stream);       /* img[n][S][S] -> sino[n][T][S] */
+int mfvi_radon_backproject(const float* dsino, const float* theta_deg, int n, int S, int T, float* dimg, void* stream); /* exact-neighbourhood transpose */
 
 /* ---- KL (VIModule._kl / MeanFieldVI.kl: BayTorch/modules/module.py:64-80, freq_to_bayes.py:43-48) ------- */
 /* kl_out (device double, overwritten) = sum_j log(s_j/s0) + (s0^2 + (mu_j-m0)^2)/(2 s_j^2) - 1/2 */

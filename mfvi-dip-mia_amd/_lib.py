@@ -61,6 +61,8 @@ SIGNATURES = {
     "mfvi_radon_mse": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
     "mfvi_radon_forward": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "mfvi_radon_adjoint": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "mfvi_radon_project": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "mfvi_radon_backproject": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "mfvi_kl": (_I, [_P, _P, _I64, _F, _F, _P, _P]),
     "mfvi_kl_backward": (_I, [_P, _P, _I64, _F, _F, _F, _P, _P, _P]),
     "mfvi_adam_step": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _I, _P]),
