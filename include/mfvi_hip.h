@@ -459,6 +459,17 @@ int mfvi_elbo_update_fits(float* params, float* grads, float* m, float* v, int64
  * C = 1 or 2) and ema[f] = first ? mean : ema[f] * weight + mean * (1 - weight); ema [n_fits][C][H][W]. */
 int mfvi_ema_fits(const float* out, int n_fits, int S, int C, int H, int W, float* ema, float weight, int first, void* stream);
 
+/* mfvi_radon_mse per fit on the plane kernels: out / dout [n_fits * S_per_fit][1][S][S], fit f against the sinogram
+ * sinos + f * sino_stride ([T][S]); mse[f] (device doubles) += sum over the fit's samples of mean((R out_k - sino_f)^2),
+ * dout_k = grad_scale * d mse_k / d out_k; dout may be NULL (loss only, nothing else is written but scratch).  Three launches whatever
+ * n_fits is: mfvi_radon_project's row loop with a residual epilogue (one fp64 partial per block, no atomics), one block per fit that adds
+ * the fit's partials in a fixed order, mfvi_radon_backproject of the residual planes.  Bit-identical from call to call.  scratch:
+ * mfvi_radon_mse_fits_scratch_bytes(...) bytes, 8-byte aligned.  Null pointers, n_fits * S_per_fit outside 1..65535, S or T outside
+ * 1..32768, sino_stride < T * S: -1 and mfvi_last_error(), before any launch (the size query returns -1). */
+int64_t mfvi_radon_mse_fits_scratch_bytes(int n_fits, int S_per_fit, int S, int T);
+int mfvi_radon_mse_fits(const float* out, const float* sinos, int64_t sino_stride, const float* theta_deg, int n_fits, int S_per_fit, int S, int T,
+                        float grad_scale, void* scratch, float* dout, double* mse, void* stream);
+
 const char* mfvi_last_error(void);
 int mfvi_abi_version(void);
 

@@ -106,6 +106,8 @@ SIGNATURES = {
     "mfvi_elbo_update_fits_scratch_bytes": (_I64, [_I]),
     "mfvi_elbo_update_fits": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _F, _F, _F, _I, _P, _P, _P, _P, _P]),
     "mfvi_ema_fits": (_I, [_P, _I, _I, _I, _I, _I, _P, _F, _I, _P]),
+    "mfvi_radon_mse_fits_scratch_bytes": (_I64, [_I, _I, _I, _I]),
+    "mfvi_radon_mse_fits": (_I, [_P, _P, _I64, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
     "mfvi_last_error": (C.c_char_p, []),
     "mfvi_abi_version": (_I, []),
 }

@@ -8,7 +8,7 @@ from . import runner
 from .nets import Concat, get_net, skip
 
 __all__ = ["build", "FitBatch", "Plan", "Program", "skip_program", "_lib", "engine", "sharding", "runner", "Concat", "get_net", "skip", "MeanFieldVI", "FusedNet", "Conv2dRT", "Conv2dLRT",
-           "gaussian_nll", "gaussian_nll_inpainting", "uncert_regression_gal", "uceloss", "Downsampler", "lanczos_taps", "FastRadonTransform"]
+           "gaussian_nll", "gaussian_nll_inpainting", "uncert_regression_gal", "uceloss", "Downsampler", "lanczos_taps", "FastRadonTransform", "CtVolume"]
 
 
 def __getattr__(name):          # bayes.py needs torch.nn at import: keep `import mfvi_dip_mia_amd` light
@@ -24,4 +24,7 @@ def __getattr__(name):          # bayes.py needs torch.nn at import: keep `impor
     if name == "FastRadonTransform":
         from . import radon
         return radon.FastRadonTransform
+    if name == "CtVolume":
+        from .ctvolume import CtVolume
+        return CtVolume
     raise AttributeError(name)

@@ -627,6 +627,72 @@ def _run_batches(task, jobs, n, rp, K, devices, verbose=False):
     return results, dropped, batches
 
 
+def parse_ct_volume(spec):
+    """--ct-volume: 'phantom:D' -> ("phantom", D), a .npy path -> ("npy", path); anything else is a ValueError (no file is touched)."""
+    if isinstance(spec, str) and spec.startswith("phantom:"):
+        try:
+            D = int(spec[len("phantom:"):])
+        except ValueError:
+            D = 0
+        if D < 1:
+            raise ValueError("--ct-volume %s: phantom:D with D >= 1 slices" % spec)
+        return "phantom", D
+    if isinstance(spec, str) and spec.endswith(".npy"):
+        return "npy", spec
+    raise ValueError("--ct-volume %s: a .npy file holding [D, S, S], or phantom:D" % (spec,))
+
+
+def _load_volume(volume, imsize, seed):
+    """[D, S, S] float32 from an array, a .npy path or 'phantom:D' (the package's phantom at seeds seed .. seed + D - 1)."""
+    if isinstance(volume, np.ndarray):
+        v = volume.astype(np.float32)
+    else:
+        kind, what = parse_ct_volume(volume)
+        v = np.stack([phantom(imsize[0], imsize[1], seed + d) for d in range(what)]) if kind == "phantom" else np.load(what).astype(np.float32)
+    if v.ndim != 3 or v.shape[1] != v.shape[2]:
+        raise ValueError("expected a stack of square slices [D, S, S], got shape %s" % (v.shape,))
+    return np.ascontiguousarray(v)
+
+
+def run_ct_volume(volume, temp, sigma, slices_per_launch=None, imsize=(256, 256), num_iter=5000, lr=3e-4, input_depth=16, seed=42, show_every=100,
+                  save=True, save_path="../logs", K=1, theta_step=4.0, net_kwargs=None, verbose=False, autotune=True, **unused):
+    """The loop of run_ct_mfvi (bayesian_optimization.py:442-648) for every slice of a stack at once, as ONE CtVolume (--ct-volume; DESIGN.md
+    section 16).  volume: [D, S, S] array, .npy path or 'phantom:D'; temp / sigma / lr: scalars or one value per slice.  Writes volume.npz
+    (angles, sinograms, hyper-parameters; per slice psnr_gt_sm, nll and kl every show_every iterations, the reconstruction, dead); the ring
+    buffers, SSIM curves, save.npz and PNG artefacts stay with the single-fit runner.  Returns dict(psnr=[per slice, NaN for a dead one], ...)."""
+    import torch
+    from .ctvolume import CtVolume
+    gt = _load_volume(volume, imsize, seed)
+    D, S = gt.shape[0], gt.shape[1]
+    theta = np.arange(0, 180.0, theta_step, dtype=np.float32)         # :545
+    vol = CtVolume(S, D, slices_per_launch=slices_per_launch, K=K, input_depth=input_depth, temp=temp, sigma=sigma, lr=lr, theta_deg=theta.tolist(),
+                   seed=seed, net_kwargs=net_kwargs, autotune=autotune)
+    vol.set_volume(torch.from_numpy(gt))                              # img_radon = forward_radon(img_torch) (:547)
+    n_it = num_iter + 1                                               # as the single-fit runners count
+    at, psnrs, nlls, kls = [], [], [], []
+    t0 = time.perf_counter()
+    for i in range(n_it):
+        vol.step()
+        if i % show_every == 0 or i == n_it - 1:
+            nll, kl, _ = vol.losses()
+            at.append(i); psnrs.append(vol.psnr(gt)); nlls.append(nll); kls.append(kl)
+            if verbose:
+                print("iter %6d  psnr_gt_sm %s  (%.1f it/s x %d slices)" % (i, np.array2string(psnrs[-1], precision=2), (i + 1) / (time.perf_counter() - t0), D))
+    dead = vol.dead
+    final = np.where(dead != 0, np.nan, psnrs[-1])
+    run_dir = None
+    if save:
+        run_dir = os.path.join(save_path, "%s_volume" % time.time())
+        os.makedirs(run_dir, exist_ok=False)
+        np.savez(os.path.join(run_dir, "volume.npz"), theta=theta, sinograms=vol.sinos.cpu().numpy(), temp=np.asarray(vol.temps), sigma=np.asarray(vol.sigmas),
+                 lr=np.asarray(vol.lrs), prior_sigma=np.asarray(vol.prior_sigma), K=np.int64(K), seed=np.int64(seed), num_iter=np.int64(num_iter),
+                 slices_per_launch=np.int64(vol.F), iterations=np.asarray(at), psnr_gt_sm=np.stack(psnrs), nll=np.stack(nlls), kl=np.stack(kls),
+                 recon=vol.recon().cpu().numpy(), dead=dead)
+    live = final[dead == 0]
+    return dict(psnr=[float(x) for x in final], mean_psnr=float(live.mean()) if live.size else float("nan"), run_dir=run_dir,
+                seconds=time.perf_counter() - t0, volume=vol, dead=dead)
+
+
 def fit_job(fn_name, **kw):
     """One independent fit in a worker process of the fan-out: run_<task>_<method>(**kw) -> PSNR (the reference's return value)."""
     return globals()[fn_name](**kw)["psnr"]
@@ -655,6 +721,10 @@ def main(argv=None):
     ap.add_argument("--fits-per-launch", type=int, default=0, help="> 0: the independent (image, candidate) fits run in batches of up to N as ONE "
                                                                    "set of launches per iteration (FitBatch; mfvi denoising / super-resolution); "
                                                                    "writes batch.npz per batch instead of save.npz per fit")
+    ap.add_argument("--ct-volume", default=None, help="--task ct --bayes mfvi: a .npy file holding a stack [D, S, S], or phantom:D; the slices are "
+                                                         "fitted as ONE CtVolume per candidate (one set of launches per group of slices) and "
+                                                         "volume.npz is written instead of save.npz per slice")
+    ap.add_argument("--slices-per-launch", type=int, default=None, help="with --ct-volume: slices per set of launches (default: all of them)")
     ap.add_argument("--sr-downsampler", default=None, choices=["nearest", "lanczos2", "lanczos3"],
                     help="super-resolution (mfvi): the forward operator of the data term, the low-resolution target and the low-resolution "
                          "metrics; nearest = [::f, ::f] (default, or the config's run_params.downsampler), lanczos2 / lanczos3 = the "
@@ -665,6 +735,21 @@ def main(argv=None):
             ap.error("--sr-downsampler %s belongs to --task super-resolution --bayes mfvi" % a.sr_downsampler)
         if a.fits_per_launch:
             ap.error("--sr-downsampler %s does not combine with --fits-per-launch (batched fits project with [::f, ::f])" % a.sr_downsampler)
+    if a.slices_per_launch is not None and (a.ct_volume is None or a.slices_per_launch < 1):
+        ap.error("--slices-per-launch %d: at least 1, and only with --ct-volume" % a.slices_per_launch)
+    if a.ct_volume is not None:      # refused before anything loads the library
+        try:
+            parse_ct_volume(a.ct_volume)
+        except ValueError as e:
+            ap.error(str(e))
+        if a.task != "ct" or a.bayes != "mfvi":
+            ap.error("--ct-volume fits a CT stack by mean-field VI (--task ct --bayes mfvi), not --task %s --bayes %s" % (a.task, a.bayes))
+        if a.param_dtype != "f32":
+            ap.error("--ct-volume takes float32 parameters (--param-dtype f32)")
+        for flag, on in (("--fits-per-launch", a.fits_per_launch), ("--predict-samples", a.predict_samples), ("--calibration", a.calibration),
+                         ("--bo-rounds", a.bo_rounds)):
+            if on:
+                ap.error("--ct-volume does not combine with %s (CtVolume.to_engine(d) serves one slice of a volume)" % flag)
     if a.fits_per_launch < 0:
         ap.error("--fits-per-launch %d: 0 (off) or the number of fits per launch" % a.fits_per_launch)
     if a.fits_per_launch:      # refused before anything loads the library
@@ -710,6 +795,17 @@ def main(argv=None):
     if a.calibration:
         rp["calibration"] = True
         rp["calibration_bins"] = a.calibration_bins
+    if a.ct_volume is not None:      # one volume fit per candidate of the config
+        from .fanout import print_table
+        vrp = {k: v for k, v in rp.items() if k not in ("img", "plot", "p_sigma")}
+        results = []
+        for i, cand in enumerate(cands):
+            r = run_ct_volume(a.ct_volume, slices_per_launch=a.slices_per_launch, K=a.k, verbose=True, **cand, **vrp)
+            print("%s -> mean PSNR %.3f dB over %d live of %d slices in %.1f s (%s)" % (" ".join("%s %.3e" % kv for kv in cand.items()), r["mean_psnr"],
+                                                                                      int((r["dead"] == 0).sum()), len(r["dead"]), r["seconds"], r["run_dir"]))
+            results.append((i, cand, r["mean_psnr"]))
+        print_table(results, list(BO_KEYS[a.bayes]))
+        return results
     imgs = a.img.split(",") if a.img else [rp.pop("img", "phantom")]
     rp.pop("img", None)
     jobs = [dict(cand, img=im) for im in imgs for cand in cands]
