@@ -162,7 +162,9 @@ int mfvi_plan_set_param_dtype(mfvi_plan* plan, int dtype);
  * global sample index k0 + i (the RNG is unchanged).  mu / rho / bn point at fit 0, fit j's blocks lie j * param_stride floats further on
  * (one flat row [MU | RHO | BN] per fit works with a single stride); dmu / drho / dbn
  * likewise with grad_stride.  z is [n_fits][Cin][H][W], one input per fit; out / dout / dz stay [n_samples][C][H][W].  Every weight gradient is
- * summed over the samples of its fit only, in a fixed order, no atomics.  S = 0 (the default) switches the mode off: one fit, as before.
+ * summed over the samples of its fit only; on the matrix-core kernels in a fixed order, no atomics.  A layer those decline (a map not a
+ * multiple of 4 wide) runs on the generic fp32 kernels with the fit's mu / rho, as in single-fit mode: their weight gradient uses fp32
+ * atomicAdd over samples and tiles in both modes, so a net that reaches them is not bit-reproducible from call to call.  S = 0 (the default) switches the mode off: one fit, as before.
  * S > 1 grows the workspace by one copy of the net input per sample: ask mfvi_plan_workspace_bytes again afterwards.
  * Not served, and refused with MFVI_ERR_FITS_UNSUPPORTED and a message (never run with fit 0's parameters): bf16 parameter storage, plans
  * with local-reparameterisation layers, sample_weights = 0, BatchNorm eval mode and mfvi_plan_bn_update_running, a gradient split, a device
@@ -458,6 +460,23 @@ int mfvi_elbo_update_fits(float* params, float* grads, float* m, float* v, int64
 /* The EMA part of mfvi_bookkeep per fit: sample means of out[:, 0] and exp(-out[:, 1]) over the fit's S samples (out [n_fits * S][C][H][W],
  * C = 1 or 2) and ema[f] = first ? mean : ema[f] * weight + mean * (1 - weight); ema [n_fits][C][H][W]. */
 int mfvi_ema_fits(const float* out, int n_fits, int S, int C, int H, int W, float* ema, float weight, int first, void* stream);
+/* Inpainting per fit.  mfvi_gaussian_nll_inpainting per fit: out / dout [n_fits * S][4][H][W], fit f against
+ * targets + f * target_stride ([3][H][W]) under masks + f * mask_stride ([mask_channels][H][W], mask_channels 1 or 3; mask_stride 0: one
+ * mask for every fit); nll[f] (device doubles) += sum over the fit's S samples; dout may be NULL.  The per-pixel code is
+ * mfvi_gaussian_nll_inpainting's own: dout of a fit is bit-equal to that entry point's. */
+int mfvi_gaussian_nll_inpainting_fits(const float* out, const float* targets, int64_t target_stride, const float* masks, int64_t mask_stride,
+                                      int mask_channels, int n_fits, int S, int H, int W, float grad_scale, float* dout, double* nll, void* stream);
+/* The EMA part of mfvi_bookkeep_inpainting per fit: sample means of sigmoid(out[:, c]), c < 3, and of exp(-out[:, 3]) over the fit's S
+ * samples (out [n_fits * S][4][H][W]); ema[f] = first ? mean : ema[f] * weight + mean * (1 - weight); ema [n_fits][4][H][W]. */
+int mfvi_ema_inpainting_fits(const float* out, int n_fits, int S, int H, int W, float* ema, float weight, int first, void* stream);
+/* acc[f] (device doubles, overwritten) = sum over [3][H][W] of (clip(ema_f, 0, 1) * mask_f - img_f * mask_f)^2 with ema_f = ema + f * ema_stride,
+ * img_f = img + f * img_stride, mask_f = masks + f * mask_stride ([mask_channels][H][W]; stride 0: shared): the squared error behind the
+ * inpainting runner's masked PSNR of the smoothed output.  fp32 per element, fp64 sums; per-block partials in scratch
+ * (n_fits * MFVI_MASKED_SQ_ERR_BLOCKS doubles), then one block per fit adds them in block order: no floating-point atomics, bit-identical
+ * from call to call.  Two launches whatever n_fits is. */
+#define MFVI_MASKED_SQ_ERR_BLOCKS 64
+int mfvi_masked_sq_err_fits(const float* ema, int64_t ema_stride, const float* img, int64_t img_stride, const float* masks, int64_t mask_stride,
+                            int mask_channels, int n_fits, int H, int W, double* acc, void* scratch, void* stream);
 
 /* mfvi_radon_mse per fit on the plane kernels: out / dout [n_fits * S_per_fit][1][S][S], fit f against the sinogram
  * sinos + f * sino_stride ([T][S]); mse[f] (device doubles) += sum over the fit's samples of mean((R out_k - sino_f)^2),

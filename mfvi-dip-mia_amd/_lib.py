@@ -10,6 +10,7 @@ OP_CONV, OP_CONCAT_UP, OP_CONV_LRT = 1, 2, 3
 DOMAIN_EPS, DOMAIN_INPUT, DOMAIN_INIT, DOMAIN_UNIFORM, DOMAIN_SGLD, DOMAIN_DROPOUT, DOMAIN_ROUND, DOMAIN_LRT = 0, 1, 2, 3, 4, 5, 6, 7
 PARAM_F32, PARAM_BF16 = 0, 1
 PRED_RAW, PRED_LOGPREC, PRED_INP, PRED_MEAN_ONLY = 0, 1, 2, 3             # MFVI_PRED_* (posterior predictive statistics)
+MASKED_SQ_ERR_BLOCKS = 64                                                 # MFVI_MASKED_SQ_ERR_BLOCKS (mfvi_masked_sq_err_fits scratch)
 UCE_MAX_BINS = 256                                                        # MFVI_UCE_MAX_BINS (uncertainty calibration)
 
 
@@ -106,6 +107,9 @@ SIGNATURES = {
     "mfvi_elbo_update_fits_scratch_bytes": (_I64, [_I]),
     "mfvi_elbo_update_fits": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _F, _F, _F, _I, _P, _P, _P, _P, _P]),
     "mfvi_ema_fits": (_I, [_P, _I, _I, _I, _I, _I, _P, _F, _I, _P]),
+    "mfvi_gaussian_nll_inpainting_fits": (_I, [_P, _P, _I64, _P, _I64, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "mfvi_ema_inpainting_fits": (_I, [_P, _I, _I, _I, _I, _P, _F, _I, _P]),
+    "mfvi_masked_sq_err_fits": (_I, [_P, _I64, _P, _I64, _P, _I64, _I, _I, _I, _I, _P, _P, _P]),
     "mfvi_radon_mse_fits_scratch_bytes": (_I64, [_I, _I, _I, _I]),
     "mfvi_radon_mse_fits": (_I, [_P, _P, _I64, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
     "mfvi_last_error": (C.c_char_p, []),

@@ -385,18 +385,23 @@ struct OutDesc {               // raw output tensor of a forward op
 
 void set_error(const char* fmt, ...);
 
+// Fit geometry of the generic kernels (fits mode, mfvi_plan_set_fits): sample k belongs to fit k / fit_s, reads mu / rho pstride floats per fit
+// further on and accumulates into dmu / drho gstride floats per fit further on.  fit_s = 0: one fit, every offset is 0
+struct FitGeom { int fit_s = 0; long long pstride = 0, gstride = 0; };
+__device__ __forceinline__ long long fit_param_off(const FitGeom& f, int k) { return f.fit_s ? (long long)(k / f.fit_s) * f.pstride : 0; }
+__device__ __forceinline__ long long fit_grad_off(const FitGeom& f, int k) { return f.fit_s ? (long long)(k / f.fit_s) * f.gstride : 0; }
 int launch_conv_fwd(const TView& in, const ConvGeom& g, const float* mu, const float* rho, RngKey key, int sample_weights,
-                    OutDesc out, int n_samples, hipStream_t st);
+                    OutDesc out, int n_samples, hipStream_t st, FitGeom fit = FitGeom{});
 int launch_conv_bwd_data(const GView& gy, const ConvGeom& g, const float* mu, const float* rho, RngKey key, int sample_weights,
-                         float* dxp, long long dxp_sstride, int n_samples, hipStream_t st);
+                         float* dxp, long long dxp_sstride, int n_samples, hipStream_t st, FitGeom fit = FitGeom{});
 int launch_conv_bwd_weight(const TView& in, const GView& gy, const ConvGeom& g, const float* rho, RngKey key, int sample_weights,
-                           float* dmu, float* drho, int n_samples, hipStream_t st);
+                           float* dmu, float* drho, int n_samples, hipStream_t st, FitGeom fit = FitGeom{});
 // ---- dispatch of one convolution (conv_dispatch.hip): the ONE path from the plan (passes and autotuner alike) to a kernel family ----
 // Weights as the kernels want them: the slab for the matrix-core families (w: sample 0, sample k at w + k*wstride — the buffer filled by
 // launch_sample_weights, or mu with stride 0) and mu / rho / key for the generic kernels, which draw eps themselves (mu == nullptr: bf16
 // parameters, which reach those only through the plan's float32 expansion of the layers outside the sampling table).
 struct ConvWeights { const float* w; long long wstride; const float* mu; const float* rho; RngKey key; int sample_weights;
-                     int fits = 0; };      // fits mode: mu == rho == nullptr (the generic kernels read ONE mu / rho: a layer that lands there is an error)
+                     FitGeom fit = FitGeom{}; };      // fits mode: mu / rho are fit 0's, the generic kernels find a sample's fit through `fit`
 // fuse (1x1 / 3x3 stride-1 layers whose input has no other consumer): the epilogue does the fold of that input tensor itself — multiplies by
 // LeakyReLU'(view(x)), accumulates the BN-backward sums of x (bsums, nullptr when x carries no BatchNorm) and writes ga directly; no
 // padded-gradient scratch, no finalize_dx launch.

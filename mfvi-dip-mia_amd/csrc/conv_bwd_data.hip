@@ -25,7 +25,7 @@ template <int KS, int STRIDE>
 __global__ __launch_bounds__(256) void conv_bwd_data_kernel(GView gy, ConvGeom g, const float* __restrict__ mu,
                                                             const float* __restrict__ rho, RngKey key,
                                                             int sample_weights, float* __restrict__ dxp,
-                                                            long long dxp_sstride, int tiles_x)
+                                                            long long dxp_sstride, int tiles_x, FitGeom fit)
 {
     key = key_now(key);
     using Cfg = BwdCfg<KS, STRIDE>;
@@ -43,6 +43,7 @@ __global__ __launch_bounds__(256) void conv_bwd_data_kernel(GView gy, ConvGeom g
     const int Cin = g.Cin, Cout = g.Cout, Ho = g.Ho, Wo = g.Wo;
     const int Hp = g.H + 2 * P, Wp = g.W + 2 * P;
     const int cit = min(CIT, Cin - ci0);
+    { const long long fo = fit_param_off(fit, k); mu += fo; rho += fo; }      // the sample's fit: uniform per block
 
     RngKey kw = key; kw.sample += (uint32_t)k; kw.stream = ((uint32_t)DOMAIN_EPS << 24) | (uint32_t)(2 * g.layer_id);
 
@@ -153,7 +154,7 @@ __global__ __launch_bounds__(256) void conv_bwd_data_kernel(GView gy, ConvGeom g
 }  // namespace
 
 int launch_conv_bwd_data(const GView& gy, const ConvGeom& g, const float* mu, const float* rho, RngKey key, int sample_weights,
-                         float* dxp, long long dxp_sstride, int n_samples, hipStream_t st)
+                         float* dxp, long long dxp_sstride, int n_samples, hipStream_t st, FitGeom fit)
 {
     if (g.Cout > MFVI_MAX_C) { set_error("conv_bwd_data: Cout %d > %d", g.Cout, MFVI_MAX_C); return -1; }
     const int P = g.ks / 2, Hp = g.H + 2 * P, Wp = g.W + 2 * P;
@@ -163,7 +164,7 @@ int launch_conv_bwd_data(const GView& gy, const ConvGeom& g, const float* mu, co
         const int tiles_x = (Wp + Cfg::TW - 1) / Cfg::TW, tiles_y = (Hp + Cfg::TH - 1) / Cfg::TH;                        \
         dim3 grid(tiles_x * tiles_y, (g.Cin + Cfg::CIT - 1) / Cfg::CIT, n_samples);                                      \
         hipLaunchKernelGGL((conv_bwd_data_kernel<KS_, S_>), grid, dim3(256), 0, st, gy, g, mu, rho, key, sample_weights, \
-                           dxp, dxp_sstride, tiles_x);                                                                   \
+                           dxp, dxp_sstride, tiles_x, fit);                                                              \
     }
     if (g.ks == 3 && g.stride == 1) LAUNCH(3, 1)
     else if (g.ks == 3 && g.stride == 2) LAUNCH(3, 2)

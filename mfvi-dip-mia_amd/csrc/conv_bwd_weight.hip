@@ -31,7 +31,7 @@ __global__ __launch_bounds__(256) void conv_bwd_weight_kernel(TView in, GView gy
                                                               const float* __restrict__ rho, RngKey key,
                                                               int sample_weights, float* __restrict__ dmu,
                                                               float* __restrict__ drho, int tiles_x, int n_tiles,
-                                                              int tiles_per_block, int ci_tiles)
+                                                              int tiles_per_block, int ci_tiles, FitGeom fit)
 {
     key = key_now(key);
     using Cfg = BwwCfg<KS, STRIDE>;
@@ -49,6 +49,8 @@ __global__ __launch_bounds__(256) void conv_bwd_weight_kernel(TView in, GView gy
     const int co0 = (blockIdx.y / ci_tiles) * COT, ci0 = (blockIdx.y % ci_tiles) * CIT;
     const int Cin = g.Cin, Cout = g.Cout, H = g.H, W = g.W, Ho = g.Ho, Wo = g.Wo;
     const bool do_bias = (ci0 == 0) && (g.b_off >= 0);
+    // the sample's fit (uniform per block): its rho for the sigmoid factor, its rows of d mu / d rho for the atomics
+    { rho += fit_param_off(fit, k); const long long go = fit_grad_off(fit, k); dmu += go; drho += go; }
 
     if (t < CIT) { s_chx[t] = chan_fwd(in, k, min(ci0 + t, Cin - 1)); }
     if (t >= 64 && t < 64 + COT) { s_chg[t - 64] = chan_bwd(gy, k, min(co0 + t - 64, Cout - 1)); }
@@ -159,7 +161,7 @@ __global__ __launch_bounds__(256) void conv_bwd_weight_kernel(TView in, GView gy
 }  // namespace
 
 int launch_conv_bwd_weight(const TView& in, const GView& gy, const ConvGeom& g, const float* rho, RngKey key, int sample_weights,
-                           float* dmu, float* drho, int n_samples, hipStream_t st)
+                           float* dmu, float* drho, int n_samples, hipStream_t st, FitGeom fit)
 {
 #define LAUNCH(KS_, S_)                                                                                                   \
     {                                                                                                                     \
@@ -174,7 +176,7 @@ int launch_conv_bwd_weight(const TView& in, const GView& gy, const ConvGeom& g, 
         strips = (n_tiles + tpb - 1) / tpb;                                                                               \
         dim3 grid(strips, co_tiles * ci_tiles, n_samples);                                                                \
         hipLaunchKernelGGL((conv_bwd_weight_kernel<KS_, S_>), grid, dim3(256), 0, st, in, gy, g, rho, key, sample_weights, \
-                           dmu, drho, tiles_x, n_tiles, tpb, ci_tiles);                                                   \
+                           dmu, drho, tiles_x, n_tiles, tpb, ci_tiles, fit);                                              \
     }
     if (g.ks == 3 && g.stride == 1) LAUNCH(3, 1)
     else if (g.ks == 3 && g.stride == 2) LAUNCH(3, 2)

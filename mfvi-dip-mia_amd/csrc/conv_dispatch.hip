@@ -101,8 +101,7 @@ int backward_weight_mfma(Launch& L, const TView& in, const GView& gy, const Conv
 bool to_generic(Launch& L, const ConvGeom& g, const ConvWeights& W, const char* pass, bool generic_fallback, int* rc)
 {
     if (!conv_declined(*rc) || !generic_fallback) return false;
-    if (W.mu) { L.family = FAM_GENERIC; return true; }
-    if (W.fits) { set_error("%s: conv layer %d needs the generic fp32 kernels, which read one mu / rho for all samples: fits mode (mfvi_plan_set_fits) does not serve it", pass, g.layer_id); *rc = MFVI_ERR_FITS_UNSUPPORTED; return false; }
+    if (W.mu) { L.family = FAM_GENERIC; return true; }      // (fits mode too: the kernels find a sample's fit through W.fit)
     set_error("%s: conv layer %d needs the generic fp32 kernels, which bf16 parameters reach only for layers outside the sampling table (use H, W multiples of 4)", pass, g.layer_id);
     *rc = -1; return false;
 }
@@ -112,7 +111,7 @@ bool to_generic(Launch& L, const ConvGeom& g, const ConvWeights& W, const char* 
 int conv_forward(Launch& L, const TView& in, const ConvGeom& g, const ConvWeights& W, OutDesc out, int n_samples, bool generic_fallback)
 {
     int rc = use_mfma() ? forward_mfma(L, in, g, W.w, W.wstride, out, n_samples) : CONV_NOT_SERVED;
-    if (to_generic(L, g, W, "forward", generic_fallback, &rc)) rc = launch_conv_fwd(in, g, W.mu, W.rho, W.key, W.sample_weights, out, n_samples, L.st);
+    if (to_generic(L, g, W, "forward", generic_fallback, &rc)) rc = launch_conv_fwd(in, g, W.mu, W.rho, W.key, W.sample_weights, out, n_samples, L.st, W.fit);
     return rc;
 }
 
@@ -121,7 +120,7 @@ int conv_backward_data(Launch& L, const GView& gy, const ConvGeom& g, const Conv
 {
     int rc = use_mfma() ? backward_data_mfma(L, gy, g, W.w, W.wstride, dxp, dxp_sstride, n_samples, fuse) : CONV_NOT_SERVED;
     if (to_generic(L, g, W, "backward-data", generic_fallback && !fuse, &rc))
-        rc = launch_conv_bwd_data(gy, g, W.mu, W.rho, W.key, W.sample_weights, dxp, dxp_sstride, n_samples, L.st);
+        rc = launch_conv_bwd_data(gy, g, W.mu, W.rho, W.key, W.sample_weights, dxp, dxp_sstride, n_samples, L.st, W.fit);
     return rc;
 }
 
@@ -129,6 +128,6 @@ int conv_backward_weight(Launch& L, const TView& in, const GView& gy, const Conv
                          float* dmu, float* drho, int n_samples, bool generic_fallback)
 {
     int rc = use_mfma() ? backward_weight_mfma(L, in, gy, g, part, strips_used, n_samples) : CONV_NOT_SERVED;
-    if (to_generic(L, g, W, "backward-weight", generic_fallback, &rc)) rc = launch_conv_bwd_weight(in, gy, g, W.rho, W.key, W.sample_weights, dmu, drho, n_samples, L.st);
+    if (to_generic(L, g, W, "backward-weight", generic_fallback, &rc)) rc = launch_conv_bwd_weight(in, gy, g, W.rho, W.key, W.sample_weights, dmu, drho, n_samples, L.st, W.fit);
     return rc;
 }

@@ -29,7 +29,7 @@ struct FwdCfg {
 template <int KS, int STRIDE>
 __global__ __launch_bounds__(256) void conv_fwd_kernel(TView in, ConvGeom g, const float* __restrict__ mu,
                                                        const float* __restrict__ rho, RngKey key, int sample_weights,
-                                                       OutDesc out, int tiles_x)
+                                                       OutDesc out, int tiles_x, FitGeom fit)
 {
     key = key_now(key);
     using Cfg = FwdCfg<KS, STRIDE>;
@@ -47,6 +47,7 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(TView in, ConvGeom g, con
     const int co0 = blockIdx.y * CT;
     const int ox0 = (blockIdx.x % tiles_x) * TW, oy0 = (blockIdx.x / tiles_x) * TH;
     const int H = g.H, W = g.W, Cin = g.Cin, Cout = g.Cout;
+    { const long long fo = fit_param_off(fit, k); mu += fo; rho += fo; }      // the sample's fit: uniform per block
 
     RngKey kw = key; kw.sample += (uint32_t)k; kw.stream = ((uint32_t)DOMAIN_EPS << 24) | (uint32_t)(2 * g.layer_id);
     RngKey kb = kw; kb.stream += 1u;
@@ -182,7 +183,7 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(TView in, ConvGeom g, con
 }  // namespace
 
 int launch_conv_fwd(const TView& in, const ConvGeom& g, const float* mu, const float* rho, RngKey key, int sample_weights,
-                    OutDesc out, int n_samples, hipStream_t st)
+                    OutDesc out, int n_samples, hipStream_t st, FitGeom fit)
 {
     if (g.Cin > MFVI_MAX_C) { set_error("conv_fwd: Cin %d > %d", g.Cin, MFVI_MAX_C); return -1; }
 #define LAUNCH(KS_, S_)                                                                                              \
@@ -191,7 +192,7 @@ int launch_conv_fwd(const TView& in, const ConvGeom& g, const float* mu, const f
         const int tiles_x = (g.Wo + Cfg::TW - 1) / Cfg::TW, tiles_y = (g.Ho + Cfg::TH - 1) / Cfg::TH;                \
         dim3 grid(tiles_x * tiles_y, (g.Cout + Cfg::CT - 1) / Cfg::CT, n_samples);                                   \
         hipLaunchKernelGGL((conv_fwd_kernel<KS_, S_>), grid, dim3(256), 0, st, in, g, mu, rho, key, sample_weights, \
-                           out, tiles_x);                                                                            \
+                           out, tiles_x, fit);                                                                       \
     }
     if (g.ks == 3 && g.stride == 1) LAUNCH(3, 1)
     else if (g.ks == 3 && g.stride == 2) LAUNCH(3, 2)

@@ -1,7 +1,8 @@
 // The element-wise passes of one ELBO iteration for MANY independent fits in one launch each (mfvi_plan_set_fits is
-// the plan side): input perturbation, Gaussian NLL, KL + AdamW, smoothed outputs.  Grid y = fit (or sample); the per-thread bodies are the
+// the plan side): input perturbation, Gaussian NLL, KL + AdamW, smoothed outputs, and for inpainting (section 17) the masked 4-channel NLL,
+// the smoothed sigmoid colours and the masked squared error of the metric.  Grid y = fit (or sample); the per-thread bodies are the
 // single-fit kernels' own (iter_ops.h), so a fit of a batch computes what mfvi_perturb_input / mfvi_gaussian_nll / mfvi_elbo_update /
-// mfvi_bookkeep compute for it alone.  The reference runs one process per fit instead (bayesian_optimization.py:3760-3775).
+// mfvi_bookkeep / mfvi_gaussian_nll_inpainting / mfvi_bookkeep_inpainting compute for it alone.  The reference runs one process per fit instead (bayesian_optimization.py:3760-3775).
 #include "common.h"
 #include "iter_ops.h"
 #include "../../include/mfvi_hip.h"
@@ -72,6 +73,57 @@ __global__ __launch_bounds__(256) void ema_fits_kernel(const float* __restrict__
     }
 }
 
+// ---- inpainting (4 outputs: 3 colours through the sigmoid + one log-precision channel, a mask per fit) ----
+__global__ __launch_bounds__(256) void gaussian_nll_inp_fits_kernel(const float* __restrict__ out, const float* __restrict__ targets, long long target_stride,
+                                                                    const float* __restrict__ masks, long long mask_stride, int mask_channels, int S,
+                                                                    long long HW, float grad_scale, float* __restrict__ dout, double* __restrict__ nll)
+{
+    __shared__ double s_red[8];
+    const int k = blockIdx.y, fit = k / S;
+    const double v = gnll_inp_sample(out + (long long)k * 4 * HW, targets + (long long)fit * target_stride, masks + (long long)fit * mask_stride, mask_channels, HW,
+                                     grad_scale, dout ? dout + (long long)k * 4 * HW : nullptr);
+    block_atomic_add(v, nll + fit, s_red);
+}
+
+__global__ __launch_bounds__(256) void ema_inp_fits_kernel(const float* __restrict__ out, int S, long long HW, float* __restrict__ ema, float w, int first)
+{
+    const float* __restrict__ o = out + (long long)blockIdx.y * S * 4 * HW;
+    float* __restrict__ e = ema + (long long)blockIdx.y * 4 * HW;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < HW; i += (long long)gridDim.x * 256) {
+        float a, m[3], e0[3];
+        sample_means_ema_inp(o, S, HW, i, e, w, first, m, e0, a);
+    }
+}
+
+// sum over [3][HW] of (clip(ema, 0, 1) * mask - img * mask)^2 of fit blockIdx.y: this block's partial, in a fixed order
+__global__ __launch_bounds__(256) void masked_sq_err_fits_kernel(const float* __restrict__ ema, long long ema_stride, const float* __restrict__ img, long long img_stride,
+                                                                 const float* __restrict__ masks, long long mask_stride, int mask_channels, long long HW,
+                                                                 double* __restrict__ partial)
+{
+    __shared__ double s_red[8];
+    const int fit = blockIdx.y;
+    const float* __restrict__ e = ema + (long long)fit * ema_stride;
+    const float* __restrict__ g = img + (long long)fit * img_stride;
+    const float* __restrict__ mk = masks + (long long)fit * mask_stride;
+    double acc = 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < 3 * HW; i += (long long)gridDim.x * 256) {
+        const float m = mk[mask_channels == 3 ? i : i % HW];
+        const float d = fminf(fmaxf(e[i], 0.f), 1.f) * m - g[i] * m;
+        acc += (double)d * (double)d;
+    }
+    const double tot = block_sum_d(acc, s_red);
+    if (threadIdx.x == 0) partial[(long long)fit * MFVI_MASKED_SQ_ERR_BLOCKS + blockIdx.x] = tot;
+}
+// one block per fit: its partials in block order
+__global__ __launch_bounds__(64) void masked_sq_err_fits_finish_kernel(const double* __restrict__ partial, int n_blocks, double* __restrict__ acc)
+{
+    if (threadIdx.x == 0) {
+        double t = 0;
+        for (int b = 0; b < n_blocks; ++b) t += partial[(long long)blockIdx.x * MFVI_MASKED_SQ_ERR_BLOCKS + b];
+        acc[blockIdx.x] = t;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -125,6 +177,42 @@ int mfvi_ema_fits(const float* out, int n_fits, int S, int C, int H, int W, floa
     if (!out || !ema || n_fits < 1 || n_fits > 65535 || S < 1 || C < 1 || C > 2 || H < 1 || W < 1) { set_error("ema_fits: bad arguments"); return -1; }
     const long long HW = (long long)H * W;
     hipLaunchKernelGGL(ema_fits_kernel, dim3(nblocks(HW, 256), n_fits), dim3(256), 0, (hipStream_t)stream, out, S, C, HW, ema, weight, first);
+    return (int)hipGetLastError();
+}
+
+int mfvi_gaussian_nll_inpainting_fits(const float* out, const float* targets, int64_t target_stride, const float* masks, int64_t mask_stride, int mask_channels,
+                                      int n_fits, int S, int H, int W, float grad_scale, float* dout, double* nll, void* stream)
+{
+    const long long HW = (long long)H * W;
+    if (!out || !targets || !masks || !nll || n_fits < 1 || S < 1 || (long long)n_fits * S > 65535 || H < 1 || W < 1 || (mask_channels != 1 && mask_channels != 3) ||
+        target_stride < 3 * HW || (mask_stride != 0 && mask_stride < mask_channels * HW)) {
+        set_error("gaussian_nll_inpainting_fits: bad arguments (n_fits=%d S=%d H=%d W=%d mask_channels=%d target_stride=%lld mask_stride=%lld)", n_fits, S, H, W,
+                  mask_channels, (long long)target_stride, (long long)mask_stride); return -1; }
+    hipLaunchKernelGGL(gaussian_nll_inp_fits_kernel, dim3(nblocks(HW, 16), n_fits * S), dim3(256), 0, (hipStream_t)stream, out, targets, (long long)target_stride, masks,
+                       (long long)mask_stride, mask_channels, S, HW, grad_scale, dout, nll);
+    return (int)hipGetLastError();
+}
+
+int mfvi_ema_inpainting_fits(const float* out, int n_fits, int S, int H, int W, float* ema, float weight, int first, void* stream)
+{
+    if (!out || !ema || n_fits < 1 || n_fits > 65535 || S < 1 || H < 1 || W < 1) { set_error("ema_inpainting_fits: bad arguments"); return -1; }
+    const long long HW = (long long)H * W;
+    hipLaunchKernelGGL(ema_inp_fits_kernel, dim3(nblocks(HW, 256), n_fits), dim3(256), 0, (hipStream_t)stream, out, S, HW, ema, weight, first);
+    return (int)hipGetLastError();
+}
+
+int mfvi_masked_sq_err_fits(const float* ema, int64_t ema_stride, const float* img, int64_t img_stride, const float* masks, int64_t mask_stride, int mask_channels,
+                            int n_fits, int H, int W, double* acc, void* scratch, void* stream)
+{
+    const long long HW = (long long)H * W;
+    if (!ema || !img || !masks || !acc || !scratch || n_fits < 1 || n_fits > 65535 || H < 1 || W < 1 || (mask_channels != 1 && mask_channels != 3) ||
+        ema_stride < 3 * HW || img_stride < 3 * HW || (mask_stride != 0 && mask_stride < mask_channels * HW)) {
+        set_error("masked_sq_err_fits: bad arguments (n_fits=%d H=%d W=%d mask_channels=%d; strides >= 3 H W, scratch of n_fits * MFVI_MASKED_SQ_ERR_BLOCKS doubles)",
+                  n_fits, H, W, mask_channels); return -1; }
+    const int nb = nblocks(3 * HW, MFVI_MASKED_SQ_ERR_BLOCKS);
+    hipLaunchKernelGGL(masked_sq_err_fits_kernel, dim3(nb, n_fits), dim3(256), 0, (hipStream_t)stream, ema, (long long)ema_stride, img, (long long)img_stride, masks,
+                       (long long)mask_stride, mask_channels, HW, (double*)scratch);
+    hipLaunchKernelGGL(masked_sq_err_fits_finish_kernel, dim3(n_fits), dim3(64), 0, (hipStream_t)stream, (const double*)scratch, nb, acc);
     return (int)hipGetLastError();
 }
 

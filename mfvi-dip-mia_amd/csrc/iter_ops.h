@@ -132,3 +132,53 @@ __device__ __forceinline__ float sample_means_ema(const float* __restrict__ out,
     if (C > 1) ema[HW + i] = first ? a : ema[HW + i] * w + a * (1.f - w);
     return e0;
 }
+
+// ---- gaussian_nll with the sigmoid on the 3 colour channels, one shared log-precision channel and a mask (bayesian_optimization.py:3001-3010)
+// of ONE sample o[4][HW] against target[3][HW] / mask[mask_channels][HW]: this thread's share of the mean over 3 HW elements (grid x strides
+// over the pixels) and, with d, the gradient d[4][HW] ----
+__device__ __forceinline__ double gnll_inp_sample(const float* __restrict__ o, const float* __restrict__ target, const float* __restrict__ mask,
+                                                  int mask_channels, long long HW, float grad_scale, float* __restrict__ d)
+{
+    const float inv_n = 1.f / (float)(3 * HW);
+    double acc = 0;
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < HW; p += (long long)gridDim.x * 256) {
+        const float sraw = o[3 * HW + p];
+        const float s = fminf(fmaxf(sraw, -20.f), 20.f);
+        const bool inside = (sraw >= -20.f) && (sraw <= 20.f);
+        const float e = expf(s);
+        float ds = 0.f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float m = sigmoid_f(o[c * HW + p]);
+            const float mk = mask[(mask_channels == 3 ? c : 0) * HW + p];
+            const float df = target[c * HW + p] - m;
+            acc += (double)((e * df * df - s) * mk);
+            if (d) {
+                d[c * HW + p] = grad_scale * (-2.f * e * df) * mk * m * (1.f - m) * inv_n;
+                ds += (e * df * df - 1.f) * mk;
+            }
+        }
+        if (d) d[3 * HW + p] = inside ? grad_scale * ds * inv_n : 0.f;
+    }
+    return acc * (double)inv_n;
+}
+
+// ---- the inpainting runner's smoothed outputs (bayesian_optimization.py:3039-3064) at pixel i over the n samples out[n][4][HW]:
+// m[c] = mean_k sigmoid(out[k][c]), a = mean_k exp(-out[k][3]); ema[c] = first ? value : ema[c] * w + value * (1 - w), e0[c] the new ema[c][i] ----
+__device__ __forceinline__ void sample_means_ema_inp(const float* __restrict__ out, int n, long long HW, long long i, float* __restrict__ ema, float w,
+                                                     int first, float m[3], float e0[3], float& a)
+{
+    a = 0.f;
+    for (int k = 0; k < n; ++k) a += expf(-out[((long long)k * 4 + 3) * HW + i]);
+    a /= (float)n;
+    ema[3 * HW + i] = first ? a : ema[3 * HW + i] * w + a * (1.f - w);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float mc = 0.f;
+        for (int k = 0; k < n; ++k) mc += sigmoid_f(out[((long long)k * 4 + c) * HW + i]);
+        mc /= (float)n;
+        m[c] = mc;
+        e0[c] = first ? mc : ema[c * HW + i] * w + mc * (1.f - w);
+        ema[c * HW + i] = e0[c];
+    }
+}

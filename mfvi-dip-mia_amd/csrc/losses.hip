@@ -36,30 +36,8 @@ __global__ __launch_bounds__(256) void gaussian_nll_inp_kernel(const float* __re
 {
     __shared__ double s_red[8];
     const int k = blockIdx.y;
-    const float* __restrict__ o = out + (long long)k * 4 * HW;
-    float* __restrict__ d = dout ? dout + (long long)k * 4 * HW : nullptr;
-    const float inv_n = 1.f / (float)(3 * HW);
-    double acc = 0;
-    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < HW; p += (long long)gridDim.x * 256) {
-        const float sraw = o[3 * HW + p];
-        const float s = fminf(fmaxf(sraw, -20.f), 20.f);
-        const bool inside = (sraw >= -20.f) && (sraw <= 20.f);
-        const float e = expf(s);
-        float ds = 0.f;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float m = sigmoid_f(o[c * HW + p]);
-            const float mk = mask[(mask_channels == 3 ? c : 0) * HW + p];
-            const float df = target[c * HW + p] - m;
-            acc += (double)((e * df * df - s) * mk);
-            if (d) {
-                d[c * HW + p] = grad_scale * (-2.f * e * df) * mk * m * (1.f - m) * inv_n;
-                ds += (e * df * df - 1.f) * mk;
-            }
-        }
-        if (d) d[3 * HW + p] = inside ? grad_scale * ds * inv_n : 0.f;
-    }
-    block_atomic_add(acc * (double)inv_n, nll_sum, s_red);
+    block_atomic_add(gnll_inp_sample(out + (long long)k * 4 * HW, target, mask, mask_channels, HW, grad_scale, dout ? dout + (long long)k * 4 * HW : nullptr),
+                     nll_sum, s_red);
 }
 
 
@@ -376,20 +354,13 @@ __global__ __launch_bounds__(256) void bookkeep_inp_kernel(const float* __restri
                                                            float* __restrict__ ring_epi, float* __restrict__ ring_ale)
 {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < HW; i += (long long)gridDim.x * 256) {
-        float a = 0.f;
-        for (int k = 0; k < n; ++k) a += expf(-out[((long long)k * 4 + 3) * HW + i]);
-        a /= (float)n;
-        ema[3 * HW + i] = first ? a : ema[3 * HW + i] * w + a * (1.f - w);
+        float a, mean[3], e0s[3];
+        sample_means_ema_inp(out, n, HW, i, ema, w, first, mean, e0s, a);
         const float ac = fminf(fmaxf(a, 0.f), 1.f);
         ale_clip[i] = ac; if (ring_ale) ring_ale[i] = ac;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            float m = 0.f;
-            for (int k = 0; k < n; ++k) m += sigmoid_f(out[((long long)k * 4 + c) * HW + i]);
-            m /= (float)n;
-            const float e0 = first ? m : ema[c * HW + i] * w + m * (1.f - w);
-            ema[c * HW + i] = e0;
-            const float mc = fminf(fmaxf(m, 0.f), 1.f), ec = fminf(fmaxf(e0, 0.f), 1.f);
+            const float mc = fminf(fmaxf(mean[c], 0.f), 1.f), ec = fminf(fmaxf(e0s[c], 0.f), 1.f);
             const float mk = mask[(mask_channels == 3 ? c : 0) * HW + i];
             out_clip[c * HW + i] = mc; avg_clip[c * HW + i] = ec;
             if (ring_epi) ring_epi[c * HW + i] = mc;

@@ -276,9 +276,9 @@ int pass_setup(PassSetup& S, bool expand, uint64_t seed, uint32_t step, uint32_t
             if (rc) { set_error("%s: fits mode: the copy of the net input per sample failed (its size must be a multiple of 4 floats, z 16-byte aligned): %s", S.who, hipGetErrorString((hipError_t)rc)); return rc > 0 ? rc : -1; }
             S.c.z = zr;
         }
-        // the generic kernels draw from ONE mu / rho: a layer that lands there is an error (conv_dispatch.hip, to_generic), never fit 0's parameters
-        S.mu = S.rho = nullptr;
-        S.W = ConvWeights{S.c.wsamp(), plan->n_vi, nullptr, nullptr, S.key, 1, 1};
+        // a layer the matrix-core kernels decline (a map not a multiple of 4 wide) runs on the generic kernels: fit 0's mu / rho plus the strides,
+        // sample k reads and accumulates at fit k / fit_s (every layer is in the sampling table here: fits_refusal)
+        S.W = ConvWeights{S.c.wsamp(), plan->n_vi, S.mu, S.rho, S.key, 1, FitGeom{plan->fit_s, plan->fit_pstride, plan->fit_gstride}};
     }
     return 0;
 }

@@ -40,7 +40,7 @@ def check_args(S, n_slices, slices_per_launch, K, temp, sigma, lr, theta_deg, in
         raise ValueError("size %r: the Radon operator takes square slices" % (S,))
     H = int(H)
     if H < 1 or H % 4:
-        raise ValueError("S=%r: a multiple of 4 (the matrix-core kernels; fits mode has no generic path)" % (S,))
+        raise ValueError("S=%r: a multiple of 4 (the input-scale layers run on the matrix-core kernels)" % (S,))
     if int(n_slices) < 1 or int(n_slices) > MAX_LAUNCH:
         raise ValueError("n_slices=%r: 1 .. %d" % (n_slices, MAX_LAUNCH))
     if int(K) < 1:

@@ -1,55 +1,54 @@
-"""Many independent MFVI fits advanced by ONE iteration of launches.
+"""Many independent MFVI inpainting fits advanced by ONE iteration of launches.
 
-The reference runs its (temp, sigma) candidates and the slices of a volume as one process per fit, each a chain of small K = 1
-launches that leave most of an MI355X idle (bayesian_optimization.py:3760-3775, :1360-1372).  A FitBatch of F fits with K samples
-each is one plan of F * K samples in fits mode (mfvi_plan_set_fits): sample i belongs to fit i // K, reads that fit's mu / rho / BN
-block and input, and its gradient is reduced into that fit's row.  One iteration is
+The reference's inpainting search runs 50 000 iterations per (temp, sigma) candidate, one process per fit, each a chain of small K = 1
+launches on the 6-scale no-skip net (bayesian_optimization.py:2923-3075, bo_configs/bo_mfvi_inp.json), and ships six images with hair
+masks.  An InpaintBatch of F fits with K samples each is one plan of F * K samples of that net (4 outputs) in fits mode, as FitBatch is
+for denoising and super-resolution; one iteration is
 
     z[f]   = z0[f] + 0.1 * N(0,1)                 RNG domain INPUT, sample f          (mfvi_perturb_input_fits)
     out    = net(z)                                eps of global sample f * K + k      (mfvi_forward, fits mode)
-    nll[f] = 1/K sum_k NLL(out[f, k], target[f])                                       (mfvi_gaussian_nll_fits)
+    nll[f] = 1/K sum_k masked NLL(out[f, k], image[f], mask[f])                        (mfvi_gaussian_nll_inpainting_fits)
     grads                                                                              (mfvi_backward, fits mode)
     KL[f], Adam with temp[f], prior_sigma[f], lr[f]                                    (mfvi_elbo_update_fits)
-    ema[f]                                         on a second stream beside the backward pass (mfvi_ema_fits)
+    ema[f]                                         on a second stream beside the backward pass (mfvi_ema_inpainting_fits)
 
-whatever F is.  RNG identity: fit f owns the global samples f * K .. f * K + K - 1 of eps and sample f of the INIT, z0 and input
-perturbation domains, so fit 0 of a batch is the standalone ElboEngine(seed, K)."""
-import math
-
+whatever F is.  The reference's images are 320 x 256: the two deepest maps (10 and 5 wide) are no multiple of 4 wide and run on the generic
+fp32 kernels, which fits mode serves with the fit's own mu / rho.  RNG identity as FitBatch: fit 0 is ElboEngine(task="inp", seed, K)."""
 from . import _lib as L
+from .fitbatch import EXP_WEIGHT, per_fit, prior_sigmas
 from .program import skip_program
 
-TASKS = ("den", "sr")
-EXP_WEIGHT = 0.99       # EMA weight of the smoothed output (bayesian_optimization.py:1292)
+
+def inp_net():
+    from .engine import INP_NET
+    return dict(INP_NET)
 
 
-def per_fit(value, n_fits, name):
-    """A scalar or a sequence of length n_fits -> list of n_fits floats."""
-    try:
-        vals = [float(v) for v in value]
-    except TypeError:
-        return [float(value)] * n_fits
-    if len(vals) != n_fits:
-        raise ValueError("%s: %d values for %d fits (a scalar, or one value per fit)" % (name, len(vals), n_fits))
-    return vals
+def pyramid(H, W, n_scales):
+    """The map sizes below the input: every scale halves with a stride-2 convolution, (h, w) -> (ceil(h / 2), ceil(w / 2))."""
+    maps = []
+    for _ in range(n_scales):
+        H, W = (H + 1) // 2, (W + 1) // 2
+        maps.append((H, W))
+    return maps
 
 
-def prior_sigmas(temps, sigmas):
-    """Per fit, exactly as ElboEngine computes it (bayesian_optimization.py:1335-1336 + modules/module.py:38, rounded to fp32)."""
-    import numpy as np
-    return [float(np.float32(math.sqrt(t) * s + 1e-6)) for t, s in zip(temps, sigmas)]
-
-
-def check_args(H, W, n_fits, task, K, temp, sigma, lr, init):
+def check_args(H, W, n_fits, K, temp, sigma, lr, init, net_kwargs=None):
     """Everything that can be refused without the library; -> (temps, sigmas, lrs)."""
-    if task in ("ct", "inp"):
-        raise NotImplementedError("FitBatch serves denoising and super-resolution; the data terms of task %r are not batched" % (task,))
-    if task not in TASKS:
-        raise ValueError("task %r: 'den' or 'sr'" % (task,))
     if int(n_fits) < 1 or int(K) < 1 or int(n_fits) * int(K) > 65535:
         raise ValueError("n_fits=%r, K=%r: at least 1 each, n_fits * K < 65536" % (n_fits, K))
     if H < 1 or W < 1 or H % 4 or W % 4:
         raise ValueError("H=%r, W=%r: multiples of 4 (the input-scale layers run on the matrix-core kernels)" % (H, W))
+    kw = inp_net(); kw.update(net_kwargs or {})
+    pad = max(kw.get("fd", 3), kw.get("fu", 3)) // 2
+    ns = kw.get("ns", ())
+    maps = pyramid(H, W, len(kw["nd"]))
+    for i, (h, w) in enumerate(maps):
+        if min(h, w) <= pad:
+            raise ValueError("H=%r, W=%r: the map of scale %d is %d x %d; every map of the pyramid must be at least %d on a side (reflection pad %d "
+                             "of the %d x %d filters)" % (H, W, i + 1, h, w, pad + 1, pad, 2 * pad + 1, 2 * pad + 1))
+        if i < len(maps) - 1 and not (ns and ns[i + 1]) and (h % 2 or w % 2):
+            raise ValueError("H=%r, W=%r: the map of scale %d is %d x %d; without a skip branch only the deepest map may be odd" % (H, W, i + 1, h, w))
     if init not in ("per_fit", "shared"):
         raise ValueError("init %r: 'per_fit' or 'shared'" % (init,))
     temps, sigmas, lrs = per_fit(temp, n_fits, "temp"), per_fit(sigma, n_fits, "sigma"), per_fit(lr, n_fits, "lr")
@@ -58,31 +57,32 @@ def check_args(H, W, n_fits, task, K, temp, sigma, lr, init):
     return temps, sigmas, lrs
 
 
-class FitBatch:
-    def __init__(self, H, W, n_fits, task="den", K=1, input_depth=16, temp=1.0, sigma=0.1, lr=1e-3, seed=1, sr_factor=4, net_kwargs=None,
-                 init="per_fit", autotune=True):
-        self.temps, self.sigmas, self.lrs = check_args(H, W, n_fits, task, K, temp, sigma, lr, init)
-        if task == "sr" and (sr_factor < 1 or H % sr_factor or W % sr_factor):
-            raise ValueError("sr_factor %r does not divide %dx%d" % (sr_factor, H, W))
+class InpaintBatch:
+    def __init__(self, H, W, n_fits, K=1, input_depth=32, temp=1.0, sigma=0.1, lr=2e-3, seed=1, net_kwargs=None, init="per_fit", autotune=True):
+        self.temps, self.sigmas, self.lrs = check_args(H, W, n_fits, K, temp, sigma, lr, init, net_kwargs)
         import numpy as np
         import torch
         self.torch = torch
-        self.task, self.F, self.K, self.H, self.W = task, int(n_fits), int(K), H, W
-        self.seed, self.sr_factor, self.input_depth, self.init = int(seed), int(sr_factor), int(input_depth), init
+        self.task, self.F, self.K, self.H, self.W = "inp", int(n_fits), int(K), H, W
+        self.seed, self.input_depth, self.init = int(seed), int(input_depth), init
         self.net_kwargs = dict(net_kwargs or {})
         self.prior_sigma = prior_sigmas(self.temps, self.sigmas)
-        self.prog, self.zin, self.zout, self.names = skip_program(H, W, input_depth, 2, **self.net_kwargs)
+        kw = inp_net(); kw.update(self.net_kwargs)
+        self.prog, self.zin, self.zout, self.names = skip_program(H, W, input_depth, 4, **kw)
         F, K, P = self.F, self.K, self.prog
         self.n = F * K
         self.plan = P.compile(self.zin, self.zout, self.n)
+        if tuple(self.plan.out_shape) != (4, H, W):
+            raise ValueError("the net maps %dx%d to %s" % (H, W, tuple(self.plan.out_shape)))
         self.n_vi, self.n_bn = P.n_vi, P.n_bn
         self.n_params = 2 * P.n_vi + P.n_bn
-        self.stride = (self.n_params + 3) // 4 * 4                   # row stride of params / m / v / grads: every fit's MU block 16-byte aligned
+        self.stride = (self.n_params + 3) // 4 * 4                   # as FitBatch: every fit's MU block 16-byte aligned
         dev = "cuda"
         self._pbuf = torch.zeros((F, self.stride), dtype=torch.float32, device=dev)
         self._mbuf = torch.zeros_like(self._pbuf); self._vbuf = torch.zeros_like(self._pbuf)
         self.params, self.m, self.v = self._pbuf[:, :self.n_params], self._mbuf[:, :self.n_params], self._vbuf[:, :self.n_params]
-        # gradients and the float64 NLL accumulators in ONE allocation: one fill launch clears both per iteration
+        # gradients and the float64 NLL accumulators in ONE allocation: one fill launch clears both per iteration (the generic kernels
+        # accumulate into the rows by atomics, so the rows must start from zero)
         self._gbuf = torch.zeros(4 * F * self.stride + 8 * F, dtype=torch.uint8, device=dev)
         self._grows = self._gbuf[:4 * F * self.stride].view(torch.float32).view(F, self.stride)
         self.grads = self._grows[:, :self.n_params]
@@ -92,11 +92,12 @@ class FitBatch:
         self.hyper = torch.tensor(np.array([[0.0, ps, t, r] for ps, t, r in zip(self.prior_sigma, self.temps, self.lrs)], np.float32), device=dev)   # mfvi_fit_hyper[F]
         self.z0 = torch.empty((F, input_depth, H, W), dtype=torch.float32, device=dev)
         self.z = torch.empty_like(self.z0)
-        self.out = torch.empty((self.n, 2, H, W), dtype=torch.float32, device=dev)
+        self.out = torch.empty((self.n, 4, H, W), dtype=torch.float32, device=dev)
         self.dout = torch.empty_like(self.out)
-        self.ema = torch.zeros((F, 2, H, W), dtype=torch.float32, device=dev)
+        self.ema = torch.zeros((F, 4, H, W), dtype=torch.float32, device=dev)
         self.upd_scratch = torch.zeros(L.lib().mfvi_elbo_update_fits_scratch_bytes(F), dtype=torch.uint8, device=dev)
-        self.targets = None
+        self.err_scratch = torch.zeros(F * L.MASKED_SQ_ERR_BLOCKS, dtype=torch.float64, device=dev)
+        self.images = None; self.masks = None; self._mask_stride = 0
         self.t = 0
         self._ema_n = 0                  # EMA updates so far (the first one copies)
         self._side = None; self._ema_done = None
@@ -130,13 +131,26 @@ class FitBatch:
             self._pbuf[1:] = self._pbuf[:1]; self.z0[1:] = self.z0[:1]
         self._mbuf.zero_(); self._vbuf.zero_(); self.dead_dev.zero_(); self.t = 0; self._ema_n = 0
 
-    def set_targets(self, targets):
-        """den: the noisy images [F, H, W]; sr: the low-resolution images [F, H / f, W / f]."""
-        t = self.torch.as_tensor(targets)
-        f = self.sr_factor if self.task == "sr" else 1
-        if tuple(t.shape) != (self.F, self.H // f, self.W // f):
-            raise ValueError("targets of shape %s, expected %s" % (tuple(t.shape), (self.F, self.H // f, self.W // f)))
-        self.targets = t.contiguous().float().cuda()
+    def set_targets(self, images, masks):
+        """The colour images [F, 3, H, W] and the masks (1 = known pixel): [F, 1|3, H, W], or one mask [1|3, H, W] / [H, W] shared by every
+        fit.  Masks are rounded as ElboEngine.set_target rounds them (bayesian_optimization.py:3024)."""
+        torch = self.torch
+        t = torch.as_tensor(images)
+        if tuple(t.shape) != (self.F, 3, self.H, self.W):
+            raise ValueError("images of shape %s, expected %s" % (tuple(t.shape), (self.F, 3, self.H, self.W)))
+        m = torch.as_tensor(masks)
+        if m.dim() == 2:
+            m = m[None]
+        shared = m.dim() == 3
+        if m.dim() not in (3, 4) or tuple(m.shape[-2:]) != (self.H, self.W) or m.shape[-3] not in (1, 3) or (not shared and m.shape[0] != self.F):
+            raise ValueError("masks of shape %s, expected [%d, 1|3, %d, %d] or one shared [1|3, %d, %d]" % (tuple(m.shape), self.F, self.H, self.W, self.H, self.W))
+        self.images = t.contiguous().float().cuda()
+        self.masks = m.contiguous().float().cuda().round()
+        self.mask_channels = int(m.shape[-3])
+        self._mask_stride = 0 if shared else self.mask_channels * self.H * self.W
+
+    def mask_of(self, f):
+        return self.masks if self._mask_stride == 0 else self.masks[f]
 
     # -------------------------------------------------------------------------------------------
     def _wait_ema(self):
@@ -151,14 +165,14 @@ class FitBatch:
         ready = t.cuda.Event(); ready.record(t.cuda.current_stream())
         with t.cuda.stream(self._side):
             self._side.wait_event(ready)
-            L.check(L.lib().mfvi_ema_fits(L.ptr(self.out), self.F, self.K, 2, self.H, self.W, L.ptr(self.ema), EXP_WEIGHT, int(self._ema_n == 0),
-                                          L.stream_ptr()))
+            L.check(L.lib().mfvi_ema_inpainting_fits(L.ptr(self.out), self.F, self.K, self.H, self.W, L.ptr(self.ema), EXP_WEIGHT, int(self._ema_n == 0),
+                                                     L.stream_ptr()))
             self._ema_done.record(self._side)
         self._ema_n += 1
 
     def grad_only(self, step=None, perturb=True, ema=False):
         """Everything of one iteration except the update: grads [F, n_params] and nll_acc [F] hold the result (no KL term)."""
-        if self.targets is None:
+        if self.images is None:
             raise ValueError("set_targets first")
         lib, sp = L.lib(), L.stream_ptr()
         step = self.t if step is None else int(step)
@@ -173,8 +187,8 @@ class FitBatch:
         mu, rho, bn = p0[:self.n_vi], p0[self.n_vi:], p0[2 * self.n_vi:]
         g0 = self._grows[0]
         self.plan.forward(mu, rho, bn, zsrc, self.seed, step, 0, self.n, True, self.out)
-        L.check(lib.mfvi_gaussian_nll_fits(L.ptr(self.out), L.ptr(self.targets), self.targets[0].numel(), F, K, self.H, self.W,
-                                           self.sr_factor if self.task == "sr" else 1, 1.0 / K, L.ptr(self.dout), L.ptr(self.nll_acc), sp))
+        L.check(lib.mfvi_gaussian_nll_inpainting_fits(L.ptr(self.out), L.ptr(self.images), 3 * self.H * self.W, L.ptr(self.masks), self._mask_stride,
+                                                      self.mask_channels, F, K, self.H, self.W, 1.0 / K, L.ptr(self.dout), L.ptr(self.nll_acc), sp))
         if ema:
             self._ema()
         self.plan.backward(mu, rho, bn, zsrc, self.seed, step, 0, self.n, self.dout, g0[:self.n_vi], g0[self.n_vi:], g0[2 * self.n_vi:], True)
@@ -203,40 +217,48 @@ class FitBatch:
         return self.dead_dev.cpu().numpy()
 
     def recon(self):
-        """clip(ema[:, 0], 0, 1) [F, H, W]: the smoothed reconstruction of every fit."""
+        """clip(ema[:, :3], 0, 1) [F, 3, H, W]: the smoothed reconstruction of every fit."""
         self._wait_ema()
-        return self.ema[:, 0].clamp(0.0, 1.0).contiguous()
+        return self.ema[:, :3].clamp(0.0, 1.0).contiguous()
+
+    def ale(self):
+        """clip(ema[:, 3], 0, 1) [F, H, W]: the smoothed aleatoric variance exp(-s) of every fit."""
+        self._wait_ema()
+        return self.ema[:, 3].clamp(0.0, 1.0).contiguous()
 
     def psnr(self, gt):
-        """[F]: PSNR of clip(ema[:, 0], 0, 1) against the ground truth ([H, W] shared, or [F, H, W]) -- the psnr_gt_sm the reference returns to
-        its search (bayesian_optimization.py:1400-1403, :1436)."""
+        """[F]: PSNR of clip(ema[:, :3]) * mask against gt * mask, gt [3, H, W] shared or [F, 3, H, W] -- the psnr_gt_sm the inpainting runner
+        returns to its search (bayesian_optimization.py:3049-3055), by mfvi_masked_sq_err_fits: one fixed-order reduction for all fits."""
         import numpy as np
         torch, lib, sp = self.torch, L.lib(), L.stream_ptr()
+        if self.masks is None:
+            raise ValueError("set_targets first")
         g = torch.as_tensor(gt).float().cuda()
-        if g.dim() == 2:
-            g = g[None].expand(self.F, -1, -1)
-        if tuple(g.shape) != (self.F, self.H, self.W):
-            raise ValueError("ground truth of shape %s, expected %s" % (tuple(g.shape), (self.F, self.H, self.W)))
+        if g.dim() == 3:
+            g = g[None].expand(self.F, -1, -1, -1)
+        if tuple(g.shape) != (self.F, 3, self.H, self.W):
+            raise ValueError("ground truth of shape %s, expected %s" % (tuple(g.shape), (self.F, 3, self.H, self.W)))
         g = g.contiguous()
-        rec = self.recon()
+        self._wait_ema()
+        HW = self.H * self.W
         acc = torch.zeros(self.F, dtype=torch.float64, device="cuda")
-        for f in range(self.F):
-            L.check(lib.mfvi_sq_err_sum(L.ptr(g[f]), L.ptr(rec[f]), self.H * self.W, L.ptr(acc[f:]), sp))
-        mse = acc.cpu().numpy() / float(self.H * self.W)
+        L.check(lib.mfvi_masked_sq_err_fits(L.ptr(self.ema), 4 * HW, L.ptr(g), 3 * HW, L.ptr(self.masks), self._mask_stride, self.mask_channels, self.F,
+                                            self.H, self.W, L.ptr(acc), L.ptr(self.err_scratch), sp))
+        mse = acc.cpu().numpy() / float(3 * HW)
         with np.errstate(divide="ignore"):
             return 10.0 * np.log10(1.0 / mse)
 
     def to_engine(self, f, autotune=False):
-        """An ElboEngine holding copies of fit f's parameters, Adam moments, step count, input and target: predict(), calibration and the
-        single-fit runner then work on any fit of a batch.  (Continued alone it draws eps of the global samples 0 .. K - 1, not f * K ..)"""
+        """An ElboEngine(task="inp") holding copies of fit f's parameters, Adam moments, step count, input, image and mask: predict() and
+        the single-fit runner then work on any fit of a batch.  (Continued alone it draws eps of the global samples 0 .. K - 1, not f * K ..)"""
         from .engine import ElboEngine
         if not 0 <= f < self.F:
             raise ValueError("fit %r outside 0..%d" % (f, self.F - 1))
-        eng = ElboEngine(self.H, self.W, task=self.task, K=self.K, input_depth=self.input_depth, temp=self.temps[f], sigma=self.sigmas[f],
-                         lr=self.lrs[f], seed=self.seed, sr_factor=self.sr_factor, net_kwargs=self.net_kwargs, autotune=autotune)
+        eng = ElboEngine(self.H, self.W, task="inp", K=self.K, input_depth=self.input_depth, temp=self.temps[f], sigma=self.sigmas[f],
+                         lr=self.lrs[f], seed=self.seed, net_kwargs=self.net_kwargs, autotune=autotune)
         v = self.fit(f)
         eng.params.copy_(v["params"]); eng.m.copy_(v["m"]); eng.v.copy_(v["v"]); eng.z0.copy_(v["z0"])
         eng.t = self.t; eng.t_applied.fill_(self.t)
-        if self.targets is not None:
-            eng.set_target(self.targets[f].clone())
+        if self.images is not None:
+            eng.set_target(self.images[f].clone(), self.mask_of(f).clone())
         return eng

@@ -438,6 +438,18 @@ run_ct_mcd = _sibling("ct", "mcd", dict(dropout_p=0.3, weight_decay=3e-4))
 run_ct_sgld = _sibling("ct", "sgld", dict(gamma=0.996, weight_decay=5e-8))
 
 
+def scratch_mask(H, W, seed):
+    """Synthetic scratches for a job without a mask: a seeded random-walk mask [1, H, W], ~12 % missing (1 = known pixel)."""
+    rng = np.random.default_rng(seed)
+    mask = np.ones((1, H, W), np.float32)
+    for _ in range(24):
+        y, x = rng.integers(0, H), rng.integers(0, W)
+        for _ in range(H):
+            mask[0, max(y - 1, 0):y + 2, max(x - 1, 0):x + 2] = 0
+            y = int(np.clip(y + rng.integers(-1, 2), 0, H - 1)); x = int(np.clip(x + rng.integers(-1, 2), 0, W - 1))
+    return mask
+
+
 def run_inp_mfvi(img="phantom", mask=None, imsize=(256, 256), num_iter=5000, lr=2e-3, temp=4e-6, sigma=0.01, input_depth=32, seed=42,
                  show_every=100, plot=False, save=True, save_path="../logs", K=1, net_kwargs=None, verbose=False, method="mfvi",
                  weight_decay=1e-4, dropout_p=0.2, gamma=0.996, predict_samples=0, calibration=False, calibration_bins=15, **unused):
@@ -462,14 +474,8 @@ def run_inp_mfvi(img="phantom", mask=None, imsize=(256, 256), num_iter=5000, lr=
     else:
         img_np = np.stack([_load_image(img, imsize, seed + c) for c in range(3)]).astype(np.float32)
     _, H, W = img_np.shape
-    if mask is None:                                                  # synthetic scratches: a seeded random-walk mask, ~12 % missing
-        rng = np.random.default_rng(seed)
-        mask = np.ones((1, H, W), np.float32)
-        for _ in range(24):
-            y, x = rng.integers(0, H), rng.integers(0, W)
-            for _ in range(H):
-                mask[0, max(y - 1, 0):y + 2, max(x - 1, 0):x + 2] = 0
-                y = int(np.clip(y + rng.integers(-1, 2), 0, H - 1)); x = int(np.clip(x + rng.integers(-1, 2), 0, W - 1))
+    if mask is None:
+        mask = scratch_mask(H, W, seed)
     mask_np = np.ascontiguousarray(mask, np.float32)
     if mask_np.ndim == 2:
         mask_np = mask_np[None]
@@ -590,9 +596,72 @@ def fit_batch_job(task, jobs, **kw):
     return run_fit_batch(task, jobs, **kw)["psnr"]
 
 
-def _run_batches(task, jobs, n, rp, K, devices, verbose=False):
-    """jobs -> batches of up to n (fanout.group_jobs) -> one FitBatch each, here or dealt round-robin to one worker per device.
-    Returns (results [(job index, job, psnr)], dropped [(job index, job, why)], batches)."""
+def run_inpaint_batch(jobs, imsize=(256, 256), num_iter=5000, lr=2e-3, input_depth=32, seed=42, show_every=100, save=True, save_path="../logs",
+                      K=1, net_kwargs=None, verbose=False, autotune=True, mask=None, **unused):
+    """The (image, mask, temp, sigma) jobs of one batch as ONE InpaintBatch (--inpaint-fits): the loop of run_inp_mfvi for
+    every job at once.  jobs: dicts with img ((3, H, W) array, or what run_inp_mfvi loads), temp, sigma and optionally mask ((1|3, H, W);
+    absent: `mask`, the run_params' mask that run_inp_mfvi takes too, else that function's seeded scratch mask) and lr.
+    Writes batch.npz with the keys of run_fit_batch plus mask, recon [F, 3, H, W] and
+    ale [F, H, W]; save.npz and the PNG artefacts stay with the single-fit runner.  Returns dict(psnr=[per fit, NaN for a dead fit], ...)."""
+    import torch
+    from .inpaintbatch import InpaintBatch
+    F = len(jobs)
+    imgs = [np.ascontiguousarray(j["img"], np.float32) if isinstance(j["img"], np.ndarray) else
+            np.stack([_load_image(j["img"], imsize, seed + c) for c in range(3)]).astype(np.float32) for j in jobs]
+    _, H, W = imgs[0].shape
+    if any(im.shape != (3, H, W) for im in imgs):
+        raise ValueError("the images of one batch must share their size, (3, H, W) each")
+    masks = []
+    for j in jobs:
+        m = j.get("mask") if j.get("mask") is not None else mask
+        m = np.ascontiguousarray(m, np.float32) if m is not None else scratch_mask(H, W, seed)
+        masks.append(m[None] if m.ndim == 2 else m)
+    if any(m.shape != masks[0].shape or m.shape[1:] != (H, W) for m in masks):
+        raise ValueError("the masks of one batch must share their shape, (1|3, H, W) each")
+    gt, mask = np.stack(imgs), np.stack(masks)
+    temps, sigmas, lrs = [j["temp"] for j in jobs], [j["sigma"] for j in jobs], [j.get("lr", lr) for j in jobs]
+    ib = InpaintBatch(H, W, F, K=K, input_depth=input_depth, temp=temps, sigma=sigmas, lr=lrs, seed=seed, net_kwargs=net_kwargs, init="shared",
+                      autotune=autotune)                               # the reference's candidates all start from one seed
+    ib.set_targets(torch.from_numpy(gt), torch.from_numpy(mask))
+    n_it = num_iter + 1                                               # bayesian_optimization.py:2935
+    at, psnrs, nlls, kls = [], [], [], []
+    t0 = time.perf_counter()
+    for i in range(n_it):
+        ib.step()
+        if i % show_every == 0 or i == n_it - 1:
+            nll, kl, _ = ib.losses()
+            at.append(i); psnrs.append(ib.psnr(gt)); nlls.append(nll); kls.append(kl)
+            if verbose:
+                print("iter %6d  psnr_gt_sm %s  (%.1f it/s x %d fits)" % (i, np.array2string(psnrs[-1], precision=2), (i + 1) / (time.perf_counter() - t0), F))
+    dead = ib.dead
+    final = np.where(dead != 0, np.nan, psnrs[-1])
+    run_dir = None
+    if save:
+        run_dir = os.path.join(save_path, "%s_batch" % time.time())
+        os.makedirs(run_dir, exist_ok=False)
+        np.savez(os.path.join(run_dir, "batch.npz"), task="inp", temp=np.asarray(temps), sigma=np.asarray(sigmas), lr=np.asarray(lrs),
+                 prior_sigma=np.asarray(ib.prior_sigma), K=np.int64(K), seed=np.int64(seed), num_iter=np.int64(num_iter), iterations=np.asarray(at),
+                 psnr_gt_sm=np.stack(psnrs), nll=np.stack(nlls), kl=np.stack(kls), recon=ib.recon().cpu().numpy(), dead=dead,
+                 mask=ib.masks.cpu().numpy(), ale=ib.ale().cpu().numpy())
+    return dict(psnr=[float(x) for x in final], run_dir=run_dir, seconds=time.perf_counter() - t0, batch=ib, dead=dead)
+
+
+def inpaint_batch_job(task, jobs, **kw):
+    """One batch of inpainting fits in a worker process of the fan-out -> the PSNR of every fit."""
+    return run_inpaint_batch(jobs, **kw)["psnr"]
+
+
+def _fit_batches(task, jobs, **kw):
+    return run_fit_batch(task, jobs, **kw)
+
+
+def _inpaint_batches(task, jobs, **kw):
+    return run_inpaint_batch(jobs, **kw)
+
+
+def _run_batches(task, jobs, n, rp, K, devices, verbose=False, batch_fn=_fit_batches, worker="mfvi_dip_mia_amd.runner:fit_batch_job"):
+    """jobs -> batches of up to n (fanout.group_jobs) -> one batch_fn(task, jobs, ...) each (a FitBatch, or an InpaintBatch), here or dealt
+    round-robin to one worker per device.  Returns (results [(job index, job, psnr)], dropped [(job index, job, why)], batches)."""
     from .fanout import group_jobs, run_jobs
     shapes = {}      # (the size of an image file is known once it is read; every distinct image once)
     for j in jobs:
@@ -604,13 +673,13 @@ def _run_batches(task, jobs, n, rp, K, devices, verbose=False):
     rp = {k: v for k, v in rp.items() if k not in ("plot",)}
     per_batch = {}
     if devices:
-        res, drop = run_jobs(bjobs, devices, "mfvi_dip_mia_amd.runner:fit_batch_job", dict(rp, task=task, K=K))
+        res, drop = run_jobs(bjobs, devices, worker, dict(rp, task=task, K=K))
         per_batch = {bi: (y, None) for bi, _, y in res}
         per_batch.update({bi: (None, why) for bi, _, why in drop})
     else:
         for bi, bj in enumerate(bjobs):
             try:
-                per_batch[bi] = (run_fit_batch(task, bj["jobs"], K=K, verbose=verbose, **rp)["psnr"], None)
+                per_batch[bi] = (batch_fn(task, bj["jobs"], K=K, verbose=verbose, **rp)["psnr"], None)
             except (RuntimeError, ValueError) as e:
                 per_batch[bi] = (None, "%s: %s" % (type(e).__name__, e))
     results, dropped = [], []
@@ -721,6 +790,9 @@ def main(argv=None):
     ap.add_argument("--fits-per-launch", type=int, default=0, help="> 0: the independent (image, candidate) fits run in batches of up to N as ONE "
                                                                    "set of launches per iteration (FitBatch; mfvi denoising / super-resolution); "
                                                                    "writes batch.npz per batch instead of save.npz per fit")
+    ap.add_argument("--inpaint-fits", type=int, default=0, help="> 0 (--task inpainting --bayes mfvi): the independent (image, candidate) fits run in "
+                                                                "batches of up to N as ONE set of launches per iteration (InpaintBatch); writes "
+                                                                "batch.npz per batch instead of save.npz per fit")
     ap.add_argument("--ct-volume", default=None, help="--task ct --bayes mfvi: a .npy file holding a stack [D, S, S], or phantom:D; the slices are "
                                                          "fitted as ONE CtVolume per candidate (one set of launches per group of slices) and "
                                                          "volume.npz is written instead of save.npz per slice")
@@ -735,6 +807,17 @@ def main(argv=None):
             ap.error("--sr-downsampler %s belongs to --task super-resolution --bayes mfvi" % a.sr_downsampler)
         if a.fits_per_launch:
             ap.error("--sr-downsampler %s does not combine with --fits-per-launch (batched fits project with [::f, ::f])" % a.sr_downsampler)
+    if a.inpaint_fits < 0:
+        ap.error("--inpaint-fits %d: 0 (off) or the number of fits per launch" % a.inpaint_fits)
+    if a.inpaint_fits:      # refused before anything loads the library, and ahead of the other batching flags' own refusals
+        for flag, on in (("--fits-per-launch", a.fits_per_launch), ("--ct-volume", a.ct_volume is not None), ("--predict-samples", a.predict_samples),
+                         ("--calibration", a.calibration)):
+            if on:
+                ap.error("--inpaint-fits does not combine with %s (InpaintBatch.to_engine(f) serves one fit of a batch)" % flag)
+        if a.task != "inpainting" or a.bayes != "mfvi":
+            ap.error("--inpaint-fits batches mean-field VI inpainting fits (--task inpainting --bayes mfvi), not --task %s --bayes %s" % (a.task, a.bayes))
+        if a.param_dtype != "f32":
+            ap.error("--inpaint-fits takes float32 parameters (--param-dtype f32)")
     if a.slices_per_launch is not None and (a.ct_volume is None or a.slices_per_launch < 1):
         ap.error("--slices-per-launch %d: at least 1, and only with --ct-volume" % a.slices_per_launch)
     if a.ct_volume is not None:      # refused before anything loads the library
@@ -810,6 +893,7 @@ def main(argv=None):
     rp.pop("img", None)
     jobs = [dict(cand, img=im) for im in imgs for cand in cands]
     devices = a.devices.split(",") if a.devices else cfg_devices
+    batch_kw = dict(batch_fn=_inpaint_batches, worker="mfvi_dip_mia_amd.runner:inpaint_batch_job") if a.inpaint_fits else {}
     if a.bo_rounds > 0:
         # bo() of the reference (bayesian_optimization.py:3727-3880): rounds of [fits of the candidates over the devices -> GP -> new candidates]
         from . import bo as _bo
@@ -820,8 +904,8 @@ def main(argv=None):
 
         def evaluate(cand_list):
             jb = [dict(zip(keys, c), img=imgs[0]) for c in cand_list]
-            if a.fits_per_launch:      # a round's candidates form batches
-                res, _, _ = _run_batches(short, jb, a.fits_per_launch, rp, a.k, devices)
+            if a.fits_per_launch or a.inpaint_fits:      # a round's candidates form batches
+                res, _, _ = _run_batches(short, jb, a.fits_per_launch or a.inpaint_fits, rp, a.k, devices, **batch_kw)
                 return [(tuple(job[k] for k in keys), y) for _, job, y in res]
             if devices:
                 from .fanout import run_jobs
@@ -829,10 +913,11 @@ def main(argv=None):
                 return [(tuple(job[k] for k in keys), y) for _, job, y in res]
             return [(c, fn(K=a.k, verbose=False, **j, **rp)["psnr"]) for c, j in zip(cand_list, jb)]
         return _bo.bo(bo_params, evaluate, n_rounds=a.bo_rounds)
-    if a.fits_per_launch:
+    if a.fits_per_launch or a.inpaint_fits:
         from .fanout import print_table
-        results, dropped, batches = _run_batches(short, jobs, a.fits_per_launch, rp, a.k, devices, verbose=True)
-        print("%d fits in %d batches of up to %d" % (len(jobs), len(batches), a.fits_per_launch))
+        per = a.fits_per_launch or a.inpaint_fits
+        results, dropped, batches = _run_batches(short, jobs, per, rp, a.k, devices, verbose=True, **batch_kw)
+        print("%d fits in %d batches of up to %d" % (len(jobs), len(batches), per))
         print_table(results, list(BO_KEYS[a.bayes]))
         for i, job, why in dropped:
             print("dropped fit %d %s: %s" % (i, {k: v for k, v in job.items() if k != "img"}, why))
