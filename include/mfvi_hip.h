@@ -167,12 +167,22 @@ int mfvi_plan_set_param_dtype(mfvi_plan* plan, int dtype);
  * atomicAdd over samples and tiles in both modes, so a net that reaches them is not bit-reproducible from call to call.  S = 0 (the default) switches the mode off: one fit, as before.
  * S > 1 grows the workspace by one copy of the net input per sample: ask mfvi_plan_workspace_bytes again afterwards.
  * Not served, and refused with MFVI_ERR_FITS_UNSUPPORTED and a message (never run with fit 0's parameters): bf16 parameter storage, plans
- * with local-reparameterisation layers, sample_weights = 0, BatchNorm eval mode and mfvi_plan_bn_update_running, a gradient split, a device
+ * with local-reparameterisation layers, sample_weights = 0 (unless mfvi_plan_set_fits_points), BatchNorm eval mode and mfvi_plan_bn_update_running, a gradient split, a device
  * step source, layers outside the sampled-weight slab (input channels / weight offsets not multiples of 4) and MFVI_DISABLE_MFMA.
  * mfvi_plan_autotune runs BEFORE the mode is switched on (tilings do not depend on it); in-kernel-eps tilings (tune bit 27) fall back to the
  * heuristic when it is. */
 #define MFVI_ERR_FITS_UNSUPPORTED (-5)
 int mfvi_plan_set_fits(mfvi_plan* plan, int samples_per_fit, int64_t param_stride, int64_t grad_stride);
+/* Point weights in fits mode (the DIP / MC-dropout / SGLD siblings run w = mu).  Off by default: fits mode refuses
+ * sample_weights = 0.  While on, a fits-mode pass with sample_weights = 0 writes every sample's row of the sampled-weight slab with its own
+ * fit's mu (eps = 0, weights and biases), every conv family reads the rows as in a sampled pass, each fit's samples are reduced into that
+ * fit's dmu row and drho is not touched.  No effect outside fits mode.  Refused (MFVI_ERR_FITS_UNSUPPORTED) for what fits mode refuses. */
+int mfvi_plan_set_fits_points(mfvi_plan* plan, int enabled);
+/* Dropout2d probability per fit (fits mode): sample k of a pass draws the factors of every tensor created with dropout with p[k / S]
+ * instead of the tensor's own drop_p -- same Philox counter, same comparison u >= p, same scale 1.0f / (1.0f - p), so a fit whose p equals
+ * the tensor's gets bit-identical masks; p = 0 gives factors of 1.  p: HOST array of n_fits values in [0, 1) (copied); NULL or n_fits = 0
+ * clears it.  A fits-mode pass whose n_samples / S differs from n_fits is refused before any launch. */
+int mfvi_plan_set_fit_dropout(mfvi_plan* plan, const float* p, int n_fits);
 /* bytes of caller-provided device workspace (activations, gradients, BN statistics) for max_samples */
 int64_t mfvi_plan_workspace_bytes(const mfvi_plan* plan);
 
@@ -488,6 +498,29 @@ int mfvi_masked_sq_err_fits(const float* ema, int64_t ema_stride, const float* i
 int64_t mfvi_radon_mse_fits_scratch_bytes(int n_fits, int S_per_fit, int S, int T);
 int mfvi_radon_mse_fits(const float* out, const float* sinos, int64_t sino_stride, const float* theta_deg, int n_fits, int S_per_fit, int S, int T,
                         float grad_scale, void* scratch, float* dout, double* mse, void* stream);
+
+/* ---- the non-Bayesian siblings (DIP, MC dropout, SGLD) for many fits per launch ------------------------------- */
+/* mfvi_mse_channel per fit: out / dout [n_fits * S][C][H][W], fit f against targets + f * target_stride ([H/factor][W/factor]);
+ * mse_acc[f] (device doubles) += sum over the fit's S samples of their mean squared error, summed in fp64 by one block per fit in a fixed
+ * order (no atomics: two calls are bit-identical); dout (optional, all C channels written) = grad_scale * d mse / d out.  -1 and a message
+ * for target_stride < (H/factor) * (W/factor) and other bad arguments, before any launch. */
+int mfvi_mse_channel_fits(const float* out, const float* targets, int64_t target_stride, int n_fits, int S, int C, int H, int W, int channel,
+                          int factor, float grad_scale, float* dout, double* mse_acc, void* stream);
+/* mfvi_adamw_step (decoupled weight decay) on the MU block [0, n_vi) and the BN block [2 n_vi, 2 n_vi + n_bn) of every fit's row in one
+ * launch; the RHO block is neither read nor written.  Per-fit hyper-parameters in DEVICE memory: the update uses (float)lr, as a caller
+ * of mfvi_adamw_step passes it.  A fit whose loss_acc[f] is not finite, or whose dead[f] is set, keeps parameters, moments and lr; a
+ * non-finite loss_acc[f] sets dead[f] = 1 (sticky).  Behind the update a one-block launch multiplies the lr of every live fit with
+ * lr > lr_floor by gamma, in fp64 (ExponentialLR while the rate is above the floor; gamma = 1: a constant rate). */
+typedef struct { double lr, gamma; float weight_decay, lr_floor; } mfvi_sibling_hyper;
+int mfvi_sibling_update_fits(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, int64_t param_stride,
+                             int64_t grad_stride, int n_fits, mfvi_sibling_hyper* hyper_dev, float beta1, float beta2, float eps, int t,
+                             const double* loss_acc, int32_t* dead, void* stream);
+/* SGLD's add_noise for every fit in one launch: x[j] = fma(std[f], N(0,1), x[j]) for j in [layer_off[l], layer_off[l] + layer_n[l]) of the
+ * row params + f * param_stride, l < n_layers (device tables of int64; the conv weights -- biases and BatchNorm parameters are not listed).
+ * RNG: domain 4, stream l, sample fit0 + f, step, element index inside the layer -- fit 0 with fit0 = 0 draws the numbers of
+ * mfvi_add_normal(x + layer_off[l], seed, l, step, layer_n[l], ...).  std[f], dead[f] in device memory; dead fits are skipped. */
+int mfvi_add_normal_fits(float* params, int64_t param_stride, int n_fits, uint32_t fit0, const int64_t* layer_off, const int64_t* layer_n,
+                         int n_layers, uint64_t seed, uint32_t step, const float* std, const int32_t* dead, void* stream);
 
 const char* mfvi_last_error(void);
 int mfvi_abi_version(void);

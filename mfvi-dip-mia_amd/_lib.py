@@ -41,6 +41,8 @@ SIGNATURES = {
     "mfvi_plan_bn_update_running": (_I, [_P, _P, _I, _F, _P, _P]),
     "mfvi_plan_set_bn_eval": (_I, [_P, _P]),
     "mfvi_plan_set_fits": (_I, [_P, _I, _I64, _I64]),
+    "mfvi_plan_set_fits_points": (_I, [_P, _I]),
+    "mfvi_plan_set_fit_dropout": (_I, [_P, _P, _I]),
     "mfvi_plan_set_side_stream": (_I, [_P, _I]),
     "mfvi_plan_set_step_source": (_I, [_P, _P]),
     "mfvi_plan_set_capture_mode": (_I, [_P, _I]),
@@ -112,6 +114,9 @@ SIGNATURES = {
     "mfvi_masked_sq_err_fits": (_I, [_P, _I64, _P, _I64, _P, _I64, _I, _I, _I, _I, _P, _P, _P]),
     "mfvi_radon_mse_fits_scratch_bytes": (_I64, [_I, _I, _I, _I]),
     "mfvi_radon_mse_fits": (_I, [_P, _P, _I64, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
+    "mfvi_mse_channel_fits": (_I, [_P, _P, _I64, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "mfvi_sibling_update_fits": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _F, _F, _F, _I, _P, _P, _P]),
+    "mfvi_add_normal_fits": (_I, [_P, _I64, _I, _U32, _P, _P, _I, _U64, _U32, _P, _P, _P]),
     "mfvi_last_error": (C.c_char_p, []),
     "mfvi_abi_version": (_I, []),
 }

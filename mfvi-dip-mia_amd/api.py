@@ -8,7 +8,7 @@ from . import runner
 from .nets import Concat, get_net, skip
 
 __all__ = ["build", "FitBatch", "Plan", "Program", "skip_program", "_lib", "engine", "sharding", "runner", "Concat", "get_net", "skip", "MeanFieldVI", "FusedNet", "Conv2dRT", "Conv2dLRT",
-           "gaussian_nll", "gaussian_nll_inpainting", "uncert_regression_gal", "uceloss", "Downsampler", "lanczos_taps", "FastRadonTransform", "CtVolume", "InpaintBatch"]
+           "gaussian_nll", "gaussian_nll_inpainting", "uncert_regression_gal", "uceloss", "Downsampler", "lanczos_taps", "FastRadonTransform", "CtVolume", "InpaintBatch", "SiblingBatch"]
 
 
 def __getattr__(name):          # bayes.py needs torch.nn at import: keep `import mfvi_dip_mia_amd` light
@@ -30,4 +30,7 @@ def __getattr__(name):          # bayes.py needs torch.nn at import: keep `impor
     if name == "InpaintBatch":
         from .inpaintbatch import InpaintBatch
         return InpaintBatch
+    if name == "SiblingBatch":
+        from .siblingbatch import SiblingBatch
+        return SiblingBatch
     raise AttributeError(name)

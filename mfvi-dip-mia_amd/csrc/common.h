@@ -534,7 +534,9 @@ int launch_concat_up_bwd(const GView& gc, const TView* a, float* ga_a, long long
                          const TView& b, float* ga_b, long long ga_b_sstride, double* bsums_b, int nearest, int n_samples, Launch& L);
 // Dropout2d factors of one forward: arena[e.drop_off + k*C + c] for every entry, sample k, channel c (RNG domain 5, stream layer_id)
 struct DropEntry { long long drop_off; int C, layer_id; float p; int pad; };
-int launch_dropout_masks(const DropEntry* table_dev, int n_entries, RngKey key, int n_samples, float* arena, hipStream_t st);
+// fit_p (fits mode, mfvi_plan_set_fit_dropout; device array): sample k draws with fit_p[k / fit_s] instead of the entry's p
+int launch_dropout_masks(const DropEntry* table_dev, int n_entries, RngKey key, int n_samples, float* arena, hipStream_t st,
+                         const float* fit_p = nullptr, int fit_s = 0);
 // nn.BatchNorm2d's running statistics after n_samples training forwards (batch sums in fstats), and their use in eval mode
 int launch_bn_update_running(const BnGradEntry* table_dev, int n_entries, int max_c, const double* fstats_base, int n_samples, float momentum,
                              float* running, hipStream_t st);

@@ -129,11 +129,13 @@ __global__ __launch_bounds__(256) void mse_channel_kernel(const float* __restric
 }
 
 // ---- Dropout2d masks (MC-dropout sibling) ----
-__global__ __launch_bounds__(64) void dropout_mask_kernel(const DropEntry* __restrict__ table, RngKey key, float* __restrict__ arena)
+__global__ __launch_bounds__(64) void dropout_mask_kernel(const DropEntry* __restrict__ table, RngKey key, float* __restrict__ arena,
+                                                          const float* __restrict__ fit_p, int fit_s)
 {
     key = key_now(key);
-    const DropEntry e = table[blockIdx.x];
+    DropEntry e = table[blockIdx.x];
     const int k = blockIdx.y;
+    if (fit_p) e.p = fit_p[k / fit_s];      // fits mode: the probability of the sample's fit (same counter, comparison and scale)
     key.stream = ((uint32_t)DOMAIN_DROPOUT << 24) | (uint32_t)e.layer_id;
     key.sample += (uint32_t)k;
     const float keep = 1.0f / (1.0f - e.p);
@@ -646,10 +648,10 @@ __global__ __launch_bounds__(256) void elbo_update_bf16_kernel(bf16_t* __restric
 
 }  // namespace
 
-int launch_dropout_masks(const DropEntry* table_dev, int n_entries, RngKey key, int n_samples, float* arena, hipStream_t st)
+int launch_dropout_masks(const DropEntry* table_dev, int n_entries, RngKey key, int n_samples, float* arena, hipStream_t st, const float* fit_p, int fit_s)
 {
     if (n_entries <= 0) return 0;
-    hipLaunchKernelGGL(dropout_mask_kernel, dim3(n_entries, n_samples), dim3(64), 0, st, table_dev, key, arena);
+    hipLaunchKernelGGL(dropout_mask_kernel, dim3(n_entries, n_samples), dim3(64), 0, st, table_dev, key, arena, fit_s > 0 ? fit_p : nullptr, fit_s);
     return (int)hipGetLastError();
 }
 

@@ -267,7 +267,7 @@ int pass_setup(PassSetup& S, bool expand, uint64_t seed, uint32_t step, uint32_t
     if (plan->fit_s) {
         // F = n_samples / fit_s fits in one pass: sample i is sample i % fit_s of fit i / fit_s and uses eps of global sample k0 + i
         if (int rc = fits_refusal(plan, S.who)) return rc;
-        if (!S.sample_weights) { set_error("%s: fits mode (mfvi_plan_set_fits) does not serve sample_weights = 0", S.who); return MFVI_ERR_FITS_UNSUPPORTED; }
+        if (!S.sample_weights && !plan->fit_points) { set_error("%s: fits mode (mfvi_plan_set_fits) does not serve sample_weights = 0", S.who); return MFVI_ERR_FITS_UNSUPPORTED; }
         if (S.n_samples % plan->fit_s) { set_error("%s: n_samples %d is not a multiple of the %d samples per fit", S.who, S.n_samples, plan->fit_s); return -1; }
         S.c.fit_s = plan->fit_s; S.c.gamma_fstride = plan->fit_pstride; S.c.z_sstride = plan->t[plan->input].numel;
         if (plan->fit_s > 1) {      // z[n_fits][Cin][H][W] once per sample
@@ -278,7 +278,11 @@ int pass_setup(PassSetup& S, bool expand, uint64_t seed, uint32_t step, uint32_t
         }
         // a layer the matrix-core kernels decline (a map not a multiple of 4 wide) runs on the generic kernels: fit 0's mu / rho plus the strides,
         // sample k reads and accumulates at fit k / fit_s (every layer is in the sampling table here: fits_refusal)
-        S.W = ConvWeights{S.c.wsamp(), plan->n_vi, S.mu, S.rho, S.key, 1, FitGeom{plan->fit_s, plan->fit_pstride, plan->fit_gstride}};
+        // points mode (sample_weights = 0 with mfvi_plan_set_fits_points): the same rows hold each sample's fit's mu, the generic kernels read w = mu
+        S.points = !S.sample_weights; S.presample = true;
+        if (!plan->fit_drop.empty() && plan->n_drop && (int)plan->fit_drop.size() != S.n_samples / plan->fit_s) {
+            set_error("%s: mfvi_plan_set_fit_dropout gave %d probabilities, this pass has %d fits", S.who, (int)plan->fit_drop.size(), S.n_samples / plan->fit_s); return -1; }
+        S.W = ConvWeights{S.c.wsamp(), plan->n_vi, S.mu, S.rho, S.key, S.sample_weights, FitGeom{plan->fit_s, plan->fit_pstride, plan->fit_gstride}};
     }
     return 0;
 }
@@ -305,7 +309,7 @@ template <typename E> int split_pieces(PassSetup& S, DeviceTable<E>& T, int pass
     if (tab.empty()) return 0;
     const hipError_t e = T.upload_if_changed(tab, plan->ops.size(), S.st);
     if (e != hipSuccess) { set_error("%s: weight-piece table setup failed: %s", S.who, hipGetErrorString(e)); return (int)e; }
-    const int rc = launch_split_all(T.dev, (int)tab.size(), nb, S.c.wsamp(), S.sample_weights ? plan->n_vi : 0, S.sample_weights ? S.n_samples : 1, S.c.farena(), S.st);
+    const int rc = launch_split_all(T.dev, (int)tab.size(), nb, S.c.wsamp(), S.slab_rows() ? plan->n_vi : 0, S.slab_rows() ? S.n_samples : 1, S.c.farena(), S.st);
     if (rc) set_error("%s: weight-piece launch failed: %s", S.who, hipGetErrorString((hipError_t)rc));
     S.x6_ready = rc == 0;
     return rc;
@@ -344,6 +348,7 @@ void mfvi_plan_destroy(mfvi_plan* plan)
     if (plan->x6b.dev) (void)hipFree(plan->x6b.dev);
     if (plan->samp_dev) (void)hipFree(plan->samp_dev);
     if (plan->drop_dev) (void)hipFree(plan->drop_dev);
+    if (plan->fit_drop_dev) (void)hipFree(plan->fit_drop_dev);
     for (auto e : plan->fork_events.ev) (void)hipEventDestroy(e);
     for (auto e : plan->fwd_events.ev) (void)hipEventDestroy(e);
     if (plan->join_event) (void)hipEventDestroy(plan->join_event);
@@ -409,6 +414,34 @@ int mfvi_plan_set_fits(mfvi_plan* plan, int samples_per_fit, int64_t param_strid
     for (auto& o : plan->ops)
         if (o.d.type == MFVI_OP_CONV) for (int& t : o.g.tune) if (t & MFVI_TUNE_GENERIC) t = 0;
     plan->fit_s = samples_per_fit; plan->fit_pstride = param_stride; plan->fit_gstride = grad_stride;
+    return 0;
+}
+
+int mfvi_plan_set_fits_points(mfvi_plan* plan, int enabled)
+{
+    if (!plan) { set_error("set_fits_points: null plan"); return -1; }
+    if (enabled) if (int rc = fits_refusal(plan, "set_fits_points")) return rc;
+    plan->fit_points = enabled != 0; plan->samp_n = 0;
+    return 0;
+}
+
+int mfvi_plan_set_fit_dropout(mfvi_plan* plan, const float* p, int n_fits)
+{
+    if (!plan) { set_error("set_fit_dropout: null plan"); return -1; }
+    if (!p || n_fits == 0) {
+        if (p) { set_error("set_fit_dropout: n_fits = 0 with a non-null array (NULL, 0 clears the per-fit probabilities)"); return -1; }
+        plan->fit_drop.clear(); return 0;
+    }
+    if (n_fits < 0 || n_fits > plan->max_samples) { set_error("set_fit_dropout: n_fits %d outside 1..%d", n_fits, plan->max_samples); return -1; }
+    for (int f = 0; f < n_fits; ++f)
+        if (!(p[f] >= 0.f && p[f] < 1.f)) { set_error("set_fit_dropout: fit %d: dropout probability %g outside [0, 1)", f, (double)p[f]); return -1; }
+    if (!plan->fit_drop_dev) {
+        const hipError_t e = hipMalloc((void**)&plan->fit_drop_dev, sizeof(float) * plan->max_samples);
+        if (e != hipSuccess) { plan->fit_drop_dev = nullptr; set_error("set_fit_dropout: hipMalloc failed: %s", hipGetErrorString(e)); return (int)e; }
+    }
+    const hipError_t e = hipMemcpy(plan->fit_drop_dev, p, sizeof(float) * n_fits, hipMemcpyHostToDevice);      // (synchronous: p is the caller's)
+    if (e != hipSuccess) { set_error("set_fit_dropout: copy failed: %s", hipGetErrorString(e)); return (int)e; }
+    plan->fit_drop.assign(p, p + n_fits);
     return 0;
 }
 

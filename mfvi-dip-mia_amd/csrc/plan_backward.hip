@@ -57,7 +57,7 @@ int begin_backward(Backward& B, void* workspace, uint64_t seed, uint32_t step, u
                       plan->samp_step == step && plan->samp_k0 == k0 && plan->samp_n == (S.sample_weights ? S.n_samples : -S.n_samples);
     if (S.presample && !held) {
         ProfScope ps(plan, -1, PASS_SAMPLE, st);
-        const int rc = launch_sample_weights(plan->samp_dev, plan->n_samp, plan->samp_blocks, S.mu_v, S.rho_v, S.key, S.sample_weights ? S.n_samples : 1, c.wsamp(),
+        const int rc = launch_sample_weights(plan->samp_dev, plan->n_samp, plan->samp_blocks, S.mu_v, S.rho_v, S.key, S.slab_rows() ? S.n_samples : 1, c.wsamp(),
                                              plan->n_vi, st, S.bf16, S.sample_weights, nullptr, 0, plan->fit_s, plan->fit_pstride);
         if (rc) { set_error("backward: sample_weights launch failed: %s", hipGetErrorString((hipError_t)rc)); return rc; }
     }

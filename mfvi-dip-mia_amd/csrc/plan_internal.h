@@ -109,13 +109,18 @@ struct mfvi_plan {
     // fits mode (mfvi_plan_set_fits): the samples of a call are n_samples / fit_s independent fits of fit_s samples each;
     // mu / rho / bn of fit j lie j * fit_pstride floats behind the pointers of the call, its gradients j * fit_gstride.  0: one fit (off)
     int fit_s = 0; long long fit_pstride = 0, fit_gstride = 0;
+    // fits mode with point weights (mfvi_plan_set_fits_points): a sample_weights = 0 pass writes every sample's slab row with
+    // its fit's mu and runs on those rows like a sampled pass.  Off (the default): fits mode refuses sample_weights = 0
+    bool fit_points = false;
+    // fits mode: Dropout2d probability per fit (mfvi_plan_set_fit_dropout); empty: every fit draws with the tensors' own drop_p
+    std::vector<float> fit_drop; float* fit_drop_dev = nullptr;
     long long zrep_off = -1;                   // floats: the net input once per SAMPLE [max_samples][Cin][H][W] (fit_s > 1: the kernels address it by sample)
     int n_lrt = 0;                             // local-reparameterisation layers
     long long sig2_off = -1, dsig2_off = -1;   // floats [n_vi] each: softplus(rho)^2 of this pass / gradient wrt it
     long long lrt_tmp_off = -1, lrt_tmp_n = 0; // floats: mean-convolution output (forward) / ds2 (backward) of the LRT layer in flight
     // identity of the draw currently held in the sampled-weight slab (set by forward, reused by the matching backward)
     const void* samp_mu = nullptr; const void* samp_rho = nullptr; const void* samp_ws = nullptr;
-    uint64_t samp_seed = 0; uint32_t samp_step = 0, samp_k0 = 0; int samp_n = 0;
+    uint64_t samp_seed = 0; uint32_t samp_step = 0, samp_k0 = 0; int samp_n = 0;      // samp_n: +n a draw for n samples, -n w = mu (one row; n rows in a points pass of fits mode)
     DropEntry* drop_dev = nullptr; int n_drop = 0; bool dropout_on = true;   // Dropout2d layers (MC-dropout sibling)
     // Backward-weight launches are off the critical path of the backward pass (only grad_finalize needs them): they run on a side
     // stream of the plan, forked per layer behind the event that marks "dy of this layer is final" and joined before grad_finalize,
@@ -253,6 +258,8 @@ struct PassSetup {
     // MFMA-served layers: every weight drawn once per (layer, sample) into the slab; without sampling the kernels read mu (stride 0)
     // (bf16 parameters: the slab also serves w = mu, as one float32 copy shared by all samples)
     bool presample = false;
+    bool points = false;        // fits mode, sample_weights = 0 (mfvi_plan_set_fits_points): the slab holds one row per sample, each its fit's mu
+    bool slab_rows() const { return sample_weights || points; }      // one slab row per sample (else one row, w = mu, shared by all samples)
     RngKey key; ConvWeights W;
     bool x6_ready = false;      // a pass-wide launch split the weight pieces of this pass's bf16x6 layers (split_weight_pieces)
 };

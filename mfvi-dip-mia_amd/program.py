@@ -180,6 +180,18 @@ class Plan:
             self.workspace_bytes = nb
             self.workspace = torch.empty(nb, dtype=torch.uint8, device="cuda")
 
+    def set_fits_points(self, enabled):
+        """mfvi_plan_set_fits_points: fits mode serves sample_weights=False (w = mu of the sample's fit: the DIP / MC-dropout / SGLD siblings)."""
+        L.check(L.lib().mfvi_plan_set_fits_points(self.handle, int(bool(enabled))))
+
+    def set_fit_dropout(self, p):
+        """mfvi_plan_set_fit_dropout: one Dropout2d probability per fit (a list of floats in [0, 1)); None clears it."""
+        if p is None:
+            L.check(L.lib().mfvi_plan_set_fit_dropout(self.handle, None, 0))
+            return
+        vals = [float(x) for x in p]
+        L.check(L.lib().mfvi_plan_set_fit_dropout(self.handle, (C.c_float * max(len(vals), 1))(*vals), len(vals)))
+
     def side_stream(self, enabled):
         """Backward-weight kernels on the plan's side stream (default) or on the caller's stream."""
         L.check(L.lib().mfvi_plan_set_side_stream(self.handle, int(bool(enabled))))

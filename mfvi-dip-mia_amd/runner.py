@@ -421,6 +421,7 @@ def _sibling(task, method, defaults):
         return _run(task, img, imsize, p_sigma if task == "den" else 0.0, num_iter, lr, 0.0, 0.0, input_depth, seed, show_every, plot, save, save_path, K,
                     method=method, **hyper, **kw)
     run.__name__ = "run_%s_%s" % (task, method)
+    run.defaults = dict(defaults)      # (run_sibling_batch fills a job's missing hyper-parameters from them)
     run.__doc__ = "bayesian_optimization.py run_%s_%s; returns the dict of results (['psnr'] is the reference's return value)." % (task, method)
     return run
 
@@ -651,6 +652,66 @@ def inpaint_batch_job(task, jobs, **kw):
     return run_inpaint_batch(jobs, **kw)["psnr"]
 
 
+def run_sibling_batch(task, method, jobs, imsize=None, p_sigma=0.1, num_iter=5000, lr=None, input_depth=None, seed=42, show_every=100, save=True,
+                      save_path="../logs", K=1, factor=4, net_kwargs=None, verbose=False, autotune=True, param_noise_sigma=2.0, **unused):
+    """The (image, candidate) jobs of one batch as ONE SiblingBatch (--sibling-fits): the loop of run_<task>_<method> for
+    every job at once.  jobs: dicts with img and, per method, dropout_p / weight_decay (mcd) or gamma / weight_decay (sgld), optionally lr;
+    what a job leaves out takes the default of run_<task>_<method>.  Writes batch.npz (hyper-parameters; per fit psnr_gt_sm and the data
+    term every show_every iterations, the final reconstruction, dead); save.npz, SGLD's iterate ring and the PNG artefacts stay with the
+    single-fit runners.  Returns dict(psnr=[per fit, NaN for a dead fit], ...)."""
+    import torch
+    from .siblingbatch import SiblingBatch
+    if task not in ("den", "sr") or method not in ("dip", "mcd", "sgld"):
+        raise NotImplementedError("--sibling-fits serves dip, mcd and sgld on denoising and super-resolution, not %r / %r" % (method, task))
+    dflt = globals()["run_%s_%s" % (task, method)].defaults
+    imsize = imsize or dflt.get("imsize", (256, 256))
+    lr = dflt.get("lr", 3e-4) if lr is None else lr
+    input_depth = dflt.get("input_depth", 16) if input_depth is None else input_depth
+    F = len(jobs)
+    imgs = [_load_image(j["img"], imsize, seed) for j in jobs]
+    H, W = imgs[0].shape
+    if any(im.shape != (H, W) for im in imgs):
+        raise ValueError("the images of one batch must share their size")
+    gt = np.stack(imgs)
+    if task == "den":      # every job's noise as the single-fit runner draws it (same image and seed: the same noisy image)
+        targets = np.stack([np.clip(im + np.random.default_rng(seed + 1).normal(scale=p_sigma, size=im.shape), 0, 1).astype(np.float32) for im in imgs])
+    else:
+        targets = np.ascontiguousarray(gt[:, ::factor, ::factor])
+    hyper = {k: [j.get(k, dflt.get(k, d)) for j in jobs] for k, d in (("weight_decay", 0.0), ("dropout_p", 0.3), ("gamma", 0.996))}
+    lrs = [j.get("lr", lr) for j in jobs]
+    sb = SiblingBatch(H, W, F, method, task=task, K=K, input_depth=input_depth, lr=lrs, seed=seed, sr_factor=factor, net_kwargs=net_kwargs,
+                      param_noise_sigma=param_noise_sigma, init="shared", autotune=autotune, **hyper)      # the reference's candidates all start from one seed
+    sb.set_targets(torch.from_numpy(targets))
+    n_it = num_iter + 1                                               # bayesian_optimization.py:1291
+    at, psnrs, losses = [], [], []
+    t0 = time.perf_counter()
+    for i in range(n_it):
+        sb.step()
+        if i % show_every == 0 or i == n_it - 1:
+            at.append(i); psnrs.append(sb.psnr(gt)); losses.append(sb.losses())
+            if verbose:
+                print("iter %6d  psnr_gt_sm %s  (%.1f it/s x %d fits)" % (i, np.array2string(psnrs[-1], precision=2), (i + 1) / (time.perf_counter() - t0), F))
+    dead = sb.dead
+    final = np.where(dead != 0, np.nan, psnrs[-1])
+    run_dir = None
+    if save:
+        run_dir = os.path.join(save_path, "%s_batch" % time.time())
+        os.makedirs(run_dir, exist_ok=False)
+        np.savez(os.path.join(run_dir, "batch.npz"), method=method, task=task, lr=np.asarray(lrs), weight_decay=np.asarray(sb.weight_decays),
+                 dropout_p=np.asarray(sb.dropout_ps), gamma=np.asarray(sb.gammas), K=np.int64(K), seed=np.int64(seed), num_iter=np.int64(num_iter),
+                 iterations=np.asarray(at), psnr_gt_sm=np.stack(psnrs), loss=np.stack(losses), recon=sb.recon().cpu().numpy(), dead=dead)
+    return dict(psnr=[float(x) for x in final], run_dir=run_dir, seconds=time.perf_counter() - t0, batch=sb, dead=dead)
+
+
+def sibling_batch_job(task, jobs, method="dip", **kw):
+    """One batch of sibling fits in a worker process of the fan-out -> the PSNR of every fit."""
+    return run_sibling_batch(task, method, jobs, **kw)["psnr"]
+
+
+def _sibling_batches(task, jobs, method="dip", **kw):
+    return run_sibling_batch(task, method, jobs, **kw)
+
+
 def _fit_batches(task, jobs, **kw):
     return run_fit_batch(task, jobs, **kw)
 
@@ -793,6 +854,9 @@ def main(argv=None):
     ap.add_argument("--inpaint-fits", type=int, default=0, help="> 0 (--task inpainting --bayes mfvi): the independent (image, candidate) fits run in "
                                                                 "batches of up to N as ONE set of launches per iteration (InpaintBatch); writes "
                                                                 "batch.npz per batch instead of save.npz per fit")
+    ap.add_argument("--sibling-fits", type=int, default=0, help="> 0 (--bayes dip, mcd or sgld; denoising / super-resolution): the independent (image, "
+                                                                "candidate) fits run in batches of up to N as ONE set of launches per iteration "
+                                                                "(SiblingBatch); writes batch.npz per batch instead of save.npz per fit")
     ap.add_argument("--ct-volume", default=None, help="--task ct --bayes mfvi: a .npy file holding a stack [D, S, S], or phantom:D; the slices are "
                                                          "fitted as ONE CtVolume per candidate (one set of launches per group of slices) and "
                                                          "volume.npz is written instead of save.npz per slice")
@@ -807,6 +871,19 @@ def main(argv=None):
             ap.error("--sr-downsampler %s belongs to --task super-resolution --bayes mfvi" % a.sr_downsampler)
         if a.fits_per_launch:
             ap.error("--sr-downsampler %s does not combine with --fits-per-launch (batched fits project with [::f, ::f])" % a.sr_downsampler)
+    if a.sibling_fits < 0:
+        ap.error("--sibling-fits %d: 0 (off) or the number of fits per launch" % a.sibling_fits)
+    if a.sibling_fits:      # refused before anything loads the library, and ahead of the other batching flags' own refusals
+        if a.bayes == "mfvi":
+            ap.error("--sibling-fits batches the DIP, MC-dropout and SGLD fits (--bayes dip, mcd or sgld); mean-field VI fits batch with --fits-per-launch")
+        if a.task not in ("denoising", "super-resolution"):
+            ap.error("--sibling-fits serves denoising and super-resolution, not %s" % a.task)
+        for flag, on in (("--fits-per-launch", a.fits_per_launch), ("--inpaint-fits", a.inpaint_fits), ("--ct-volume", a.ct_volume is not None),
+                         ("--predict-samples", a.predict_samples), ("--calibration", a.calibration)):
+            if on:
+                ap.error("--sibling-fits does not combine with %s (SiblingBatch.to_engine(f) serves one fit of a batch)" % flag)
+        if a.param_dtype != "f32":
+            ap.error("--sibling-fits takes float32 parameters (--param-dtype f32)")
     if a.inpaint_fits < 0:
         ap.error("--inpaint-fits %d: 0 (off) or the number of fits per launch" % a.inpaint_fits)
     if a.inpaint_fits:      # refused before anything loads the library, and ahead of the other batching flags' own refusals
@@ -894,6 +971,9 @@ def main(argv=None):
     jobs = [dict(cand, img=im) for im in imgs for cand in cands]
     devices = a.devices.split(",") if a.devices else cfg_devices
     batch_kw = dict(batch_fn=_inpaint_batches, worker="mfvi_dip_mia_amd.runner:inpaint_batch_job") if a.inpaint_fits else {}
+    if a.sibling_fits:      # the method rides in the run parameters to the batch function (here, or in a worker of the fan-out)
+        batch_kw = dict(batch_fn=_sibling_batches, worker="mfvi_dip_mia_amd.runner:sibling_batch_job")
+        rp["method"] = a.bayes
     if a.bo_rounds > 0:
         # bo() of the reference (bayesian_optimization.py:3727-3880): rounds of [fits of the candidates over the devices -> GP -> new candidates]
         from . import bo as _bo
@@ -904,8 +984,8 @@ def main(argv=None):
 
         def evaluate(cand_list):
             jb = [dict(zip(keys, c), img=imgs[0]) for c in cand_list]
-            if a.fits_per_launch or a.inpaint_fits:      # a round's candidates form batches
-                res, _, _ = _run_batches(short, jb, a.fits_per_launch or a.inpaint_fits, rp, a.k, devices, **batch_kw)
+            if a.fits_per_launch or a.inpaint_fits or a.sibling_fits:      # a round's candidates form batches
+                res, _, _ = _run_batches(short, jb, a.fits_per_launch or a.inpaint_fits or a.sibling_fits, rp, a.k, devices, **batch_kw)
                 return [(tuple(job[k] for k in keys), y) for _, job, y in res]
             if devices:
                 from .fanout import run_jobs
@@ -913,9 +993,9 @@ def main(argv=None):
                 return [(tuple(job[k] for k in keys), y) for _, job, y in res]
             return [(c, fn(K=a.k, verbose=False, **j, **rp)["psnr"]) for c, j in zip(cand_list, jb)]
         return _bo.bo(bo_params, evaluate, n_rounds=a.bo_rounds)
-    if a.fits_per_launch or a.inpaint_fits:
+    if a.fits_per_launch or a.inpaint_fits or a.sibling_fits:
         from .fanout import print_table
-        per = a.fits_per_launch or a.inpaint_fits
+        per = a.fits_per_launch or a.inpaint_fits or a.sibling_fits
         results, dropped, batches = _run_batches(short, jobs, per, rp, a.k, devices, verbose=True, **batch_kw)
         print("%d fits in %d batches of up to %d" % (len(jobs), len(batches), per))
         print_table(results, list(BO_KEYS[a.bayes]))
