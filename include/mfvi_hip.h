@@ -159,7 +159,7 @@ int mfvi_plan_set_bn_eval(mfvi_plan* plan, const float* running);
 int mfvi_plan_set_param_dtype(mfvi_plan* plan, int dtype);
 /* Fits mode: one call of mfvi_forward / mfvi_backward advances MANY independent fits.  With S = samples_per_fit > 0
  * the n_samples of a call (a multiple of S) are n_samples / S fits of S samples each: sample i belongs to fit i / S and still uses eps of
- * global sample index k0 + i (the RNG is unchanged).  mu / rho / bn point at fit 0, fit j's blocks lie j * param_stride floats further on
+ * global sample index k0 + i (the RNG is unchanged; mfvi_plan_set_fits_sample_stride below changes the index).  mu / rho / bn point at fit 0, fit j's blocks lie j * param_stride floats further on
  * (one flat row [MU | RHO | BN] per fit works with a single stride); dmu / drho / dbn
  * likewise with grad_stride.  z is [n_fits][Cin][H][W], one input per fit; out / dout / dz stay [n_samples][C][H][W].  Every weight gradient is
  * summed over the samples of its fit only; on the matrix-core kernels in a fixed order, no atomics.  A layer those decline (a map not a
@@ -183,6 +183,12 @@ int mfvi_plan_set_fits_points(mfvi_plan* plan, int enabled);
  * the tensor's gets bit-identical masks; p = 0 gives factors of 1.  p: HOST array of n_fits values in [0, 1) (copied); NULL or n_fits = 0
  * clears it.  A fits-mode pass whose n_samples / S differs from n_fits is refused before any launch. */
 int mfvi_plan_set_fit_dropout(mfvi_plan* plan, const float* p, int n_fits);
+/* The eps / Dropout2d sample index of a fit (fits mode): afterwards sample i of a pass (fit j = i / S, draw s = i % S) uses
+ * global sample k0 + j * stride + s.  The default, restored by every mfvi_plan_set_fits call, is stride = S: k0 + i, as described above.
+ * stride = 0 makes every fit draw the samples k0 .. k0 + S - 1, the indices a single-fit plan uses for the same call -- what a batched
+ * posterior prediction needs to reproduce each fit's stand-alone draws.  -1 (and a message) for a negative stride or a plan outside fits
+ * mode.  Forward only: mfvi_backward on a plan whose stride differs from S is refused with MFVI_ERR_FITS_UNSUPPORTED before any launch. */
+int mfvi_plan_set_fits_sample_stride(mfvi_plan* plan, int64_t stride);
 /* bytes of caller-provided device workspace (activations, gradients, BN statistics) for max_samples */
 int64_t mfvi_plan_workspace_bytes(const mfvi_plan* plan);
 
@@ -420,6 +426,24 @@ int mfvi_predictive_accumulate(const float* out, int n, int C, int H, int W, int
  * order (per-block partials in the accumulator's tail, then one block): deterministic. */
 int mfvi_predictive_finalize(double* acc, int n_total, int C, int H, int W, int mode, const float* ref, float* mean, float* epi, float* ale,
                              float* total, float* err2, float* mse_mc, double* sums, void* stream);
+
+/* The same statistics for MANY fits in one set of launches: the fit is a grid dimension, each fit's accumulator is a row
+ * of acc_stride doubles.  Per fit the maps and sum ale / sum epi / sum total are bit-equal to the single-fit entry points run on that fit's
+ * slice of out.  No atomics; bit-identical from call to call.  n_fits and n_fits * S must be below 65536.
+ * Length in doubles of ONE fit's accumulator row: the state part first, laid out as mfvi_predictive_acc_doubles describes, then the finalize
+ * partials (4 per block); -1 for an invalid (C, mode).  acc_stride may be larger; nothing is written between the rows. */
+int64_t mfvi_predictive_acc_doubles_fits(int C, int H, int W, int mode);
+/* out[n_fits * S][C][H][W] as a fits-mode mfvi_forward writes it: fit f folds its samples f*S .. f*S + n_use - 1 (1 <= n_use <= S; a partial
+ * last chunk leaves the rest unread) into acc + f * acc_stride; first as in mfvi_predictive_accumulate.  One launch whatever n_fits is. */
+int mfvi_predictive_accumulate_fits(const float* out, int n_fits, int S, int n_use, int C, int H, int W, int mode, int clip, int first,
+                                    double* acc, int64_t acc_stride, void* stream);
+/* ref: NULL, or [Cimg][H][W] per fit, ref_stride floats from one fit's to the next (0: one ground truth shared by all fits).
+ * mean [n_fits][Cimg][H][W]; epi, ale (NULL in MEAN_ONLY), total, err2, mse_mc (either may be NULL) [n_fits][H][W].  sums: [n_fits][4] device
+ * doubles, overwritten with sum ale, sum epi, sum total, sum err2 (of the fp32 values of the maps; the last is 0 without ref), through
+ * per-block partials and then one block per fit in block order.  Two launches whatever n_fits is. */
+int mfvi_predictive_finalize_fits(double* acc, int64_t acc_stride, int n_fits, int n_total, int C, int H, int W, int mode, const float* ref,
+                                  int64_t ref_stride, float* mean, float* epi, float* ale, float* total, float* err2, float* mse_mc, double* sums,
+                                  void* stream);
 
 /* ---- uncertainty calibration (utils/uce.py uceloss, the evaluation notebooks' "UCE" cells) ------------------ */
 /* Bin k of the n_bins bins given by the n_bins + 1 device floats bounds[] (used as given, non-decreasing) holds the elements with

@@ -43,6 +43,7 @@ SIGNATURES = {
     "mfvi_plan_set_fits": (_I, [_P, _I, _I64, _I64]),
     "mfvi_plan_set_fits_points": (_I, [_P, _I]),
     "mfvi_plan_set_fit_dropout": (_I, [_P, _P, _I]),
+    "mfvi_plan_set_fits_sample_stride": (_I, [_P, _I64]),
     "mfvi_plan_set_side_stream": (_I, [_P, _I]),
     "mfvi_plan_set_step_source": (_I, [_P, _P]),
     "mfvi_plan_set_capture_mode": (_I, [_P, _I]),
@@ -99,6 +100,9 @@ SIGNATURES = {
     "mfvi_predictive_acc_doubles": (_I64, [_I, _I, _I, _I]),
     "mfvi_predictive_accumulate": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "mfvi_predictive_finalize": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfvi_predictive_acc_doubles_fits": (_I64, [_I, _I, _I, _I]),
+    "mfvi_predictive_accumulate_fits": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I64, _P]),
+    "mfvi_predictive_finalize_fits": (_I, [_P, _I64, _I, _I, _I, _I, _I, _I, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfvi_uce_scratch_bytes": (_I64, [_I64, _I]),
     "mfvi_uce_minmax": (_I, [_P, _I64, _P, _P, _P]),
     "mfvi_uce_bins": (_I, [_P, _P, _I64, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),

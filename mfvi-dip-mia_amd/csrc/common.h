@@ -387,7 +387,11 @@ void set_error(const char* fmt, ...);
 
 // Fit geometry of the generic kernels (fits mode, mfvi_plan_set_fits): sample k belongs to fit k / fit_s, reads mu / rho pstride floats per fit
 // further on and accumulates into dmu / drho gstride floats per fit further on.  fit_s = 0: one fit, every offset is 0
-struct FitGeom { int fit_s = 0; long long pstride = 0, gstride = 0; };
+struct FitGeom { int fit_s = 0; long long pstride = 0, gstride = 0; uint32_t kdelta = 0; };      // kdelta: fit_sample_index
+// The eps / dropout sample index of pass sample k, relative to the pass's k0.  Fits mode with a sample stride (mfvi_plan_set_fits_sample_stride):
+// sample k is draw k % fit_s of fit k / fit_s and uses global sample k0 + (k / fit_s) * stride + k % fit_s = k0 + k + (k / fit_s) * kdelta with
+// kdelta = stride - fit_s, modulo 2^32 like the counter word itself.  kdelta = 0 (the default stride fit_s) and fit_s = 0 (one fit) give k.
+__device__ __forceinline__ uint32_t fit_sample_index(int k, int fit_s, uint32_t kdelta) { return (uint32_t)k + (fit_s ? (uint32_t)(k / fit_s) * kdelta : 0u); }
 __device__ __forceinline__ long long fit_param_off(const FitGeom& f, int k) { return f.fit_s ? (long long)(k / f.fit_s) * f.pstride : 0; }
 __device__ __forceinline__ long long fit_grad_off(const FitGeom& f, int k) { return f.fit_s ? (long long)(k / f.fit_s) * f.gstride : 0; }
 int launch_conv_fwd(const TView& in, const ConvGeom& g, const float* mu, const float* rho, RngKey key, int sample_weights,
@@ -481,7 +485,8 @@ struct SampleEntry { long long w_off, b_off; int n_w, n_b, layer_id, first_block
 // bf16: mu / rho point to bf16_t arrays; sample = 0 writes W = mu (RTLayer's eval branch) — callers then launch it for ONE sample
 int launch_sample_weights(const SampleEntry* table_dev, int n_entries, int n_blocks, const void* mu, const void* rho, RngKey key,
                           int n_samples, float* wsamp, long long wstride, hipStream_t st, int bf16 = 0, int sample = 1, double* zero = nullptr, long long n_zero = 0,      // zero: n_zero doubles cleared by the same launch
-                          int fit_s = 0, long long param_fstride = 0);      // fits mode: sample k draws from mu / rho + (k / fit_s) * param_fstride
+                          int fit_s = 0, long long param_fstride = 0,      // fits mode: sample k draws from mu / rho + (k / fit_s) * param_fstride
+                          uint32_t fit_kdelta = 0);                        // with eps of sample k0 + fit_sample_index(k, fit_s, fit_kdelta)
 // bf16 -> float32 expansion (the generic fp32 kernels of shapes the MFMA path does not serve read float32 mu / rho)
 int launch_expand_bf16(const void* src, long long n, float* dst, hipStream_t st);
 constexpr int SAMPLE_QUADS = 256;       // weight quads per block of the sampling kernel
@@ -536,7 +541,7 @@ int launch_concat_up_bwd(const GView& gc, const TView* a, float* ga_a, long long
 struct DropEntry { long long drop_off; int C, layer_id; float p; int pad; };
 // fit_p (fits mode, mfvi_plan_set_fit_dropout; device array): sample k draws with fit_p[k / fit_s] instead of the entry's p
 int launch_dropout_masks(const DropEntry* table_dev, int n_entries, RngKey key, int n_samples, float* arena, hipStream_t st,
-                         const float* fit_p = nullptr, int fit_s = 0);
+                         const float* fit_p = nullptr, int fit_s = 0, uint32_t fit_kdelta = 0);      // fit_kdelta: as launch_sample_weights
 // nn.BatchNorm2d's running statistics after n_samples training forwards (batch sums in fstats), and their use in eval mode
 int launch_bn_update_running(const BnGradEntry* table_dev, int n_entries, int max_c, const double* fstats_base, int n_samples, float momentum,
                              float* running, hipStream_t st);

@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(TView in, ConvGeom g, con
     const int H = g.H, W = g.W, Cin = g.Cin, Cout = g.Cout;
     { const long long fo = fit_param_off(fit, k); mu += fo; rho += fo; }      // the sample's fit: uniform per block
 
-    RngKey kw = key; kw.sample += (uint32_t)k; kw.stream = ((uint32_t)DOMAIN_EPS << 24) | (uint32_t)(2 * g.layer_id);
+    RngKey kw = key; kw.sample += fit_sample_index(k, fit.fit_s, fit.kdelta); kw.stream = ((uint32_t)DOMAIN_EPS << 24) | (uint32_t)(2 * g.layer_id);
     RngKey kb = kw; kb.stream += 1u;
 
     for (int c = t; c < Cin; c += 256) s_ch[c] = chan_fwd(in, k, c);

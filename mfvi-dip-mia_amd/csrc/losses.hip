@@ -130,14 +130,14 @@ __global__ __launch_bounds__(256) void mse_channel_kernel(const float* __restric
 
 // ---- Dropout2d masks (MC-dropout sibling) ----
 __global__ __launch_bounds__(64) void dropout_mask_kernel(const DropEntry* __restrict__ table, RngKey key, float* __restrict__ arena,
-                                                          const float* __restrict__ fit_p, int fit_s)
+                                                          const float* __restrict__ fit_p, int fit_s, uint32_t fit_kdelta)
 {
     key = key_now(key);
     DropEntry e = table[blockIdx.x];
     const int k = blockIdx.y;
     if (fit_p) e.p = fit_p[k / fit_s];      // fits mode: the probability of the sample's fit (same counter, comparison and scale)
     key.stream = ((uint32_t)DOMAIN_DROPOUT << 24) | (uint32_t)e.layer_id;
-    key.sample += (uint32_t)k;
+    key.sample += fit_sample_index(k, fit_s, fit_kdelta);
     const float keep = 1.0f / (1.0f - e.p);
     float* __restrict__ d = arena + e.drop_off + (long long)k * e.C;
     for (int blk = threadIdx.x; blk * 4 < e.C; blk += 64) {
@@ -534,7 +534,8 @@ template <bool BF16>
 __global__ __launch_bounds__(256) void sample_weights_kernel(const SampleEntry* __restrict__ table, int n_entries,
                                                              const void* __restrict__ mu_v, const void* __restrict__ rho_v,
                                                              RngKey key, float* __restrict__ wsamp, long long wstride, int sample,
-                                                             double* __restrict__ zero, long long n_zero, int n_k, int fit_s, long long param_fstride)
+                                                             double* __restrict__ zero, long long n_zero, int n_k, int fit_s, long long param_fstride,
+                                                             uint32_t fit_kdelta)
 {
     key = key_now(key);
     // the pass's statistics buffers, cleared by the draw's own threads (plan_forward.hip, begin_forward)
@@ -565,7 +566,7 @@ __global__ __launch_bounds__(256) void sample_weights_kernel(const SampleEntry* 
                 else { m = *reinterpret_cast<const float4*>(mu + jf); r = *reinterpret_cast<const float4*>(rho + jf); }
                 if (sample) { sp[0] = softplus_fast(r.x); sp[1] = softplus_fast(r.y); sp[2] = softplus_fast(r.z); sp[3] = softplus_fast(r.w); }
             }
-            RngKey kw = key; kw.sample += (uint32_t)k;
+            RngKey kw = key; kw.sample += fit_sample_index(k, fit_s, fit_kdelta);
             kw.stream = ((uint32_t)DOMAIN_EPS << 24) | (uint32_t)(2 * e.layer_id);
             float z[4] = {0.f, 0.f, 0.f, 0.f};
             if (sample) spec_normal4(kw, (uint32_t)item, z);
@@ -576,7 +577,7 @@ __global__ __launch_bounds__(256) void sample_weights_kernel(const SampleEntry* 
     } else {
         const int q = item - nq_w;
         for (int k = k0; k < k1; ++k) {
-            RngKey kw = key; kw.sample += (uint32_t)k;
+            RngKey kw = key; kw.sample += fit_sample_index(k, fit_s, fit_kdelta);
             kw.stream = ((uint32_t)DOMAIN_EPS << 24) | (uint32_t)(2 * e.layer_id + 1);
             float z[4] = {0.f, 0.f, 0.f, 0.f};
             if (sample) spec_normal4(kw, (uint32_t)q, z);
@@ -648,21 +649,22 @@ __global__ __launch_bounds__(256) void elbo_update_bf16_kernel(bf16_t* __restric
 
 }  // namespace
 
-int launch_dropout_masks(const DropEntry* table_dev, int n_entries, RngKey key, int n_samples, float* arena, hipStream_t st, const float* fit_p, int fit_s)
+int launch_dropout_masks(const DropEntry* table_dev, int n_entries, RngKey key, int n_samples, float* arena, hipStream_t st, const float* fit_p, int fit_s,
+                         uint32_t fit_kdelta)
 {
     if (n_entries <= 0) return 0;
-    hipLaunchKernelGGL(dropout_mask_kernel, dim3(n_entries, n_samples), dim3(64), 0, st, table_dev, key, arena, fit_s > 0 ? fit_p : nullptr, fit_s);
+    hipLaunchKernelGGL(dropout_mask_kernel, dim3(n_entries, n_samples), dim3(64), 0, st, table_dev, key, arena, fit_s > 0 ? fit_p : nullptr, fit_s, fit_kdelta);
     return (int)hipGetLastError();
 }
 
 int launch_sample_weights(const SampleEntry* table_dev, int n_entries, int n_blocks, const void* mu, const void* rho, RngKey key,
                           int n_samples, float* wsamp, long long wstride, hipStream_t st, int bf16, int sample, double* zero, long long n_zero,
-                          int fit_s, long long param_fstride)
+                          int fit_s, long long param_fstride, uint32_t fit_kdelta)
 {
     if (n_entries < 1 || n_blocks < 1) { if (n_zero > 0) return (int)hipMemsetAsync(zero, 0, sizeof(double) * n_zero, st); return 0; }
     const dim3 grid(n_blocks, (n_samples + SAMPLE_KPT - 1) / SAMPLE_KPT);
-    if (bf16) hipLaunchKernelGGL(sample_weights_kernel<true>, grid, dim3(256), 0, st, table_dev, n_entries, mu, rho, key, wsamp, wstride, sample, zero, n_zero, n_samples, fit_s, param_fstride);
-    else hipLaunchKernelGGL(sample_weights_kernel<false>, grid, dim3(256), 0, st, table_dev, n_entries, mu, rho, key, wsamp, wstride, sample, zero, n_zero, n_samples, fit_s, param_fstride);
+    if (bf16) hipLaunchKernelGGL(sample_weights_kernel<true>, grid, dim3(256), 0, st, table_dev, n_entries, mu, rho, key, wsamp, wstride, sample, zero, n_zero, n_samples, fit_s, param_fstride, fit_kdelta);
+    else hipLaunchKernelGGL(sample_weights_kernel<false>, grid, dim3(256), 0, st, table_dev, n_entries, mu, rho, key, wsamp, wstride, sample, zero, n_zero, n_samples, fit_s, param_fstride, fit_kdelta);
     return (int)hipGetLastError();
 }
 

@@ -266,6 +266,7 @@ int pass_setup(PassSetup& S, bool expand, uint64_t seed, uint32_t step, uint32_t
     S.W = ConvWeights{S.presample ? S.c.wsamp() : S.mu, (S.presample && S.sample_weights) ? plan->n_vi : 0, S.mu, S.rho, S.key, S.sample_weights};
     if (plan->fit_s) {
         // F = n_samples / fit_s fits in one pass: sample i is sample i % fit_s of fit i / fit_s and uses eps of global sample k0 + i
+        // (k0 + (i / fit_s) * fit_kstride + i % fit_s after mfvi_plan_set_fits_sample_stride)
         if (int rc = fits_refusal(plan, S.who)) return rc;
         if (!S.sample_weights && !plan->fit_points) { set_error("%s: fits mode (mfvi_plan_set_fits) does not serve sample_weights = 0", S.who); return MFVI_ERR_FITS_UNSUPPORTED; }
         if (S.n_samples % plan->fit_s) { set_error("%s: n_samples %d is not a multiple of the %d samples per fit", S.who, S.n_samples, plan->fit_s); return -1; }
@@ -282,7 +283,7 @@ int pass_setup(PassSetup& S, bool expand, uint64_t seed, uint32_t step, uint32_t
         S.points = !S.sample_weights; S.presample = true;
         if (!plan->fit_drop.empty() && plan->n_drop && (int)plan->fit_drop.size() != S.n_samples / plan->fit_s) {
             set_error("%s: mfvi_plan_set_fit_dropout gave %d probabilities, this pass has %d fits", S.who, (int)plan->fit_drop.size(), S.n_samples / plan->fit_s); return -1; }
-        S.W = ConvWeights{S.c.wsamp(), plan->n_vi, S.mu, S.rho, S.key, S.sample_weights, FitGeom{plan->fit_s, plan->fit_pstride, plan->fit_gstride}};
+        S.W = ConvWeights{S.c.wsamp(), plan->n_vi, S.mu, S.rho, S.key, S.sample_weights, FitGeom{plan->fit_s, plan->fit_pstride, plan->fit_gstride, plan->fit_kdelta()}};
     }
     return 0;
 }
@@ -399,7 +400,7 @@ int mfvi_plan_set_fits(mfvi_plan* plan, int samples_per_fit, int64_t param_strid
 {
     if (!plan) { set_error("set_fits: null plan"); return -1; }
     plan->samp_n = 0;
-    if (samples_per_fit == 0) { plan->fit_s = 0; plan->fit_pstride = plan->fit_gstride = 0; return 0; }
+    if (samples_per_fit == 0) { plan->fit_s = 0; plan->fit_pstride = plan->fit_gstride = plan->fit_kstride = 0; return 0; }
     const long long n_params = 2 * plan->n_vi + plan->n_bn;
     if (samples_per_fit < 0 || samples_per_fit > plan->max_samples || param_stride < 0 || grad_stride < 0) {
         set_error("set_fits: samples_per_fit %d outside 0..%d, or a negative stride (%lld, %lld; %lld parameters per fit)",
@@ -414,6 +415,16 @@ int mfvi_plan_set_fits(mfvi_plan* plan, int samples_per_fit, int64_t param_strid
     for (auto& o : plan->ops)
         if (o.d.type == MFVI_OP_CONV) for (int& t : o.g.tune) if (t & MFVI_TUNE_GENERIC) t = 0;
     plan->fit_s = samples_per_fit; plan->fit_pstride = param_stride; plan->fit_gstride = grad_stride;
+    plan->fit_kstride = samples_per_fit;      // sample i draws eps of global sample k0 + i
+    return 0;
+}
+
+int mfvi_plan_set_fits_sample_stride(mfvi_plan* plan, int64_t stride)
+{
+    if (!plan) { set_error("set_fits_sample_stride: null plan"); return -1; }
+    if (!plan->fit_s) { set_error("set_fits_sample_stride: the plan is not in fits mode (call mfvi_plan_set_fits first; it also restores the default stride)"); return -1; }
+    if (stride < 0) { set_error("set_fits_sample_stride: negative stride %lld", (long long)stride); return -1; }
+    plan->fit_kstride = stride; plan->samp_n = 0;
     return 0;
 }
 

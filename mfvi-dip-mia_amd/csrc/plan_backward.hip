@@ -294,6 +294,11 @@ extern "C" int mfvi_backward(mfvi_plan* plan, const void* mu_v, const void* rho_
     if (!check_call(plan, n_samples, workspace)) return -1;
     if (!mu_v || !rho_v || !z || !dout || !dmu || !drho || (plan->n_bn > 0 && (!bn || !dbn))) { set_error("backward: null pointer argument"); return -1; }
     if (plan->bn_eval) { set_error("backward: BatchNorm is in eval mode (mfvi_plan_set_bn_eval); the kernels implement the training-mode backward only"); return -1; }
+    if (plan->fit_s && plan->fit_kstride != plan->fit_s) {      // (the gradient reduction re-derives eps of sample k0 + i)
+        set_error("backward: fits mode with a sample stride of %lld (mfvi_plan_set_fits_sample_stride) serves forward passes only; the default is the %d samples per fit",
+                  plan->fit_kstride, plan->fit_s);
+        return MFVI_ERR_FITS_UNSUPPORTED;
+    }
     hipStream_t st = (hipStream_t)stream;
     Backward B{PassSetup{plan, "backward", st, Ctx{*plan, (char*)workspace, bn, z, n_samples}, mu_v, rho_v, n_samples, sample_weights}, dout, dmu, drho, dbn, dz};
     int rc = pass_setup(B.S, true, seed, step, k0);

@@ -47,13 +47,14 @@ int begin_forward(Forward& F, void* workspace, uint64_t seed, uint32_t step, uin
         ProfScope ps(plan, -1, PASS_SAMPLE, st);
         const int rc = launch_sample_weights(plan->samp_dev, plan->n_samp, plan->samp_blocks, S.mu_v, S.rho_v, S.key, S.slab_rows() ? S.n_samples : 1, c.wsamp(),
                                              plan->n_vi, st, S.bf16, S.sample_weights, zero_in_draw ? c.fstats() : nullptr, zero_in_draw ? 2 * plan->stats_doubles : 0,
-                                             plan->fit_s, plan->fit_pstride);
+                                             plan->fit_s, plan->fit_pstride, plan->fit_kdelta());
         if (rc) { set_error("forward: sample_weights launch failed: %s", hipGetErrorString((hipError_t)rc)); return rc; }
         plan->samp_mu = S.mu_v; plan->samp_rho = S.rho_v; plan->samp_ws = workspace; plan->samp_seed = seed; plan->samp_step = step; plan->samp_k0 = k0;
         plan->samp_n = S.sample_weights ? S.n_samples : -S.n_samples;
     }
     if (plan->n_drop && plan->dropout_on) {      // Dropout2d factors of this pass; the backward reads them from the workspace
-        const int rc = launch_dropout_masks(plan->drop_dev, plan->n_drop, S.key, S.n_samples, c.farena(), st, plan->fit_s && !plan->fit_drop.empty() ? plan->fit_drop_dev : nullptr, plan->fit_s);
+        const int rc = launch_dropout_masks(plan->drop_dev, plan->n_drop, S.key, S.n_samples, c.farena(), st, plan->fit_s && !plan->fit_drop.empty() ? plan->fit_drop_dev : nullptr, plan->fit_s,
+                                            plan->fit_kdelta());
         if (rc) { set_error("forward: dropout mask launch failed: %s", hipGetErrorString((hipError_t)rc)); return rc; }
     }
     return split_weight_pieces(S, 0, nullptr);

@@ -109,6 +109,10 @@ struct mfvi_plan {
     // fits mode (mfvi_plan_set_fits): the samples of a call are n_samples / fit_s independent fits of fit_s samples each;
     // mu / rho / bn of fit j lie j * fit_pstride floats behind the pointers of the call, its gradients j * fit_gstride.  0: one fit (off)
     int fit_s = 0; long long fit_pstride = 0, fit_gstride = 0;
+    // fits mode: the eps / dropout sample index of fit j's draw s is k0 + j * fit_kstride + s (mfvi_plan_set_fits_sample_stride).
+    // mfvi_plan_set_fits puts it back to fit_s, which is k0 + i for sample i; any other value serves forward passes only
+    long long fit_kstride = 0;
+    uint32_t fit_kdelta() const { return (uint32_t)(fit_kstride - fit_s); }      // what the kernels add per fit (fit_sample_index)
     // fits mode with point weights (mfvi_plan_set_fits_points): a sample_weights = 0 pass writes every sample's slab row with
     // its fit's mu and runs on those rows like a sampled pass.  Off (the default): fits mode refuses sample_weights = 0
     bool fit_points = false;

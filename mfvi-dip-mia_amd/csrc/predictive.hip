@@ -43,10 +43,11 @@ __device__ __forceinline__ float pred_tr(float y, int tr, int clip)
 
 // grid (ceil(HW / (4 * 64)), Cimg + has_ale).  blockIdx.y < Cimg: image channel c -> sum m, sum m^2 of that channel; the last row: sum a.
 // Each thread owns 4 consecutive pixels of one plane.  VEC: 16-byte loads (HW % 4 == 0 and a 16-byte aligned chunk); otherwise scalar
-// loads of the same 4 pixels with a bounds check on the tail.
+// loads of the same 4 pixels with a bounds check on the tail.  The thread's work is one function for the single-fit kernel and the one with
+// the fit as grid z (as iter_ops.h serves fits.hip): the same arithmetic in the same order, so the two agree bit for bit.
 template <bool VEC>
-__global__ __launch_bounds__(PRED_ACC_THREADS) void pred_accumulate_kernel(const float* __restrict__ out, int n, int C, long long HW,
-                                                                           PredLayout lay, int clip, int first, double* __restrict__ acc)
+__device__ __forceinline__ void pred_accumulate_thread(const float* __restrict__ out, int n, int C, long long HW, const PredLayout& lay, int clip,
+                                                       int first, double* __restrict__ acc)
 {
     const long long p0 = ((long long)blockIdx.x * PRED_ACC_THREADS + threadIdx.x) * 4;
     if (p0 >= HW) return;
@@ -103,20 +104,36 @@ __global__ __launch_bounds__(PRED_ACC_THREADS) void pred_accumulate_kernel(const
     }
 }
 
+template <bool VEC>
+__global__ __launch_bounds__(PRED_ACC_THREADS) void pred_accumulate_kernel(const float* __restrict__ out, int n, int C, long long HW,
+                                                                           PredLayout lay, int clip, int first, double* __restrict__ acc)
+{
+    pred_accumulate_thread<VEC>(out, n, C, HW, lay, clip, first, acc);
+}
+
+// grid z = fit: fit f folds its first n_use samples out[f * S ..] into its own accumulator row
+template <bool VEC>
+__global__ __launch_bounds__(PRED_ACC_THREADS) void pred_accumulate_fits_kernel(const float* __restrict__ out, int S, int n_use, int C, long long HW,
+                                                                                PredLayout lay, int clip, int first, double* __restrict__ acc,
+                                                                                long long acc_stride)
+{
+    const long long f = blockIdx.z;
+    pred_accumulate_thread<VEC>(out + f * S * C * HW, n_use, C, HW, lay, clip, first, acc + f * acc_stride);
+}
+
 // per pixel: mean[c] = S/N, epi = mean_c max-clamped unbiased variance, ale = A/N, total = ale + epi, and with a ground truth
 // err2 = mean_c (mean[c] - g[c])^2, mse_mc = err2 + (N-1)/N * epi.  Per-block fp64 partials of sum ale / sum epi / sum total.
-__global__ __launch_bounds__(PRED_FIN_THREADS) void pred_finalize_kernel(const double* __restrict__ acc, int N, long long HW, PredLayout lay,
-                                                                         const float* __restrict__ ref, float* __restrict__ mean,
-                                                                         float* __restrict__ epi, float* __restrict__ ale,
-                                                                         float* __restrict__ total, float* __restrict__ err2,
-                                                                         float* __restrict__ mse_mc, double* __restrict__ partials)
+// The thread's pixels, shared by the single-fit kernel and the one with the fit as grid y; sa / se / st / sr: the thread's sums of the
+// stored ale / epi / total / err2 values.
+__device__ __forceinline__ void pred_finalize_thread(const double* __restrict__ acc, int N, long long HW, const PredLayout& lay,
+                                                     const float* __restrict__ ref, float* __restrict__ mean, float* __restrict__ epi,
+                                                     float* __restrict__ ale, float* __restrict__ total, float* __restrict__ err2,
+                                                     float* __restrict__ mse_mc, double& sa, double& se, double& st, double& sr)
 {
-    __shared__ double s_red[PRED_FIN_THREADS / 64];
     const double inv_n = 1.0 / N, inv_n1 = 1.0 / (N - 1);
     const double* __restrict__ S = acc;
     const double* __restrict__ Q = acc + (long long)lay.cimg * HW;
     const double* __restrict__ A = acc + 2LL * lay.cimg * HW;
-    double sa = 0, se = 0, st = 0;
     for (long long p = (long long)blockIdx.x * PRED_FIN_THREADS + threadIdx.x; p < HW; p += (long long)gridDim.x * PRED_FIN_THREADS) {
         double var = 0, e2 = 0;
         for (int c = 0; c < lay.cimg; ++c) {
@@ -144,24 +161,70 @@ __global__ __launch_bounds__(PRED_FIN_THREADS) void pred_finalize_kernel(const d
             const double e2m = e2 / lay.cimg;
             if (err2) err2[p] = (float)e2m;
             if (mse_mc) mse_mc[p] = (float)(e2m + (double)(N - 1) * inv_n * (double)epf);
+            sr += (float)e2m;
         }
     }
+}
+
+__global__ __launch_bounds__(PRED_FIN_THREADS) void pred_finalize_kernel(const double* __restrict__ acc, int N, long long HW, PredLayout lay,
+                                                                         const float* __restrict__ ref, float* __restrict__ mean,
+                                                                         float* __restrict__ epi, float* __restrict__ ale,
+                                                                         float* __restrict__ total, float* __restrict__ err2,
+                                                                         float* __restrict__ mse_mc, double* __restrict__ partials)
+{
+    __shared__ double s_red[PRED_FIN_THREADS / 64];
+    double sa = 0, se = 0, st = 0, sr = 0;
+    pred_finalize_thread(acc, N, HW, lay, ref, mean, epi, ale, total, err2, mse_mc, sa, se, st, sr);
     const double ba = block_sum_d(sa, s_red);
     const double be = block_sum_d(se, s_red);
     const double bt = block_sum_d(st, s_red);
     if (threadIdx.x == 0) { partials[3 * blockIdx.x] = ba; partials[3 * blockIdx.x + 1] = be; partials[3 * blockIdx.x + 2] = bt; }
 }
 
-// one block: sums[j] = sum over the finalize blocks of partials[3 b + j], strided per thread then one block sum (a fixed order)
-__global__ __launch_bounds__(PRED_FIN_THREADS) void pred_sums_kernel(const double* __restrict__ partials, int nb, double* __restrict__ sums)
+// grid (blocks, fit): fit f's maps from its accumulator row; its partials hold a fourth word per block, the sum of err2
+__global__ __launch_bounds__(PRED_FIN_THREADS) void pred_finalize_fits_kernel(double* acc, long long acc_stride, int N, long long HW,
+                                                                              PredLayout lay, const float* __restrict__ ref, long long ref_stride,
+                                                                              float* __restrict__ mean, float* __restrict__ epi,
+                                                                              float* __restrict__ ale, float* __restrict__ total,
+                                                                              float* __restrict__ err2, float* __restrict__ mse_mc, long long state)
 {
     __shared__ double s_red[PRED_FIN_THREADS / 64];
-    for (int j = 0; j < 3; ++j) {
+    const long long f = blockIdx.y;
+    double* __restrict__ partials = acc + f * acc_stride + state;      // behind the words the threads read
+    double sa = 0, se = 0, st = 0, sr = 0;
+    pred_finalize_thread(acc + f * acc_stride, N, HW, lay, ref ? ref + f * ref_stride : nullptr, mean + f * lay.cimg * HW, epi + f * HW,
+                         ale ? ale + f * HW : nullptr, total + f * HW, err2 ? err2 + f * HW : nullptr, mse_mc ? mse_mc + f * HW : nullptr, sa, se, st, sr);
+    const double ba = block_sum_d(sa, s_red);
+    const double be = block_sum_d(se, s_red);
+    const double bt = block_sum_d(st, s_red);
+    const double br = block_sum_d(sr, s_red);
+    if (threadIdx.x == 0) { partials[4 * blockIdx.x] = ba; partials[4 * blockIdx.x + 1] = be; partials[4 * blockIdx.x + 2] = bt; partials[4 * blockIdx.x + 3] = br; }
+}
+
+// one block: sums[j] = sum over the finalize blocks of partials[NS b + j], strided per thread then one block sum (a fixed order)
+template <int NS>
+__device__ __forceinline__ void pred_sums_block(const double* __restrict__ partials, int nb, double* __restrict__ sums, double* s_red)
+{
+    for (int j = 0; j < NS; ++j) {
         double v = 0;
-        for (int b = threadIdx.x; b < nb; b += PRED_FIN_THREADS) v += partials[3 * b + j];
+        for (int b = threadIdx.x; b < nb; b += PRED_FIN_THREADS) v += partials[NS * b + j];
         const double t = block_sum_d(v, s_red);
         if (threadIdx.x == 0) sums[j] = t;
     }
+}
+
+__global__ __launch_bounds__(PRED_FIN_THREADS) void pred_sums_kernel(const double* __restrict__ partials, int nb, double* __restrict__ sums)
+{
+    __shared__ double s_red[PRED_FIN_THREADS / 64];
+    pred_sums_block<3>(partials, nb, sums, s_red);
+}
+
+// one block per fit: sums[f][0..3] from that fit's partials
+__global__ __launch_bounds__(PRED_FIN_THREADS) void pred_sums_fits_kernel(const double* __restrict__ acc, long long acc_stride, long long state, int nb,
+                                                                          double* __restrict__ sums)
+{
+    __shared__ double s_red[PRED_FIN_THREADS / 64];
+    pred_sums_block<4>(acc + (long long)blockIdx.x * acc_stride + state, nb, sums + 4 * blockIdx.x, s_red);
 }
 
 inline int fin_blocks(long long HW)
@@ -213,6 +276,65 @@ int mfvi_predictive_finalize(double* acc, int n_total, int C, int H, int W, int 
                        lay.has_ale ? ale : nullptr, total, ref ? err2 : nullptr, ref ? mse_mc : nullptr, partials);
     hipError_t e = hipGetLastError(); if (e) return (int)e;
     hipLaunchKernelGGL(pred_sums_kernel, dim3(1), dim3(PRED_FIN_THREADS), 0, st, partials, nb, sums);
+    return (int)hipGetLastError();
+}
+
+int64_t mfvi_predictive_acc_doubles_fits(int C, int H, int W, int mode)
+{
+    PredLayout lay;
+    if (H < 1 || W < 1 || !pred_layout(C, mode, lay)) { set_error("predictive_acc_doubles_fits: C=%d mode=%d H=%d W=%d not valid", C, mode, H, W); return -1; }
+    const long long HW = (long long)H * W;
+    return (2LL * lay.cimg + lay.has_ale) * HW + 4LL * PRED_FIN_BLOCKS;
+}
+
+int mfvi_predictive_accumulate_fits(const float* out, int n_fits, int S, int n_use, int C, int H, int W, int mode, int clip, int first,
+                                    double* acc, int64_t acc_stride, void* stream)
+{
+    PredLayout lay;
+    if (!out || !acc || H < 1 || W < 1 || !pred_layout(C, mode, lay)) {
+        set_error("predictive_accumulate_fits: bad arguments (C=%d mode=%d H=%d W=%d)", C, mode, H, W); return -1;
+    }
+    if (n_fits < 1 || S < 1 || n_fits > 65535 || (long long)n_fits * S > 65535 || n_use < 1 || n_use > S) {
+        set_error("predictive_accumulate_fits: n_fits=%d, S=%d, n_use=%d: at least 1 each, n_fits and n_fits * S below 65536, n_use <= S", n_fits, S, n_use); return -1;
+    }
+    const long long HW = (long long)H * W;
+    if (acc_stride < (2LL * lay.cimg + lay.has_ale) * HW + 4LL * PRED_FIN_BLOCKS) {
+        set_error("predictive_accumulate_fits: acc_stride %lld below the %lld doubles of one fit (mfvi_predictive_acc_doubles_fits)", (long long)acc_stride,
+                  (2LL * lay.cimg + lay.has_ale) * HW + 4LL * PRED_FIN_BLOCKS); return -1;
+    }
+    const dim3 grid((unsigned)((HW + 4 * PRED_ACC_THREADS - 1) / (4 * PRED_ACC_THREADS)), (unsigned)(lay.cimg + lay.has_ale), (unsigned)n_fits);
+    // every fit's slice of out starts 16-byte aligned: out itself and the S * C * HW floats between two fits
+    const bool vec = (HW & 3) == 0 && ((uintptr_t)out & 15) == 0 && (((long long)S * C * HW) & 3) == 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (vec) hipLaunchKernelGGL(pred_accumulate_fits_kernel<true>, grid, dim3(PRED_ACC_THREADS), 0, st, out, S, n_use, C, HW, lay, clip, first, acc, (long long)acc_stride);
+    else hipLaunchKernelGGL(pred_accumulate_fits_kernel<false>, grid, dim3(PRED_ACC_THREADS), 0, st, out, S, n_use, C, HW, lay, clip, first, acc, (long long)acc_stride);
+    return (int)hipGetLastError();
+}
+
+int mfvi_predictive_finalize_fits(double* acc, int64_t acc_stride, int n_fits, int n_total, int C, int H, int W, int mode, const float* ref,
+                                  int64_t ref_stride, float* mean, float* epi, float* ale, float* total, float* err2, float* mse_mc, double* sums,
+                                  void* stream)
+{
+    PredLayout lay;
+    if (!acc || !mean || !epi || !total || !sums || H < 1 || W < 1 || !pred_layout(C, mode, lay) || (lay.has_ale && !ale)) {
+        set_error("predictive_finalize_fits: bad arguments (C=%d mode=%d H=%d W=%d)", C, mode, H, W); return -1;
+    }
+    if (n_fits < 1 || n_fits > 65535) { set_error("predictive_finalize_fits: n_fits %d outside 1..65535", n_fits); return -1; }
+    if (n_total < 2) { set_error("predictive_finalize_fits: %d samples; the unbiased variance needs at least 2", n_total); return -1; }
+    const long long HW = (long long)H * W, state = (2LL * lay.cimg + lay.has_ale) * HW;
+    if (acc_stride < state + 4LL * PRED_FIN_BLOCKS) {
+        set_error("predictive_finalize_fits: acc_stride %lld below the %lld doubles of one fit (mfvi_predictive_acc_doubles_fits)", (long long)acc_stride,
+                  state + 4LL * PRED_FIN_BLOCKS); return -1;
+    }
+    if (ref && ref_stride != 0 && ref_stride < lay.cimg * HW) {
+        set_error("predictive_finalize_fits: ref_stride %lld: 0 (one ground truth for all fits) or at least the %lld floats of one", (long long)ref_stride, lay.cimg * HW); return -1;
+    }
+    const int nb = fin_blocks(HW);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(pred_finalize_fits_kernel, dim3(nb, n_fits), dim3(PRED_FIN_THREADS), 0, st, acc, (long long)acc_stride, n_total, HW, lay, ref,
+                       (long long)ref_stride, mean, epi, lay.has_ale ? ale : nullptr, total, ref ? err2 : nullptr, ref ? mse_mc : nullptr, state);
+    hipError_t e = hipGetLastError(); if (e) return (int)e;
+    hipLaunchKernelGGL(pred_sums_fits_kernel, dim3(n_fits), dim3(PRED_FIN_THREADS), 0, st, acc, (long long)acc_stride, state, nb, sums);
     return (int)hipGetLastError();
 }
 

@@ -245,6 +245,12 @@ class CtVolume:
         with np.errstate(divide="ignore"):
             return 10.0 * np.log10(1.0 / mse)
 
+    def predict(self, n_samples, target=None, clip=False, step=None, chunk=None, fits_per_call=None, calibration=None):
+        """Posterior predictive maps of every slice at once (batchpredict.predict_fits): per slice what
+        to_engine(d).predict(n_samples, ...) returns, stacked, from one set of launches per chunk of draws instead of one chain per slice."""
+        from .batchpredict import predict_fits
+        return predict_fits(self, n_samples, target=target, clip=clip, step=step, chunk=chunk, fits_per_call=fits_per_call, calibration=calibration)
+
     def to_engine(self, d, autotune=False):
         """A CT ElboEngine holding copies of slice d's parameters, Adam moments, step count, input, angles and sinogram: predict() and
         calibration work on any slice of a volume.  (Continued alone it draws eps of the global samples 0 .. K - 1, not d * K ..)"""

@@ -226,6 +226,12 @@ class FitBatch:
         with np.errstate(divide="ignore"):
             return 10.0 * np.log10(1.0 / mse)
 
+    def predict(self, n_samples, target=None, clip=False, step=None, chunk=None, fits_per_call=None, calibration=None):
+        """Posterior predictive maps of every fit at once (batchpredict.predict_fits): per fit what
+        to_engine(f).predict(n_samples, ...) returns, stacked, from one set of launches per chunk of draws instead of one chain per fit."""
+        from .batchpredict import predict_fits
+        return predict_fits(self, n_samples, target=target, clip=clip, step=step, chunk=chunk, fits_per_call=fits_per_call, calibration=calibration)
+
     def to_engine(self, f, autotune=False):
         """An ElboEngine holding copies of fit f's parameters, Adam moments, step count, input and target: predict(), calibration and the
         single-fit runner then work on any fit of a batch.  (Continued alone it draws eps of the global samples 0 .. K - 1, not f * K ..)"""

@@ -192,6 +192,12 @@ class Plan:
         vals = [float(x) for x in p]
         L.check(L.lib().mfvi_plan_set_fit_dropout(self.handle, (C.c_float * max(len(vals), 1))(*vals), len(vals)))
 
+    def set_fits_sample_stride(self, stride):
+        """mfvi_plan_set_fits_sample_stride: sample i of a fits-mode pass (fit j = i // S, draw s = i % S) uses eps / dropout masks of global
+        sample k0 + j * stride + s.  The default (restored by set_fits) is S; 0 gives every fit the samples k0 .. k0 + S - 1 of a stand-alone
+        plan.  Forward only: backward refuses any stride but S."""
+        L.check(L.lib().mfvi_plan_set_fits_sample_stride(self.handle, int(stride)))
+
     def side_stream(self, enabled):
         """Backward-weight kernels on the plan's side stream (default) or on the caller's stream."""
         L.check(L.lib().mfvi_plan_set_side_stream(self.handle, int(bool(enabled))))

@@ -256,6 +256,33 @@ def _check_predict(method, predict_samples):
         raise ValueError("predict_samples=%d: at least 2 draws" % predict_samples)
 
 
+def _check_batch_predict(batch_predict_samples, batch_calibration_bins=0):
+    if batch_predict_samples and batch_predict_samples < 2:
+        raise ValueError("batch_predict_samples=%d: 0 (off) or at least 2 draws" % batch_predict_samples)
+    if batch_calibration_bins and not batch_predict_samples:
+        raise ValueError("batch_calibration_bins: the calibration of a batch is that of its posterior predictive maps (batch_predict_samples >= 2)")
+    if batch_calibration_bins and not 1 <= int(batch_calibration_bins) <= L.UCE_MAX_BINS:
+        raise ValueError("batch_calibration_bins=%r outside 1..%d" % (batch_calibration_bins, L.UCE_MAX_BINS))
+
+
+def _batch_predict(batch, n, gt, run_dir, calibration_bins=0):
+    """After the last iteration of a batch: batch.predict(n, target=gt) -> predictive_batch.npz beside batch.npz /
+    volume.npz (the maps stacked over the fits, psnr_mean, n, step, dead) and, with calibration_bins > 0, calibration_batch.npz (the pred_
+    block of calibration.npz for every fit, stacked along axis 0).  Returns the arrays of the first file."""
+    import torch
+    from . import calibration as Cb
+    r = batch.predict(n, target=torch.from_numpy(np.ascontiguousarray(gt, np.float32)),
+                      calibration=dict(n_bins=calibration_bins) if calibration_bins else None)
+    arrs = {k: r[k].cpu().numpy() for k in ("mean", "epi", "ale", "total", "err2", "mse_mc") if r[k] is not None}
+    arrs.update(psnr_mean=r["psnr_mean"], n=np.int64(r["n"]), step=np.int64(r["step"]), dead=r["dead"])
+    if run_dir is not None:
+        np.savez(os.path.join(run_dir, "predictive_batch.npz"), **arrs)
+        if calibration_bins:
+            blocks = [Cb.npz_block(c, "pred_") for c in r["calibration"]]
+            np.savez(os.path.join(run_dir, "calibration_batch.npz"), **{k: np.stack([b[k] for b in blocks]) for k in blocks[0]})
+    return arrs
+
+
 def _check_calibration(method, calibration, n_bins=15):
     if calibration and method not in CALIBRATION_METHODS:
         raise ValueError("calibration: the uncertainty calibration error needs uncertainty maps (mfvi, mcd, sgld), not %r" % (method,))
@@ -545,13 +572,16 @@ def load_config(path, bayes="mfvi", with_devices=False):
 
 
 def run_fit_batch(task, jobs, imsize=(256, 256), p_sigma=0.1, num_iter=5000, lr=3e-4, input_depth=16, seed=42, show_every=100, save=True,
-                  save_path="../logs", K=1, factor=4, net_kwargs=None, verbose=False, autotune=True, **unused):
+                  save_path="../logs", K=1, factor=4, net_kwargs=None, verbose=False, autotune=True, batch_predict_samples=0,
+                  batch_calibration_bins=0, **unused):
     """The (image, temp, sigma) jobs of one batch as ONE FitBatch (--fits-per-launch): the loop of run_den_mfvi /
     run_sr_mfvi for every job at once, every fit with the noise of its own RNG samples.  jobs: dicts with img, temp, sigma (and optionally
     lr).  Writes batch.npz (hyper-parameters; per fit psnr_gt_sm, nll and kl every show_every iterations, the final reconstruction, dead);
-    save.npz and the PNG artefacts stay with the single-fit runners.  Returns dict(psnr=[per fit, NaN for a dead fit], ...)."""
+    save.npz and the PNG artefacts stay with the single-fit runners.  batch_predict_samples >= 2: predictive_batch.npz (and with
+    batch_calibration_bins calibration_batch.npz) beside it (_batch_predict).  Returns dict(psnr=[per fit, NaN for a dead fit], ...)."""
     import torch
     from .fitbatch import FitBatch
+    _check_batch_predict(batch_predict_samples, batch_calibration_bins)
     if task not in ("den", "sr"):
         raise NotImplementedError("--fits-per-launch serves denoising and super-resolution, not %r" % (task,))
     if unused.get("downsampler", "nearest") != "nearest":
@@ -589,7 +619,8 @@ def run_fit_batch(task, jobs, imsize=(256, 256), p_sigma=0.1, num_iter=5000, lr=
         np.savez(os.path.join(run_dir, "batch.npz"), task=task, temp=np.asarray(temps), sigma=np.asarray(sigmas), lr=np.asarray(lrs),
                  prior_sigma=np.asarray(fb.prior_sigma), K=np.int64(K), seed=np.int64(seed), num_iter=np.int64(num_iter), iterations=np.asarray(at),
                  psnr_gt_sm=np.stack(psnrs), nll=np.stack(nlls), kl=np.stack(kls), recon=fb.recon().cpu().numpy(), dead=dead)
-    return dict(psnr=[float(x) for x in final], run_dir=run_dir, seconds=time.perf_counter() - t0, batch=fb, dead=dead)
+    pred = _batch_predict(fb, batch_predict_samples, gt, run_dir, batch_calibration_bins) if batch_predict_samples else None
+    return dict(psnr=[float(x) for x in final], run_dir=run_dir, seconds=time.perf_counter() - t0, batch=fb, dead=dead, predictive=pred)
 
 
 def fit_batch_job(task, jobs, **kw):
@@ -598,7 +629,7 @@ def fit_batch_job(task, jobs, **kw):
 
 
 def run_inpaint_batch(jobs, imsize=(256, 256), num_iter=5000, lr=2e-3, input_depth=32, seed=42, show_every=100, save=True, save_path="../logs",
-                      K=1, net_kwargs=None, verbose=False, autotune=True, mask=None, **unused):
+                      K=1, net_kwargs=None, verbose=False, autotune=True, mask=None, batch_predict_samples=0, batch_calibration_bins=0, **unused):
     """The (image, mask, temp, sigma) jobs of one batch as ONE InpaintBatch (--inpaint-fits): the loop of run_inp_mfvi for
     every job at once.  jobs: dicts with img ((3, H, W) array, or what run_inp_mfvi loads), temp, sigma and optionally mask ((1|3, H, W);
     absent: `mask`, the run_params' mask that run_inp_mfvi takes too, else that function's seeded scratch mask) and lr.
@@ -606,6 +637,7 @@ def run_inpaint_batch(jobs, imsize=(256, 256), num_iter=5000, lr=2e-3, input_dep
     ale [F, H, W]; save.npz and the PNG artefacts stay with the single-fit runner.  Returns dict(psnr=[per fit, NaN for a dead fit], ...)."""
     import torch
     from .inpaintbatch import InpaintBatch
+    _check_batch_predict(batch_predict_samples, batch_calibration_bins)
     F = len(jobs)
     imgs = [np.ascontiguousarray(j["img"], np.float32) if isinstance(j["img"], np.ndarray) else
             np.stack([_load_image(j["img"], imsize, seed + c) for c in range(3)]).astype(np.float32) for j in jobs]
@@ -644,7 +676,8 @@ def run_inpaint_batch(jobs, imsize=(256, 256), num_iter=5000, lr=2e-3, input_dep
                  prior_sigma=np.asarray(ib.prior_sigma), K=np.int64(K), seed=np.int64(seed), num_iter=np.int64(num_iter), iterations=np.asarray(at),
                  psnr_gt_sm=np.stack(psnrs), nll=np.stack(nlls), kl=np.stack(kls), recon=ib.recon().cpu().numpy(), dead=dead,
                  mask=ib.masks.cpu().numpy(), ale=ib.ale().cpu().numpy())
-    return dict(psnr=[float(x) for x in final], run_dir=run_dir, seconds=time.perf_counter() - t0, batch=ib, dead=dead)
+    pred = _batch_predict(ib, batch_predict_samples, gt, run_dir, batch_calibration_bins) if batch_predict_samples else None      # (as batch.npz)
+    return dict(psnr=[float(x) for x in final], run_dir=run_dir, seconds=time.perf_counter() - t0, batch=ib, dead=dead, predictive=pred)
 
 
 def inpaint_batch_job(task, jobs, **kw):
@@ -653,7 +686,8 @@ def inpaint_batch_job(task, jobs, **kw):
 
 
 def run_sibling_batch(task, method, jobs, imsize=None, p_sigma=0.1, num_iter=5000, lr=None, input_depth=None, seed=42, show_every=100, save=True,
-                      save_path="../logs", K=1, factor=4, net_kwargs=None, verbose=False, autotune=True, param_noise_sigma=2.0, **unused):
+                      save_path="../logs", K=1, factor=4, net_kwargs=None, verbose=False, autotune=True, param_noise_sigma=2.0,
+                      batch_predict_samples=0, batch_calibration_bins=0, **unused):
     """The (image, candidate) jobs of one batch as ONE SiblingBatch (--sibling-fits): the loop of run_<task>_<method> for
     every job at once.  jobs: dicts with img and, per method, dropout_p / weight_decay (mcd) or gamma / weight_decay (sgld), optionally lr;
     what a job leaves out takes the default of run_<task>_<method>.  Writes batch.npz (hyper-parameters; per fit psnr_gt_sm and the data
@@ -663,6 +697,9 @@ def run_sibling_batch(task, method, jobs, imsize=None, p_sigma=0.1, num_iter=500
     from .siblingbatch import SiblingBatch
     if task not in ("den", "sr") or method not in ("dip", "mcd", "sgld"):
         raise NotImplementedError("--sibling-fits serves dip, mcd and sgld on denoising and super-resolution, not %r / %r" % (method, task))
+    _check_batch_predict(batch_predict_samples, batch_calibration_bins)
+    if batch_predict_samples and method != "mcd":
+        raise ValueError("batch_predict_samples=%d: of the batched siblings only MC dropout (mcd) has a posterior to draw from, not %r" % (batch_predict_samples, method))
     dflt = globals()["run_%s_%s" % (task, method)].defaults
     imsize = imsize or dflt.get("imsize", (256, 256))
     lr = dflt.get("lr", 3e-4) if lr is None else lr
@@ -700,7 +737,8 @@ def run_sibling_batch(task, method, jobs, imsize=None, p_sigma=0.1, num_iter=500
         np.savez(os.path.join(run_dir, "batch.npz"), method=method, task=task, lr=np.asarray(lrs), weight_decay=np.asarray(sb.weight_decays),
                  dropout_p=np.asarray(sb.dropout_ps), gamma=np.asarray(sb.gammas), K=np.int64(K), seed=np.int64(seed), num_iter=np.int64(num_iter),
                  iterations=np.asarray(at), psnr_gt_sm=np.stack(psnrs), loss=np.stack(losses), recon=sb.recon().cpu().numpy(), dead=dead)
-    return dict(psnr=[float(x) for x in final], run_dir=run_dir, seconds=time.perf_counter() - t0, batch=sb, dead=dead)
+    pred = _batch_predict(sb, batch_predict_samples, gt, run_dir, batch_calibration_bins) if batch_predict_samples else None
+    return dict(psnr=[float(x) for x in final], run_dir=run_dir, seconds=time.perf_counter() - t0, batch=sb, dead=dead, predictive=pred)
 
 
 def sibling_batch_job(task, jobs, method="dip", **kw):
@@ -785,13 +823,15 @@ def _load_volume(volume, imsize, seed):
 
 
 def run_ct_volume(volume, temp, sigma, slices_per_launch=None, imsize=(256, 256), num_iter=5000, lr=3e-4, input_depth=16, seed=42, show_every=100,
-                  save=True, save_path="../logs", K=1, theta_step=4.0, net_kwargs=None, verbose=False, autotune=True, **unused):
+                  save=True, save_path="../logs", K=1, theta_step=4.0, net_kwargs=None, verbose=False, autotune=True, batch_predict_samples=0,
+                  batch_calibration_bins=0, **unused):
     """The loop of run_ct_mfvi (bayesian_optimization.py:442-648) for every slice of a stack at once, as ONE CtVolume (--ct-volume; DESIGN.md
     section 16).  volume: [D, S, S] array, .npy path or 'phantom:D'; temp / sigma / lr: scalars or one value per slice.  Writes volume.npz
     (angles, sinograms, hyper-parameters; per slice psnr_gt_sm, nll and kl every show_every iterations, the reconstruction, dead); the ring
     buffers, SSIM curves, save.npz and PNG artefacts stay with the single-fit runner.  Returns dict(psnr=[per slice, NaN for a dead one], ...)."""
     import torch
     from .ctvolume import CtVolume
+    _check_batch_predict(batch_predict_samples, batch_calibration_bins)
     gt = _load_volume(volume, imsize, seed)
     D, S = gt.shape[0], gt.shape[1]
     theta = np.arange(0, 180.0, theta_step, dtype=np.float32)         # :545
@@ -818,9 +858,10 @@ def run_ct_volume(volume, temp, sigma, slices_per_launch=None, imsize=(256, 256)
                  lr=np.asarray(vol.lrs), prior_sigma=np.asarray(vol.prior_sigma), K=np.int64(K), seed=np.int64(seed), num_iter=np.int64(num_iter),
                  slices_per_launch=np.int64(vol.F), iterations=np.asarray(at), psnr_gt_sm=np.stack(psnrs), nll=np.stack(nlls), kl=np.stack(kls),
                  recon=vol.recon().cpu().numpy(), dead=dead)
+    pred = _batch_predict(vol, batch_predict_samples, gt, run_dir, batch_calibration_bins) if batch_predict_samples else None
     live = final[dead == 0]
     return dict(psnr=[float(x) for x in final], mean_psnr=float(live.mean()) if live.size else float("nan"), run_dir=run_dir,
-                seconds=time.perf_counter() - t0, volume=vol, dead=dead)
+                seconds=time.perf_counter() - t0, volume=vol, dead=dead, predictive=pred)
 
 
 def fit_job(fn_name, **kw):
@@ -848,6 +889,12 @@ def main(argv=None):
                                                                 "UCE of the run's uncertainty maps (mfvi, mcd, sgld), and of the posterior "
                                                                 "predictive maps with --predict-samples")
     ap.add_argument("--calibration-bins", type=int, default=15)
+    ap.add_argument("--batch-predict-samples", type=int, default=0, help="0 (off) or >= 2, with --fits-per-launch, --ct-volume, --inpaint-fits or --sibling-fits "
+                                                                       "(--bayes mcd): after the last iteration of a batch draw N posterior samples of "
+                                                                       "EVERY fit in one set of launches and write predictive_batch.npz beside batch.npz / "
+                                                                       "volume.npz")
+    ap.add_argument("--batch-calibration", action="store_true", help="with --batch-predict-samples: calibration_batch.npz, the calibration statistics of "
+                                                                      "every fit's posterior predictive maps (--calibration-bins bins)")
     ap.add_argument("--fits-per-launch", type=int, default=0, help="> 0: the independent (image, candidate) fits run in batches of up to N as ONE "
                                                                    "set of launches per iteration (FitBatch; mfvi denoising / super-resolution); "
                                                                    "writes batch.npz per batch instead of save.npz per fit")
@@ -871,6 +918,18 @@ def main(argv=None):
             ap.error("--sr-downsampler %s belongs to --task super-resolution --bayes mfvi" % a.sr_downsampler)
         if a.fits_per_launch:
             ap.error("--sr-downsampler %s does not combine with --fits-per-launch (batched fits project with [::f, ::f])" % a.sr_downsampler)
+    if a.batch_predict_samples or a.batch_calibration:      # refused before anything loads the library
+        if a.batch_predict_samples < 0 or a.batch_predict_samples == 1:
+            ap.error("--batch-predict-samples %d: 0 (off) or at least 2" % a.batch_predict_samples)
+        if not (a.fits_per_launch > 0 or a.ct_volume is not None or a.inpaint_fits > 0 or a.sibling_fits > 0):
+            ap.error("--batch-predict-samples / --batch-calibration predict every fit of a batch: they need --fits-per-launch, --ct-volume, --inpaint-fits or "
+                     "--sibling-fits (a single fit takes --predict-samples / --calibration)")
+        if a.sibling_fits > 0 and a.bayes != "mcd":
+            ap.error("--batch-predict-samples / --batch-calibration with --sibling-fits need a posterior to draw from (--bayes mcd), not %s" % a.bayes)
+        if a.batch_calibration and not a.batch_predict_samples:
+            ap.error("--batch-calibration calibrates the posterior predictive maps of --batch-predict-samples N (N >= 2)")
+        if a.batch_calibration and not 1 <= a.calibration_bins <= L.UCE_MAX_BINS:
+            ap.error("--calibration-bins %d outside 1..%d" % (a.calibration_bins, L.UCE_MAX_BINS))
     if a.sibling_fits < 0:
         ap.error("--sibling-fits %d: 0 (off) or the number of fits per launch" % a.sibling_fits)
     if a.sibling_fits:      # refused before anything loads the library, and ahead of the other batching flags' own refusals
@@ -955,6 +1014,9 @@ def main(argv=None):
     if a.calibration:
         rp["calibration"] = True
         rp["calibration_bins"] = a.calibration_bins
+    if a.batch_predict_samples:
+        rp["batch_predict_samples"] = a.batch_predict_samples
+        rp["batch_calibration_bins"] = a.calibration_bins if a.batch_calibration else 0
     if a.ct_volume is not None:      # one volume fit per candidate of the config
         from .fanout import print_table
         vrp = {k: v for k, v in rp.items() if k not in ("img", "plot", "p_sigma")}
