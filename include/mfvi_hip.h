@@ -51,6 +51,7 @@
  */
 #ifndef MFVI_HIP_H
 #define MFVI_HIP_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -545,6 +546,29 @@ int mfvi_sibling_update_fits(float* params, float* grads, float* m, float* v, in
  * mfvi_add_normal(x + layer_off[l], seed, l, step, layer_n[l], ...).  std[f], dead[f] in device memory; dead fits are skipped. */
 int mfvi_add_normal_fits(float* params, int64_t param_stride, int n_fits, uint32_t fit0, const int64_t* layer_off, const int64_t* layer_n,
                          int n_layers, uint64_t seed, uint32_t step, const float* std, const int32_t* dead, void* stream);
+
+/* ---- batched bookkeeping: the runner's per-iteration records for many fits per launch ---------------------------- */
+/* mfvi_bookkeep per fit in one launch (grid = pixels x fit): out [n_fits * S][C][H][W], ema [n_fits][C][H][W], every map buffer
+ * [n_fits][H][W].  Fit f gets exactly what mfvi_bookkeep(out + f S C HW, S, C, H, W, ema + f C HW, ...) writes (the same per-pixel code),
+ * so ema is bit-equal to mfvi_ema_fits.  ale_clip / ring_ale are unused (may be NULL) for C = 1; ring_epi / ring_ale may be NULL.  Null
+ * out / ema / out_clip / avg_clip, n_fits outside 1..65535, S < 1, C outside 1..2, H or W < 1: -1 and mfvi_last_error(), no launch. */
+int mfvi_bookkeep_fits(const float* out, int n_fits, int S, int C, int H, int W, float* ema, float weight, int first, float* out_clip,
+                       float* avg_clip, float* ale_clip, float* ring_epi, float* ring_ale, void* stream);
+/* Squared-error and SSIM sums of n_pairs pairs of [H][W] maps, x_p = x + p * x_stride, y_p = y + p * y_stride (a stride of 0 shares one
+ * map, e.g. a common ground truth).  Both overwritten, no memset, no atomics:
+ *   sums[p * sums_stride + 0] = sum (double)((x - y) * (x - y))     difference and product in float, as mfvi_sq_err_sum
+ *   sums[p * sums_stride + 1] = sum of the SSIM map                   only with want_ssim (otherwise untouched); the map of mfvi_ssim_sum:
+ *                                                                      11-tap sigma 1.5 Gaussian, zero padding 5, C1 = 0.01^2, C2 = 0.03^2
+ * One block stages a 16 x 64 tile of a pair with its 5-pixel halo in LDS, filters the five moment planes horizontally then vertically
+ * (separable: rounding differs from the 121-tap form of mfvi_ssim_sum by a few 1e-6 of the mean), reduces its two sums in fp64 in a fixed
+ * order and writes them to its own slot of scratch; one block per pair then adds the tile partials in index order.  Two launches whatever
+ * n_pairs is; bit-identical from call to call; pair p's sums depend neither on n_pairs nor on the other pairs (a NaN stays in its pair).
+ * scratch: mfvi_pair_metrics_scratch_bytes(n_pairs, H, W) bytes, 8-byte aligned (0 for arguments mfvi_pair_metrics refuses).  Null
+ * pointers, n_pairs outside 1..65535, H or W < 1, a stride between 1 and H W - 1, sums_stride < 1 (2 with want_ssim): -1 and
+ * mfvi_last_error(), no launch. */
+size_t mfvi_pair_metrics_scratch_bytes(int n_pairs, int H, int W);
+int mfvi_pair_metrics(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int n_pairs, int H, int W, int want_ssim,
+                      void* scratch, double* sums, int64_t sums_stride, void* stream);
 
 const char* mfvi_last_error(void);
 int mfvi_abi_version(void);

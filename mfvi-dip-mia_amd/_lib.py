@@ -121,6 +121,9 @@ SIGNATURES = {
     "mfvi_mse_channel_fits": (_I, [_P, _P, _I64, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "mfvi_sibling_update_fits": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _F, _F, _F, _I, _P, _P, _P]),
     "mfvi_add_normal_fits": (_I, [_P, _I64, _I, _U32, _P, _P, _I, _U64, _U32, _P, _P, _P]),
+    "mfvi_bookkeep_fits": (_I, [_P, _I, _I, _I, _I, _I, _P, _F, _I, _P, _P, _P, _P, _P, _P]),
+    "mfvi_pair_metrics_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
+    "mfvi_pair_metrics": (_I, [_P, _I64, _P, _I64, _I, _I, _I, _I, _P, _P, _I64, _P]),
     "mfvi_last_error": (C.c_char_p, []),
     "mfvi_abi_version": (_I, []),
 }

@@ -63,6 +63,8 @@ def check_args(S, n_slices, slices_per_launch, K, temp, sigma, lr, theta_deg, in
 
 
 class CtVolume:
+    _book = None            # a BatchBook once track()ed
+
     def __init__(self, S, n_slices, slices_per_launch=None, K=1, input_depth=16, temp=1.0, sigma=0.1, lr=1e-3, theta_deg=None, seed=1,
                  net_kwargs=None, init="per_fit", autotune=True):
         self.S, self.F, self.temps, self.sigmas, self.lrs, self.theta_list = check_args(S, n_slices, slices_per_launch, K, temp, sigma, lr,
@@ -170,9 +172,26 @@ class CtVolume:
         ready = t.cuda.Event(); ready.record(t.cuda.current_stream())
         with t.cuda.stream(self._side):
             self._side.wait_event(ready)
-            L.check(L.lib().mfvi_ema_fits(L.ptr(self.out), nd, self.K, 1, self.S, self.S, L.ptr(self.ema[d0:]), EXP_WEIGHT, int(self._ema_n == 0),
-                                          L.stream_ptr()))
+            if self._book is None:
+                L.check(L.lib().mfvi_ema_fits(L.ptr(self.out), nd, self.K, 1, self.S, self.S, L.ptr(self.ema[d0:]), EXP_WEIGHT, int(self._ema_n == 0),
+                                              L.stream_ptr()))
+            else:                        # the same EMA from mfvi_bookkeep_fits; behind the last group, the iteration's records of every slice
+                self._book.group(self.out, d0, nd, self.K, self._ema_n == 0)
+                if d0 + nd == self.D:
+                    self._book.finish()
             self._ema_done.record(self._side)
+
+    def track(self, gt, num_iter, noisy=None):
+        """Record what the single-fit CT runner records per iteration, for every slice -> the BatchBook; step() then
+        runs its iteration where the EMA runs.  gt: the stack [D, S, S] (or one [S, S] slice for all); noisy stays None (both
+        'corrupted' columns of the CT runner are against the ground truth)."""
+        from .batchbook import BatchBook
+        return BatchBook(self, num_iter, gt, noisy)
+
+    def metrics(self, gt):
+        """dict(psnr=[D], ssim=[D]) of recon() against the ground truth ([S, S] shared, or [D, S, S]), one mfvi_pair_metrics call."""
+        from .batchbook import recon_metrics
+        return recon_metrics(self, gt)
 
     def grad_only(self, step=None, perturb=True, ema=False):
         """Everything of one iteration except the update, group by group: grads [D, n_params] and nll_acc [D] hold the result (no KL term)."""

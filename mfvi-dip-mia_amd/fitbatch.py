@@ -59,6 +59,8 @@ def check_args(H, W, n_fits, task, K, temp, sigma, lr, init):
 
 
 class FitBatch:
+    _book = None            # a BatchBook once track()ed
+
     def __init__(self, H, W, n_fits, task="den", K=1, input_depth=16, temp=1.0, sigma=0.1, lr=1e-3, seed=1, sr_factor=4, net_kwargs=None,
                  init="per_fit", autotune=True):
         self.temps, self.sigmas, self.lrs = check_args(H, W, n_fits, task, K, temp, sigma, lr, init)
@@ -151,10 +153,24 @@ class FitBatch:
         ready = t.cuda.Event(); ready.record(t.cuda.current_stream())
         with t.cuda.stream(self._side):
             self._side.wait_event(ready)
-            L.check(L.lib().mfvi_ema_fits(L.ptr(self.out), self.F, self.K, 2, self.H, self.W, L.ptr(self.ema), EXP_WEIGHT, int(self._ema_n == 0),
-                                          L.stream_ptr()))
+            if self._book is None:
+                L.check(L.lib().mfvi_ema_fits(L.ptr(self.out), self.F, self.K, 2, self.H, self.W, L.ptr(self.ema), EXP_WEIGHT, int(self._ema_n == 0),
+                                              L.stream_ptr()))
+            else:                        # the same EMA from mfvi_bookkeep_fits, and the iteration's records (batchbook.BatchBook)
+                self._book.iteration(self.out, self.K, self._ema_n == 0)
             self._ema_done.record(self._side)
         self._ema_n += 1
+
+    def track(self, gt, num_iter, noisy=None):
+        """Record what the single-fit runner records per iteration, for every fit -> the BatchBook; step() then
+        runs its iteration where the EMA runs."""
+        from .batchbook import BatchBook
+        return BatchBook(self, num_iter, gt, noisy)
+
+    def metrics(self, gt):
+        """dict(psnr=[F], ssim=[F]) of recon() against the ground truth ([H, W] shared, or [F, H, W]), one mfvi_pair_metrics call."""
+        from .batchbook import recon_metrics
+        return recon_metrics(self, gt)
 
     def grad_only(self, step=None, perturb=True, ema=False):
         """Everything of one iteration except the update: grads [F, n_params] and nll_acc [F] hold the result (no KL term)."""

@@ -170,6 +170,11 @@ class InpaintBatch:
             self._ema_done.record(self._side)
         self._ema_n += 1
 
+    def track(self, gt, num_iter, noisy=None):
+        """FitBatch.track for inpainting is not built: the 3-channel masked bookkeeping of the inpainting runner is not batched."""
+        raise NotImplementedError("InpaintBatch.track: the 3-channel masked bookkeeping (runner._BookInp) is not batched; run the single-fit "
+                                  "runner on to_engine(f) for per-iteration records")
+
     def grad_only(self, step=None, perturb=True, ema=False):
         """Everything of one iteration except the update: grads [F, n_params] and nll_acc [F] hold the result (no KL term)."""
         if self.images is None:

@@ -571,14 +571,33 @@ def load_config(path, bayes="mfvi", with_devices=False):
     return (cands, rp, devices) if with_devices else (cands, rp)
 
 
+def _save_bookkeeping(book, run_dir, heads):
+    """--batch-bookkeeping: bookkeeping_batch.npz (the per-iteration curves [n_it, F, ...] and the snapshots [n_snap, F, H, W] of a BatchBook)
+    beside batch.npz / volume.npz, and fit_%03d/save.npz per fit as the single-fit runner of the task writes it (heads[f]: its two
+    task-specific arrays, artifacts.save_npz)."""
+    mse_noisy, mse_gt, psnrs, ssims = book.results()
+    stack = lambda k: np.stack([s[k] for s in book.snaps]) if book.snaps else np.zeros((0, book.F, book.H, book.W), np.float32)
+    arrs = dict(iterations=np.asarray([s[0] for s in book.snaps], np.int64), mse_noisy=mse_noisy, mse_gt=mse_gt, psnrs=psnrs, ssims=ssims, recons=stack(3),
+                uncerts=stack(1))
+    if book.C > 1:
+        arrs["uncerts_ale"] = stack(2)
+    np.savez(os.path.join(run_dir, "bookkeeping_batch.npz"), **arrs)
+    for f in range(book.F):
+        fit_dir = os.path.join(run_dir, "fit_%03d" % f)
+        os.makedirs(fit_dir, exist_ok=False)
+        book.save_npz(f, fit_dir, heads[f])
+
+
 def run_fit_batch(task, jobs, imsize=(256, 256), p_sigma=0.1, num_iter=5000, lr=3e-4, input_depth=16, seed=42, show_every=100, save=True,
                   save_path="../logs", K=1, factor=4, net_kwargs=None, verbose=False, autotune=True, batch_predict_samples=0,
-                  batch_calibration_bins=0, **unused):
+                  batch_calibration_bins=0, batch_bookkeeping=False, **unused):
     """The (image, temp, sigma) jobs of one batch as ONE FitBatch (--fits-per-launch): the loop of run_den_mfvi /
     run_sr_mfvi for every job at once, every fit with the noise of its own RNG samples.  jobs: dicts with img, temp, sigma (and optionally
     lr).  Writes batch.npz (hyper-parameters; per fit psnr_gt_sm, nll and kl every show_every iterations, the final reconstruction, dead);
     save.npz and the PNG artefacts stay with the single-fit runners.  batch_predict_samples >= 2: predictive_batch.npz (and with
-    batch_calibration_bins calibration_batch.npz) beside it (_batch_predict).  Returns dict(psnr=[per fit, NaN for a dead fit], ...)."""
+    batch_calibration_bins calibration_batch.npz) beside it (_batch_predict).  batch_bookkeeping: the per-iteration records of every fit
+    (BatchBook) -> bookkeeping_batch.npz and fit_%03d/save.npz beside it (_save_bookkeeping).  Returns dict(psnr=[per fit, NaN for a dead
+    fit], ...)."""
     import torch
     from .fitbatch import FitBatch
     _check_batch_predict(batch_predict_samples, batch_calibration_bins)
@@ -601,10 +620,13 @@ def run_fit_batch(task, jobs, imsize=(256, 256), p_sigma=0.1, num_iter=5000, lr=
                   net_kwargs=net_kwargs, init="shared", autotune=autotune)      # the reference's candidates all start from one seed
     fb.set_targets(torch.from_numpy(targets))
     n_it = num_iter + 1                                               # bayesian_optimization.py:1291
+    book = fb.track(gt, n_it, noisy=targets if task == "den" else None) if batch_bookkeeping else None      # 
     at, psnrs, nlls, kls = [], [], [], []
     t0 = time.perf_counter()
     for i in range(n_it):
         fb.step()
+        if book is not None and i % show_every == 0:
+            book.snapshot()
         if i % show_every == 0 or i == n_it - 1:
             nll, kl, _ = fb.losses()
             at.append(i); psnrs.append(fb.psnr(gt)); nlls.append(nll); kls.append(kl)
@@ -619,6 +641,8 @@ def run_fit_batch(task, jobs, imsize=(256, 256), p_sigma=0.1, num_iter=5000, lr=
         np.savez(os.path.join(run_dir, "batch.npz"), task=task, temp=np.asarray(temps), sigma=np.asarray(sigmas), lr=np.asarray(lrs),
                  prior_sigma=np.asarray(fb.prior_sigma), K=np.int64(K), seed=np.int64(seed), num_iter=np.int64(num_iter), iterations=np.asarray(at),
                  psnr_gt_sm=np.stack(psnrs), nll=np.stack(nlls), kl=np.stack(kls), recon=fb.recon().cpu().numpy(), dead=dead)
+        if book is not None:
+            _save_bookkeeping(book, run_dir, [(gt[f][None], targets[f][None] if task == "den" else targets[f]) for f in range(F)])
     pred = _batch_predict(fb, batch_predict_samples, gt, run_dir, batch_calibration_bins) if batch_predict_samples else None
     return dict(psnr=[float(x) for x in final], run_dir=run_dir, seconds=time.perf_counter() - t0, batch=fb, dead=dead, predictive=pred)
 
@@ -687,12 +711,13 @@ def inpaint_batch_job(task, jobs, **kw):
 
 def run_sibling_batch(task, method, jobs, imsize=None, p_sigma=0.1, num_iter=5000, lr=None, input_depth=None, seed=42, show_every=100, save=True,
                       save_path="../logs", K=1, factor=4, net_kwargs=None, verbose=False, autotune=True, param_noise_sigma=2.0,
-                      batch_predict_samples=0, batch_calibration_bins=0, **unused):
+                      batch_predict_samples=0, batch_calibration_bins=0, batch_bookkeeping=False, **unused):
     """The (image, candidate) jobs of one batch as ONE SiblingBatch (--sibling-fits): the loop of run_<task>_<method> for
     every job at once.  jobs: dicts with img and, per method, dropout_p / weight_decay (mcd) or gamma / weight_decay (sgld), optionally lr;
     what a job leaves out takes the default of run_<task>_<method>.  Writes batch.npz (hyper-parameters; per fit psnr_gt_sm and the data
     term every show_every iterations, the final reconstruction, dead); save.npz, SGLD's iterate ring and the PNG artefacts stay with the
-    single-fit runners.  Returns dict(psnr=[per fit, NaN for a dead fit], ...)."""
+    single-fit runners; batch_bookkeeping: bookkeeping_batch.npz and fit_%03d/save.npz as run_fit_batch writes them.  Returns
+    dict(psnr=[per fit, NaN for a dead fit], ...)."""
     import torch
     from .siblingbatch import SiblingBatch
     if task not in ("den", "sr") or method not in ("dip", "mcd", "sgld"):
@@ -720,10 +745,13 @@ def run_sibling_batch(task, method, jobs, imsize=None, p_sigma=0.1, num_iter=500
                       param_noise_sigma=param_noise_sigma, init="shared", autotune=autotune, **hyper)      # the reference's candidates all start from one seed
     sb.set_targets(torch.from_numpy(targets))
     n_it = num_iter + 1                                               # bayesian_optimization.py:1291
+    book = sb.track(gt, n_it, noisy=targets if task == "den" else None) if batch_bookkeeping else None      # 
     at, psnrs, losses = [], [], []
     t0 = time.perf_counter()
     for i in range(n_it):
         sb.step()
+        if book is not None and i % show_every == 0:
+            book.snapshot()
         if i % show_every == 0 or i == n_it - 1:
             at.append(i); psnrs.append(sb.psnr(gt)); losses.append(sb.losses())
             if verbose:
@@ -737,6 +765,8 @@ def run_sibling_batch(task, method, jobs, imsize=None, p_sigma=0.1, num_iter=500
         np.savez(os.path.join(run_dir, "batch.npz"), method=method, task=task, lr=np.asarray(lrs), weight_decay=np.asarray(sb.weight_decays),
                  dropout_p=np.asarray(sb.dropout_ps), gamma=np.asarray(sb.gammas), K=np.int64(K), seed=np.int64(seed), num_iter=np.int64(num_iter),
                  iterations=np.asarray(at), psnr_gt_sm=np.stack(psnrs), loss=np.stack(losses), recon=sb.recon().cpu().numpy(), dead=dead)
+        if book is not None:
+            _save_bookkeeping(book, run_dir, [(gt[f][None], targets[f][None] if task == "den" else targets[f]) for f in range(F)])
     pred = _batch_predict(sb, batch_predict_samples, gt, run_dir, batch_calibration_bins) if batch_predict_samples else None
     return dict(psnr=[float(x) for x in final], run_dir=run_dir, seconds=time.perf_counter() - t0, batch=sb, dead=dead, predictive=pred)
 
@@ -824,11 +854,12 @@ def _load_volume(volume, imsize, seed):
 
 def run_ct_volume(volume, temp, sigma, slices_per_launch=None, imsize=(256, 256), num_iter=5000, lr=3e-4, input_depth=16, seed=42, show_every=100,
                   save=True, save_path="../logs", K=1, theta_step=4.0, net_kwargs=None, verbose=False, autotune=True, batch_predict_samples=0,
-                  batch_calibration_bins=0, **unused):
+                  batch_calibration_bins=0, batch_bookkeeping=False, **unused):
     """The loop of run_ct_mfvi (bayesian_optimization.py:442-648) for every slice of a stack at once, as ONE CtVolume (--ct-volume; DESIGN.md
     section 16).  volume: [D, S, S] array, .npy path or 'phantom:D'; temp / sigma / lr: scalars or one value per slice.  Writes volume.npz
     (angles, sinograms, hyper-parameters; per slice psnr_gt_sm, nll and kl every show_every iterations, the reconstruction, dead); the ring
-    buffers, SSIM curves, save.npz and PNG artefacts stay with the single-fit runner.  Returns dict(psnr=[per slice, NaN for a dead one], ...)."""
+    buffers, SSIM curves, save.npz and PNG artefacts stay with the single-fit runner unless batch_bookkeeping (bookkeeping_batch.npz and
+    fit_%03d/save.npz per slice, _save_bookkeeping; no PNGs).  Returns dict(psnr=[per slice, NaN for a dead one], ...)."""
     import torch
     from .ctvolume import CtVolume
     _check_batch_predict(batch_predict_samples, batch_calibration_bins)
@@ -839,10 +870,13 @@ def run_ct_volume(volume, temp, sigma, slices_per_launch=None, imsize=(256, 256)
                    seed=seed, net_kwargs=net_kwargs, autotune=autotune)
     vol.set_volume(torch.from_numpy(gt))                              # img_radon = forward_radon(img_torch) (:547)
     n_it = num_iter + 1                                               # as the single-fit runners count
+    book = vol.track(gt, n_it) if batch_bookkeeping else None          # 
     at, psnrs, nlls, kls = [], [], [], []
     t0 = time.perf_counter()
     for i in range(n_it):
         vol.step()
+        if book is not None and i % show_every == 0:
+            book.snapshot()
         if i % show_every == 0 or i == n_it - 1:
             nll, kl, _ = vol.losses()
             at.append(i); psnrs.append(vol.psnr(gt)); nlls.append(nll); kls.append(kl)
@@ -858,6 +892,9 @@ def run_ct_volume(volume, temp, sigma, slices_per_launch=None, imsize=(256, 256)
                  lr=np.asarray(vol.lrs), prior_sigma=np.asarray(vol.prior_sigma), K=np.int64(K), seed=np.int64(seed), num_iter=np.int64(num_iter),
                  slices_per_launch=np.int64(vol.F), iterations=np.asarray(at), psnr_gt_sm=np.stack(psnrs), nll=np.stack(nlls), kl=np.stack(kls),
                  recon=vol.recon().cpu().numpy(), dead=dead)
+        if book is not None:      # heads as run_ct_mfvi writes them: img_gt (1, 1, S, S), img_radon (1, 1, T, S)
+            sinos = vol.sinos.cpu().numpy()
+            _save_bookkeeping(book, run_dir, [(gt[d][None, None], sinos[d][None, None]) for d in range(D)])
     pred = _batch_predict(vol, batch_predict_samples, gt, run_dir, batch_calibration_bins) if batch_predict_samples else None
     live = final[dead == 0]
     return dict(psnr=[float(x) for x in final], mean_psnr=float(live.mean()) if live.size else float("nan"), run_dir=run_dir,
@@ -895,6 +932,9 @@ def main(argv=None):
                                                                        "volume.npz")
     ap.add_argument("--batch-calibration", action="store_true", help="with --batch-predict-samples: calibration_batch.npz, the calibration statistics of "
                                                                       "every fit's posterior predictive maps (--calibration-bins bins)")
+    ap.add_argument("--batch-bookkeeping", action="store_true", help="with --fits-per-launch, --sibling-fits or --ct-volume: record what the single-fit "
+                                                                     "runner records per iteration for EVERY fit of a batch (BatchBook) and write "
+                                                                     "bookkeeping_batch.npz and fit_NNN/save.npz beside batch.npz / volume.npz")
     ap.add_argument("--fits-per-launch", type=int, default=0, help="> 0: the independent (image, candidate) fits run in batches of up to N as ONE "
                                                                    "set of launches per iteration (FitBatch; mfvi denoising / super-resolution); "
                                                                    "writes batch.npz per batch instead of save.npz per fit")
@@ -918,6 +958,9 @@ def main(argv=None):
             ap.error("--sr-downsampler %s belongs to --task super-resolution --bayes mfvi" % a.sr_downsampler)
         if a.fits_per_launch:
             ap.error("--sr-downsampler %s does not combine with --fits-per-launch (batched fits project with [::f, ::f])" % a.sr_downsampler)
+    if a.batch_bookkeeping and not (a.fits_per_launch > 0 or a.sibling_fits > 0 or a.ct_volume is not None):      # refused before anything loads the library
+        ap.error("--batch-bookkeeping records every fit of a batch: it needs --fits-per-launch, --sibling-fits or --ct-volume (a single fit always "
+                 "keeps these records; --inpaint-fits has no batched bookkeeping)")
     if a.batch_predict_samples or a.batch_calibration:      # refused before anything loads the library
         if a.batch_predict_samples < 0 or a.batch_predict_samples == 1:
             ap.error("--batch-predict-samples %d: 0 (off) or at least 2" % a.batch_predict_samples)
@@ -1017,6 +1060,8 @@ def main(argv=None):
     if a.batch_predict_samples:
         rp["batch_predict_samples"] = a.batch_predict_samples
         rp["batch_calibration_bins"] = a.calibration_bins if a.batch_calibration else 0
+    if a.batch_bookkeeping:
+        rp["batch_bookkeeping"] = True
     if a.ct_volume is not None:      # one volume fit per candidate of the config
         from .fanout import print_table
         vrp = {k: v for k, v in rp.items() if k not in ("img", "plot", "p_sigma")}
