@@ -21,15 +21,13 @@ EXP_WEIGHT = 0.99       # EMA weight (:1292)
 
 
 def owner_geometry(batch):
-    """(kind, n_fits, C, H, W, factor) of a batch that can be tracked: 'den' / 'sr' (FitBatch, SiblingBatch; two output channels), 'ct'
-    (CtVolume; one)."""
-    if type(batch).__name__ == "InpaintBatch":
+    """(kind, n_fits, C, H, W, factor) of a batch that can be tracked, from the attributes every RowBatch has: 'den' / 'sr' (FitBatch,
+    SiblingBatch; two output channels), 'ct' (CtVolume; one)."""
+    if batch.task == "inp":
         raise NotImplementedError("InpaintBatch is not tracked: its 3-channel masked bookkeeping is not batched")
-    if hasattr(batch, "groups"):
-        return "ct", int(batch.D), 1, int(batch.S), int(batch.S), 1
-    if batch.task not in ("den", "sr"):
+    if batch.task not in ("den", "sr", "ct"):
         raise NotImplementedError("bookkeeping of task %r is not batched" % (batch.task,))
-    return batch.task, int(batch.F), 2, int(batch.H), int(batch.W), int(batch.sr_factor) if batch.task == "sr" else 1
+    return batch.task, int(batch.n_rows), int(batch.C), int(batch.H), int(batch.W), int(batch.sr_factor) if batch.task == "sr" else 1
 
 
 def check_maps(kind, n_fits, H, W, gt, noisy):
@@ -140,11 +138,6 @@ class BatchBook:
         pairs(ema, C * hw, self.gt, hw, F, H, W, 0, 1)                               # mse(out_avg[:, :1], gt)                       :1390
         pairs(self.gt2, hw, self.clips, hw, 2 * F, H, W, 1, 3)                       # psnr / ssim of gt vs out_clip, then vs avg_clip
         self.i += 1
-
-    def iteration(self, out, S, first):
-        """One iteration of a batch whose fits all ran in one set of launches."""
-        self.group(out, 0, self.F, S, first)
-        self.finish()
 
     # ---- results -------------------------------------------------------------------------------------------------------------------
     @property

@@ -14,12 +14,12 @@ MAX_WORKSPACE_SAMPLES = 64      # default S = max(1, min(N, 64 // G)): the predi
 
 
 def n_fits_of(owner):
-    """Fits of a batch: the D slices of a CtVolume (whose F is the slices per launch), else F."""
-    return int(getattr(owner, "D", owner.F))
+    """Fits of a batch: its rows (the D slices of a CtVolume, whose F is the slices per launch)."""
+    return int(owner.n_rows)
 
 
 def task_of(owner):
-    return getattr(owner, "task", "ct")
+    return owner.task
 
 
 def plan_chunks(n_fits, n_samples, fits_per_call, chunk):
@@ -64,7 +64,7 @@ def check_args(owner, n_samples, target=None, step=None, chunk=None, fits_per_ca
         raise ValueError("step %d outside the 32-bit counter word" % step)
     kind = None
     if target is not None:
-        H, W = getattr(owner, "H", getattr(owner, "S", None)), getattr(owner, "W", getattr(owner, "S", None))
+        H, W = owner.H, owner.W
         cimg = 3 if task_of(owner) == "inp" else 1
         shape = tuple(target.shape)
         shared = [(cimg, H, W)] + ([(H, W)] if cimg == 1 else [])

@@ -69,9 +69,9 @@ def test_inpaint_batch_is_not_tracked(no_library):
 def test_wrong_shapes_are_refused_before_the_library(no_library):
     M = no_library
     H, W, F = 32, 40, 3
-    den = types.SimpleNamespace(task="den", F=F, H=H, W=W, sr_factor=4)
-    sr = types.SimpleNamespace(task="sr", F=F, H=H, W=W, sr_factor=4)
-    ct = types.SimpleNamespace(groups=[(0, 2, 0, 0, 2)], D=F, S=H)
+    den = types.SimpleNamespace(task="den", n_rows=F, C=2, F=F, H=H, W=W, sr_factor=4)
+    sr = types.SimpleNamespace(task="sr", n_rows=F, C=2, F=F, H=H, W=W, sr_factor=4)
+    ct = types.SimpleNamespace(task="ct", n_rows=F, C=1, H=H, W=H, groups=[(0, 2, 0, 0, 2)], D=F, S=H)
     ok, okF = np.zeros((H, W), np.float32), np.zeros((F, H, W), np.float32)
     for gt in (np.zeros((W, H)), np.zeros((F + 1, H, W)), np.zeros((F, H, W, 1)), np.zeros((H,))):
         with pytest.raises(ValueError, match="ground truth"):

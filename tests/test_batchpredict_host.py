@@ -58,6 +58,7 @@ def test_planner_chunks_and_groups(no_library):
 def owner(**kw):
     d = dict(F=3, H=32, W=32, task="den")
     d.update(kw)
+    d.setdefault("n_rows", d["F"])                     # the rows of a batch are its F fits, except on a CtVolume
     return types.SimpleNamespace(**d)
 
 
@@ -67,7 +68,7 @@ def test_predict_arguments_are_checked_without_the_library(no_library):
     gt = np.zeros((32, 32), np.float32)
     assert B.check_args(owner(), 7) == (7, 7, 3, DEFAULT_STEP, None, None)
     assert B.check_args(owner(F=16), 64)[1:3] == (4, 16)                                             # S = 64 // G: at most 64 samples in the workspace
-    assert B.check_args(owner(F=2, D=16, S=32, task="ct"), 64)[1:3] == (32, 2)                        # CtVolume: D slices, G = its slices per launch
+    assert B.check_args(owner(F=2, D=16, S=32, n_rows=16, H=32, W=32, task="ct"), 64)[1:3] == (32, 2)                       # CtVolume: D slices, G = its slices per launch
     assert B.check_args(owner(F=100), 7)[1] == 1
     assert B.check_args(owner(), 7, target=gt, chunk=3, fits_per_call=2, step=5, calibration=True) == (7, 3, 2, 5, {}, "shared")
     assert B.check_args(owner(), 7, target=np.zeros((1, 32, 32)))[5] == "shared"
