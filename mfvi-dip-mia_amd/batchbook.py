@@ -2,7 +2,7 @@
 
 The single-fit runners keep mse_noisy, mse_gt, three PSNRs and three SSIMs per iteration and, every show_every iterations, the variance and
 the mean of two 25-slot ring buffers and the clipped EMA reconstruction (bayesian_optimization.py:1374-1416, :2190-2236, :584-626;
-runner._Book).  A BatchBook attached to a FitBatch, a SiblingBatch or a CtVolume records the same per fit from a number of launches per
+book._Book).  A BatchBook attached to a FitBatch, a SiblingBatch or a CtVolume records the same per fit from a number of launches per
 iteration that does not depend on the number of fits:
 
     mfvi_bookkeep_fits       EMA (in the batch's own ema: it replaces mfvi_ema_fits), clipped copies, ring slots      1 launch (per group: CtVolume)
@@ -15,9 +15,8 @@ import numpy as np
 
 from . import _lib as L
 from . import artifacts as A
-
-MC_ITER = 25            # ring-buffer length (bayesian_optimization.py:1314)
-EXP_WEIGHT = 0.99       # EMA weight (:1292)
+from .book import MC_ITER
+from .rowbatch import EXP_WEIGHT
 
 
 def owner_geometry(batch):
@@ -142,7 +141,7 @@ class BatchBook:
     # ---- results -------------------------------------------------------------------------------------------------------------------
     @property
     def metrics(self):
-        """[num_iter, F, 8] float64 on the device, the columns of runner._Book: mse_noisy, mse_gt, 3 squared-error sums for the PSNRs, 3 SSIM
+        """[num_iter, F, 8] float64 on the device, the columns of book._Book: mse_noisy, mse_gt, 3 squared-error sums for the PSNRs, 3 SSIM
         sums (sums over the pixels; results() divides).  Gathered from the raw pair sums on the device, no host sync."""
         self.batch._wait_ema()
         r = self.raw
@@ -151,7 +150,7 @@ class BatchBook:
 
     def results(self):
         """(mse_noisy [n_it, F], mse_gt [n_it, F], psnrs [n_it, F, 3], ssims [n_it, F, 3]) of the iterations recorded so far, by the host
-        arithmetic of runner._Book.results."""
+        arithmetic of book._Book.results."""
         m = self.metrics[:self.i].cpu().numpy()
         n = np.full(8, float(self.H * self.W))
         if self.kind == "sr":

@@ -109,7 +109,7 @@ class InpaintBatch(ElboRowBatch):
 
     def track(self, gt, num_iter, noisy=None):
         """FitBatch.track for inpainting is not built: the 3-channel masked bookkeeping of the inpainting runner is not batched."""
-        raise NotImplementedError("InpaintBatch.track: the 3-channel masked bookkeeping (runner._BookInp) is not batched; run the single-fit "
+        raise NotImplementedError("InpaintBatch.track: the 3-channel masked bookkeeping (book._BookInp) is not batched; run the single-fit "
                                   "runner on to_engine(f) for per-iteration records")
 
     def recon(self):

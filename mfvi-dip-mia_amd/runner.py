@@ -20,12 +20,11 @@ import numpy as np
 
 from . import _lib as L
 from . import artifacts as A
+from .book import EXP_WEIGHT, MC_ITER, _Book, _BookInp      # noqa: F401  (the bookkeeping's home is book.py; the names stay readable here)
 from .engine import ElboEngine, SiblingEngine
 
-MC_ITER = 25            # ring-buffer length (bayesian_optimization.py:1314)
 PREDICT_METHODS = ("mfvi", "mcd")      # methods whose fit is a posterior predict_samples can draw from (engine.ElboEngine.predict)
 CALIBRATION_METHODS = ("mfvi", "mcd", "sgld")      # methods whose run carries uncertainty maps to calibrate (dip has none)
-EXP_WEIGHT = 0.99       # EMA weight (:1292)
 
 
 def phantom(H, W, seed):
@@ -62,169 +61,6 @@ def _load_image(img, imsize, seed):
         raise ValueError("expected one grayscale image, got shape %s" % (a.shape,))
     h, w = a.shape
     return np.ascontiguousarray(a[:h - h % 32, :w - w % 32])                     # crop to a multiple of 32 (get_image: d=32)
-
-
-class _AsyncBook:
-    """The per-iteration bookkeeping only READS the iteration's forward output, so it runs on a second stream beside the backward pass:
-    `eng.step(after_forward=book.hook(eng, i, n))` enqueues it behind the forward, `book.wait()` (called by the next hook and by snapshot /
-    results) orders the caller's stream behind it before `eng.out` is written again."""
-    _side = None; _done = None
-
-    def hook(self, eng, i, n=None):
-        """-> the callable for eng.step(after_forward=...).  The engine passes the sample count of its LAST launch (eng.out holds only
-        those; with K_local not a multiple of the launch size the last launch is partial), which overrides `n`."""
-        def run(n_last=None):
-            n_ = n if n_last is None else n_last
-            t = self.t
-            if self._side is None:
-                self._side = t.cuda.Stream(); self._done = t.cuda.Event()
-            main = t.cuda.current_stream()
-            ready = t.cuda.Event(); ready.record(main)
-            with t.cuda.stream(self._side):
-                self._side.wait_event(ready)
-                self.iteration(eng, i, n_)
-                self._done.record(self._side)
-        self.wait()          # the previous iteration's bookkeeping has read eng.out before this iteration's forward overwrites it
-        return run
-
-    def wait(self):
-        if self._done is not None:
-            self.t.cuda.current_stream().wait_event(self._done)
-
-
-class _Book(_AsyncBook):
-    """Device-side bookkeeping state of one den / sr / ct fit (bayesian_optimization.py:1374-1416, :2190-2236, :584-626).
-    Column 0 of mse_noisy / psnrs / ssims is the 'corrupted' reference of the task: the noisy image (den), the low-resolution image
-    against the [::f, ::f] projection of the output (sr: downsampler(out_avg) / out_lr, :2203-2218), the ground truth (ct)."""
-
-    def __init__(self, eng, num_iter, gt, noisy_or_none, task="den", factor=4, downsampler="nearest"):
-        import torch
-        self.t = torch
-        H, W, C = eng.H, eng.W, eng.out.shape[1]
-        dev = "cuda"
-        self.C, self.H, self.W, self.task, self.f = C, H, W, task, int(factor)
-        self.ema = torch.zeros((C, H, W), device=dev)
-        self.out_clip = torch.zeros((H, W), device=dev); self.ale_clip = torch.zeros((H, W), device=dev); self.avg_clip = torch.zeros((H, W), device=dev)
-        self.ring_epi = torch.zeros((MC_ITER, H, W), device=dev); self.ring_ale = torch.zeros((MC_ITER, H, W), device=dev)
-        self.metrics = torch.zeros((num_iter, 8), dtype=torch.float64, device=dev)     # mse_noisy, mse_gt, 3 psnr-mse, 3 ssim sums
-        self.gt = torch.from_numpy(np.ascontiguousarray(gt, np.float32)).to(dev)
-        self.noisy = None if noisy_or_none is None else torch.from_numpy(np.ascontiguousarray(noisy_or_none, np.float32)).to(dev)
-        self.var = torch.zeros((H, W), device=dev); self.ale_mean = torch.zeros((H, W), device=dev)
-        if task == "sr":      # img_small_torch = downsampler(img_torch) and the projections of out_avg / out (:2101, :2203, :2207)
-            h, w = H // self.f, W // self.f
-            self.taps = None
-            if downsampler != "nearest":      # the run's `downsampler` is the Lanczos operator (DESIGN.md section 14): project with it throughout
-                from .downsampler import c_taps
-                self.taps = c_taps(downsampler, self.f)
-                self.gt_lr = torch.empty((h, w), device=dev)
-                self._project(self.gt, self.gt_lr)
-            else:
-                self.gt_lr = self.gt[::self.f, ::self.f].contiguous()
-            self.avg_lr = torch.zeros((h, w), device=dev); self.out_lr_clip = torch.zeros((h, w), device=dev)
-
-    def _project(self, src, dst):
-        """dst = downsampler(src) for one [H][W] map: [::f, ::f] (mfvi_decimate) or the run's Lanczos operator (mfvi_downsample)."""
-        lib, sp, p = L.lib(), L.stream_ptr(), L.ptr
-        if self.taps is None:
-            L.check(lib.mfvi_decimate(p(src), self.H, self.W, self.f, p(dst), sp))
-        else:
-            L.check(lib.mfvi_downsample(p(src), 1, 1, self.H, self.W, self.f, self.taps[0], self.taps[1], p(dst), sp))
-
-    def iteration(self, eng, i, n, lr_view=None):
-        lib, sp, p = L.lib(), L.stream_ptr(), L.ptr
-        slot = i % MC_ITER
-        L.check(lib.mfvi_bookkeep(p(eng.out), n, self.C, self.H, self.W, p(self.ema), EXP_WEIGHT, int(i == 0), p(self.out_clip), p(self.ale_clip),
-                                  p(self.avg_clip), p(self.ring_epi[slot]), p(self.ring_ale[slot]) if self.C > 1 else None, sp))
-        m = self.metrics[i]
-        hw = self.H * self.W
-        avg0 = self.ema[0]
-        if self.task == "sr":
-            h, w = self.gt_lr.shape
-            self._project(avg0, self.avg_lr)
-            self._project(self.out_clip, self.out_lr_clip)      # nearest: clip and [::f, ::f] commute; Lanczos: downsampler(out) of the clipped output
-            L.check(lib.mfvi_sq_err_sum(p(self.avg_lr), p(self.gt_lr), h * w, p(m[0:]), sp))         # mse(downsampler(out_avg)[:, :1], img_small)  :2203
-            L.check(lib.mfvi_sq_err_sum(p(self.gt_lr), p(self.out_lr_clip), h * w, p(m[2:]), sp))    # psnr_lr                                       :2214
-            L.check(lib.mfvi_ssim_sum(p(self.gt_lr), p(self.out_lr_clip), h, w, p(m[5:]), sp))       # ssim_lr                                       :2217
-        else:
-            ref_noisy = self.noisy if self.noisy is not None else self.gt                            # ct: both columns against the ground truth (:594-606)
-            L.check(lib.mfvi_sq_err_sum(p(avg0), p(ref_noisy), hw, p(m[0:]), sp))                    # mse(out_avg[:, :1], noisy)  :1389
-            L.check(lib.mfvi_sq_err_sum(p(ref_noisy), p(self.out_clip), hw, p(m[2:]), sp))           # psnr_corrupted              :1398
-            L.check(lib.mfvi_ssim_sum(p(ref_noisy), p(self.out_clip), self.H, self.W, p(m[5:]), sp))
-        L.check(lib.mfvi_sq_err_sum(p(avg0), p(self.gt), hw, p(m[1:]), sp))              # mse(out_avg[:, :1], gt)     :1390
-        L.check(lib.mfvi_sq_err_sum(p(self.gt), p(self.out_clip), hw, p(m[3:]), sp))     # psnr_gt
-        L.check(lib.mfvi_sq_err_sum(p(self.gt), p(self.avg_clip), hw, p(m[4:]), sp))     # psnr_gt_sm
-        L.check(lib.mfvi_ssim_sum(p(self.gt), p(self.out_clip), self.H, self.W, p(m[6:]), sp))
-        L.check(lib.mfvi_ssim_sum(p(self.gt), p(self.avg_clip), self.H, self.W, p(m[7:]), sp))
-
-    def snapshot(self):
-        self.wait()
-        lib, sp, p = L.lib(), L.stream_ptr(), L.ptr
-        L.check(lib.mfvi_ring_stats(p(self.ring_epi), MC_ITER, self.H, self.W, p(self.var), None, sp))
-        if self.C > 1:
-            L.check(lib.mfvi_ring_stats(p(self.ring_ale), MC_ITER, self.H, self.W, None, p(self.ale_mean), sp))
-        return self.var.cpu().numpy(), self.ale_mean.cpu().numpy(), self.avg_clip.cpu().numpy()
-
-    def results(self):
-        self.wait()
-        m = self.metrics.cpu().numpy(); hw = float(self.H * self.W)
-        n = np.full(8, hw)
-        if self.task == "sr":
-            n[[0, 2, 5]] = float(self.gt_lr.numel())
-        m = m / n
-        with np.errstate(divide="ignore"):
-            psnrs = 10.0 * np.log10(1.0 / m[:, 2:5])
-        return m[:, 0], m[:, 1], psnrs, m[:, 5:8]
-
-
-class _BookInp(_AsyncBook):
-    """Device-side bookkeeping of the inpainting runner (bayesian_optimization.py:3039-3090): sigmoid colour channels, masked PSNR / SSIM."""
-
-    def __init__(self, eng, num_iter, img, mask):
-        import torch
-        self.t = torch
-        dev = "cuda"
-        H, W = eng.H, eng.W
-        self.H, self.W = H, W
-        self.img = torch.from_numpy(np.ascontiguousarray(img, np.float32)).to(dev)
-        self.mask = torch.from_numpy(np.ascontiguousarray(mask, np.float32)).to(dev).round()
-        self.mc = self.mask.shape[0]
-        self.ema = torch.zeros((4, H, W), device=dev)
-        self.out_clip = torch.zeros((3, H, W), device=dev); self.avg_clip = torch.zeros_like(self.out_clip); self.ale_clip = torch.zeros((H, W), device=dev)
-        self.img_m = torch.zeros_like(self.out_clip); self.out_m = torch.zeros_like(self.out_clip); self.avg_m = torch.zeros_like(self.out_clip)
-        self.ring_epi = torch.zeros((MC_ITER, 3, H, W), device=dev); self.ring_ale = torch.zeros((MC_ITER, H, W), device=dev)
-        self.metrics = torch.zeros((num_iter, 10, 3), dtype=torch.float64, device=dev)      # per channel: mse, 3 psnr-mse, 3 ssim sums (+ spare)
-        self.var = torch.zeros((3, H, W), device=dev); self.ale_mean = torch.zeros((H, W), device=dev)
-
-    def iteration(self, eng, i, n):
-        lib, p, sp = L.lib(), L.ptr, L.stream_ptr()
-        H, W = self.H, self.W; HW = H * W; slot = i % MC_ITER
-        L.check(lib.mfvi_bookkeep_inpainting(p(eng.out), n, H, W, p(self.img), p(self.mask), self.mc, p(self.ema), EXP_WEIGHT, int(i == 0),
-                                             p(self.out_clip), p(self.ale_clip), p(self.avg_clip), p(self.img_m), p(self.out_m), p(self.avg_m),
-                                             p(self.ring_epi[slot]), p(self.ring_ale[slot]), sp))
-        m = self.metrics[i]
-        for c in range(3):                                            # channel-wise sums; means over the 3 channels taken on the host
-            L.check(lib.mfvi_sq_err_sum(p(self.ema[c]), p(self.img[c]), HW, p(m[0, c:]), sp))            # mse(out_avg[:, :3], img)        :3051-3052
-            L.check(lib.mfvi_sq_err_sum(p(self.img[c]), p(self.out_clip[c]), HW, p(m[1, c:]), sp))       # psnr_corrupted                  :3062
-            L.check(lib.mfvi_sq_err_sum(p(self.img_m[c]), p(self.out_m[c]), HW, p(m[2, c:]), sp))        # psnr_gt (masked)                :3063
-            L.check(lib.mfvi_sq_err_sum(p(self.img_m[c]), p(self.avg_m[c]), HW, p(m[3, c:]), sp))        # psnr_gt_sm
-            L.check(lib.mfvi_ssim_sum(p(self.img[c]), p(self.out_clip[c]), H, W, p(m[4, c:]), sp))
-            L.check(lib.mfvi_ssim_sum(p(self.img_m[c]), p(self.out_m[c]), H, W, p(m[5, c:]), sp))
-            L.check(lib.mfvi_ssim_sum(p(self.img_m[c]), p(self.avg_m[c]), H, W, p(m[6, c:]), sp))
-
-    def snapshot(self):
-        self.wait()
-        lib, p, sp = L.lib(), L.ptr, L.stream_ptr()
-        for c in range(3):
-            L.check(lib.mfvi_ring_stats(p(self.ring_epi[:, c].contiguous()), MC_ITER, self.H, self.W, p(self.var[c]), None, sp))
-        L.check(lib.mfvi_ring_stats(p(self.ring_ale), MC_ITER, self.H, self.W, None, p(self.ale_mean), sp))
-        return self.var.cpu().numpy(), self.ale_mean.cpu().numpy(), self.avg_clip.cpu().numpy()
-
-    def results(self):
-        self.wait()
-        mt = self.metrics.cpu().numpy().mean(axis=2) / (self.H * self.W)      # mean over the colour channels == mean over all 3*H*W elements
-        with np.errstate(divide="ignore"):
-            psnrs = 10.0 * np.log10(1.0 / mt[:, 1:4])
-        return mt[:, 0], mt[:, 0], psnrs, mt[:, 4:7]                          # the reference computes both MSEs against img_torch (:3051-3052)
 
 
 def _make_engine(method, H, W, task, K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, param_dtype="f32", **kw):
@@ -321,58 +157,28 @@ def _predict(eng, n, gt, run_dir, drop_ale=False, calibration_bins=0):
     return arrs
 
 
-def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, seed, show_every, plot, save, save_path, K, factor=4,
-         theta_step=4.0, verbose=False, net_kwargs=None, method="mfvi", weight_decay=0.0, dropout_p=0.3, gamma=0.996, param_dtype="f32", predict_samples=0,
-         calibration=False, calibration_bins=15, downsampler="nearest", **unused):
+def _fit(task, method, fields, prepare, num_iter, show_every, plot, save, save_path, verbose=False, predict_samples=0, calibration=False,
+         calibration_bins=15, downsampler="nearest", factor=4):
+    """The loop of every single-fit runner: the refusals; the run directory and the head of locals.txt (`fields`), written
+    before anything is loaded; `prepare(n_it)` -> (ground truth, engine with its target set, book, the two head arrays of save.npz, mask or
+    None, channel count of recons / uncerts); the iterations with a snapshot every show_every; predictive.npz and calibration.npz; save.npz,
+    the tail of locals.txt and the plots -> the dict of results.  The inpainting runner writes its snapshot PNGs once, at the end."""
     import torch
     _check_downsampler(task, method, downsampler, factor)
     _check_predict(method, predict_samples)
     _check_calibration(method, calibration, calibration_bins)
-    sib = dict(weight_decay=weight_decay, dropout_p=dropout_p, gamma=gamma)
-    timestamp = str(time.time())
-    run_dir = os.path.join(save_path, timestamp)
+    run_dir = os.path.join(save_path, str(time.time()))
     if save:
         os.makedirs(run_dir, exist_ok=False)
-        with open(os.path.join(run_dir, "locals.txt"), "w") as f:
-            hyper = dict(temp=temp, sigma=sigma) if method == "mfvi" else {"dip": {}, "mcd": dict(dropout_p=dropout_p, weight_decay=weight_decay),
-                                                                          "sgld": dict(gamma=gamma, weight_decay=weight_decay)}[method]
-            for key, val in dict(task=task, method=method, img=img if not isinstance(img, np.ndarray) else "<array>", imsize=imsize, p_sigma=p_sigma,
-                                 num_iter=num_iter, lr=lr, input_depth=input_depth, seed=seed, show_every=show_every,
-                                 K=K, save_path=save_path, **(dict(downsampler=downsampler) if task == "sr" else {}), **hyper).items():
-                print(key, "=", val, file=f)
-    img_np = _load_image(img, imsize, seed)
-    H, W = img_np.shape
-    num_iter += 1                                                    # bayesian_optimization.py:1291
-    extra = {}
-    noisy = None
-    if task == "den":
-        rng = np.random.default_rng(seed + 1)
-        noisy = np.clip(img_np + rng.normal(scale=p_sigma, size=img_np.shape), 0, 1).astype(np.float32)      # denoising_utils.py:11
-        target = noisy
-        eng = _make_engine(method, H, W, "den", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, param_dtype=param_dtype)
-    elif task == "sr":
-        noisy = None
-        if downsampler != "nearest":      # img_small = downsampler(img_hr) with the run's operator (models/downsampler.py)
-            from .downsampler import downsample
-            eng = _make_engine(method, H, W, "sr", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, sr_factor=factor, param_dtype=param_dtype,
-                               downsampler=downsampler)
-            target = downsample(torch.from_numpy(img_np).cuda(), downsampler, factor).cpu().numpy()
-        else:
-            target = np.ascontiguousarray(img_np[::factor, ::factor])    # nearest /factor decimation (:2095-2099)
-            eng = _make_engine(method, H, W, "sr", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, sr_factor=factor, param_dtype=param_dtype)
-        extra["img_lr"] = target
-    else:
-        theta = np.arange(0, 180.0, theta_step, dtype=np.float32)     # :545
-        eng = _make_engine(method, H, W, "ct", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, theta_deg=theta.tolist())
-        sino = torch.empty((len(theta), W), device="cuda")
-        gt_d = torch.from_numpy(img_np).cuda()
-        L.check(L.lib().mfvi_radon_forward(L.ptr(gt_d), L.ptr(eng.theta), 1, H, W, len(theta), L.ptr(sino), L.stream_ptr()))
-        target = sino
-        extra["img_radon"] = sino.cpu().numpy()[None, None]
-    eng.set_target(torch.from_numpy(target) if isinstance(target, np.ndarray) else target)
-    book = _Book(eng, num_iter, img_np, noisy, task=task, factor=factor, downsampler=downsampler)
+        A.write_locals(run_dir, **fields)
+    num_iter += 1                                                    # bayesian_optimization.py:1291, :2935
+    gt, eng, book, head, mask, C = prepare(num_iter)
+    H, W = gt.shape[-2:]
+
+    def pngs(i, curves, recon, var, ale):      # loss_<method>.png, out_avg.png, out_var.png, out_ale.png (:1418-1422); the maps (C | 1, H, W)
+        A.snapshot_pngs(run_dir, method, i, *curves, recon, None if method == "dip" else var, None if (method == "dip" or task == "ct") else ale)
     n_snap = num_iter // show_every + 1
-    recons = np.zeros((n_snap, 1, H, W)); uncerts_epi = np.zeros((n_snap, 1, H, W)); uncerts_ale = np.zeros((n_snap, 1, H, W))
+    recons = np.zeros((n_snap, C, H, W)); uncerts_epi = np.zeros((n_snap, C, H, W)); uncerts_ale = np.zeros((n_snap, 1, H, W))
     t0 = time.perf_counter()
     for i in range(num_iter):
         # one fused ELBO iteration (a non-finite loss skips the update on the device: engine.step); the bookkeeping of :1374-1406 reads only the
@@ -380,39 +186,82 @@ def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, see
         eng.step(after_forward=book.hook(eng, i, eng.chunk))
         if i % show_every == 0:
             var, ale, recon = book.snapshot()
-            uncerts_epi[i // show_every, 0] = var; uncerts_ale[i // show_every, 0] = ale; recons[i // show_every, 0] = recon
+            uncerts_epi[i // show_every] = var; uncerts_ale[i // show_every, 0] = ale; recons[i // show_every] = recon
             if verbose:
                 nll, kl, loss = eng.losses()
                 print("iter %6d  loss %.5f  nll %.5f  kl %.4e  (%.1f it/s)" % (i, loss, nll, kl, (i + 1) / (time.perf_counter() - t0)))
-            if plot and save:                                        # loss_<method>.png, out_avg.png, out_var.png, out_ale.png (:1418-1422)
-                mn, mg, ps_, _ = book.results()
-                A.snapshot_pngs(run_dir, method, i, mn, mg, ps_, recon[None], None if method == "dip" else var[None],
-                                None if (method == "dip" or task == "ct") else ale[None])
-    pred = _predict(eng, predict_samples, img_np, run_dir if save else None, drop_ale=task == "ct",
+            if plot and save and task != "inp":
+                pngs(i, book.results()[:3], recon.reshape(C, H, W), var.reshape(C, H, W), ale[None])
+    pred = _predict(eng, predict_samples, gt, run_dir if save else None, drop_ale=task == "ct",
                     calibration_bins=calibration_bins if calibration else 0) if predict_samples else None
-    cal = _calibrate(run_dir if save else None, img_np, recons, uncerts_epi, uncerts_ale, pred.pop("_calibration") if pred else None,
-                     calibration_bins) if calibration else None
+    cal = _calibrate(run_dir if save else None, gt, recons, uncerts_epi, uncerts_ale, pred.pop("_calibration") if pred else None,
+                     calibration_bins, mask=mask) if calibration else None
     torch.cuda.synchronize()
-    mse_noisy, mse_gt, psnrs, ssims = book.results()
+    mse_corrupted, mse_gt, psnrs, ssims = book.results()
     if save:
-        # first two keys as the reference writes them per task: den img_gt / img_noisy (:1438), sr img_hr / img_lr (:2258), ct img_gt / img_radon (:643)
-        # with the reference's shapes: get_image() arrays are (1, H, W), img_lr is squeezed, the CT tensors keep (1, 1, ., .)
-        head = dict(den=(img_np[None], None if noisy is None else noisy[None]), sr=(img_np[None], extra.get("img_lr")),
-                    ct=(img_np[None, None], extra.get("img_radon")))[task]
-        A.save_npz(run_dir, task, method, head, mse_noisy, mse_gt, recons, uncerts_epi, uncerts_ale, psnrs, ssims)
+        A.save_npz(run_dir, task, method, head, mse_corrupted, mse_gt, recons, uncerts_epi, uncerts_ale, psnrs, ssims)
         with open(os.path.join(run_dir, "locals.txt"), "a") as f:
             print("max psnr_gt_sm = %.4f, max ssim_gt_sm = %.4f" % (np.nanmax(psnrs[:, 2]), np.nanmax(ssims[:, 2])), file=f)
             if plot:                                                  # mse_noisy / mse_gt / psnrs / ssims .png + the maxima lines (:201-258, :1431-1433)
-                A.plot_results({method: mse_noisy}, {method: mse_gt}, {method: psnrs}, {method: ssims}, run_dir, f)
+                A.plot_results({method: mse_corrupted}, {method: mse_gt}, {method: psnrs}, {method: ssims}, run_dir, f)
         if plot and task == "sr":
-            A.sr_input_png(run_dir, img_np[None], extra["img_lr"], factor)
-    res = dict(psnr=float(psnrs[-1, 2]), run_dir=run_dir if save else None, psnrs=psnrs, ssims=ssims, mse_noisy=mse_noisy, mse_gt=mse_gt,
-               recons=recons, uncerts=uncerts_epi, uncerts_ale=uncerts_ale, seconds=time.perf_counter() - t0, engine=eng)
+            A.sr_input_png(run_dir, head[0], head[1], factor)
+        if plot and task == "inp":
+            pngs(num_iter - 1, (mse_corrupted, mse_gt, psnrs), recons[-1], uncerts_epi[-1], uncerts_ale[-1])
+    res = {"psnr": float(psnrs[-1, 2]), "run_dir": run_dir if save else None, "psnrs": psnrs, "ssims": ssims, A.MSE_KEY[task]: mse_corrupted,
+           "mse_gt": mse_gt, "recons": recons, "uncerts": uncerts_epi, "uncerts_ale": uncerts_ale, "seconds": time.perf_counter() - t0, "engine": eng}
     if pred is not None:
         res["predictive"] = pred
     if cal is not None:
         res["calibration"] = cal
     return res
+
+
+def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, seed, show_every, plot, save, save_path, K, factor=4,
+         theta_step=4.0, verbose=False, net_kwargs=None, method="mfvi", weight_decay=0.0, dropout_p=0.3, gamma=0.996, param_dtype="f32", predict_samples=0,
+         calibration=False, calibration_bins=15, downsampler="nearest", **unused):
+    """What _fit needs of a den / sr / ct run: its locals.txt fields and, once the run directory stands, the image, the task's target and engine,
+    the _Book and the two head arrays as the reference writes them per task: den img_gt / img_noisy (:1438), sr img_hr / img_lr (:2258), ct
+    img_gt / img_radon (:643) with the reference's shapes (get_image() arrays are (1, H, W), img_lr is squeezed, the CT tensors keep
+    (1, 1, ., .))."""
+    sib = dict(weight_decay=weight_decay, dropout_p=dropout_p, gamma=gamma)
+    hyper = dict(temp=temp, sigma=sigma) if method == "mfvi" else {"dip": {}, "mcd": dict(dropout_p=dropout_p, weight_decay=weight_decay),
+                                                                  "sgld": dict(gamma=gamma, weight_decay=weight_decay)}.get(method, {})
+    fields = dict(task=task, method=method, img=img if not isinstance(img, np.ndarray) else "<array>", imsize=imsize, p_sigma=p_sigma,
+                  num_iter=num_iter, lr=lr, input_depth=input_depth, seed=seed, show_every=show_every, K=K, save_path=save_path,
+                  **(dict(downsampler=downsampler) if task == "sr" else {}), **hyper)
+
+    def prepare(n_it):
+        import torch
+        img_np = _load_image(img, imsize, seed)
+        H, W = img_np.shape
+        noisy = None
+        if task == "den":
+            rng = np.random.default_rng(seed + 1)
+            noisy = np.clip(img_np + rng.normal(scale=p_sigma, size=img_np.shape), 0, 1).astype(np.float32)      # denoising_utils.py:11
+            target, head = noisy, (img_np[None], noisy[None])
+            eng = _make_engine(method, H, W, "den", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, param_dtype=param_dtype)
+        elif task == "sr":
+            if downsampler != "nearest":      # img_small = downsampler(img_hr) with the run's operator (models/downsampler.py; DESIGN.md section 14)
+                from .downsampler import downsample
+                eng = _make_engine(method, H, W, "sr", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, sr_factor=factor, param_dtype=param_dtype,
+                                   downsampler=downsampler)
+                target = downsample(torch.from_numpy(img_np).cuda(), downsampler, factor).cpu().numpy()
+            else:
+                target = np.ascontiguousarray(img_np[::factor, ::factor])    # nearest /factor decimation (:2095-2099)
+                eng = _make_engine(method, H, W, "sr", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, sr_factor=factor, param_dtype=param_dtype)
+            head = (img_np[None], target)
+        else:
+            theta = np.arange(0, 180.0, theta_step, dtype=np.float32)     # :545
+            eng = _make_engine(method, H, W, "ct", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, theta_deg=theta.tolist())
+            target = torch.empty((len(theta), W), device="cuda")
+            gt_d = torch.from_numpy(img_np).cuda()
+            L.check(L.lib().mfvi_radon_forward(L.ptr(gt_d), L.ptr(eng.theta), 1, H, W, len(theta), L.ptr(target), L.stream_ptr()))
+            head = (img_np[None, None], target.cpu().numpy()[None, None])
+        eng.set_target(torch.from_numpy(target) if isinstance(target, np.ndarray) else target)
+        return img_np, eng, _Book(eng, n_it, img_np, noisy, task=task, factor=factor, downsampler=downsampler), head, None, 1
+    return _fit(task, method, fields, prepare, num_iter, show_every, plot, save, save_path, verbose, predict_samples, calibration, calibration_bins,
+                downsampler, factor)
 
 
 def run_den_mfvi(img="phantom", imsize=(256, 256), p_sigma=0.1, num_iter=5000, lr=3e-4, temp=4e-6, sigma=0.01, input_depth=16, seed=42,
@@ -485,65 +334,24 @@ def run_inp_mfvi(img="phantom", mask=None, imsize=(256, 256), num_iter=5000, lr=
     the colour channels, masked Gaussian NLL.  img: (3, H, W) array in [0, 1] or 'phantom' (three synthetic planes); mask: (1|3, H, W),
     1 = known pixel (the reference ships its masks in data/inpainting/).  save.npz carries the reference's keys for this task
     (img_inpainting, img_mask, mse_corrupted, mse_gt, recons, uncerts, uncerts_ale, psnrs, ssims)."""
-    import torch
-    _check_downsampler("inp", method, unused.get("downsampler", "nearest"))
-    _check_predict(method, predict_samples)
-    _check_calibration(method, calibration, calibration_bins)
-    timestamp = str(time.time())
-    run_dir = os.path.join(save_path, timestamp)
-    if save:
-        os.makedirs(run_dir, exist_ok=False)
-        with open(os.path.join(run_dir, "locals.txt"), "w") as f:
-            for key, val in dict(task="inp", imsize=imsize, num_iter=num_iter, lr=lr, temp=temp, sigma=sigma, input_depth=input_depth,
-                                 seed=seed, show_every=show_every, K=K, save_path=save_path).items():
-                print(key, "=", val, file=f)
-    if isinstance(img, np.ndarray):
-        img_np = np.ascontiguousarray(img, np.float32)
-    else:
-        img_np = np.stack([_load_image(img, imsize, seed + c) for c in range(3)]).astype(np.float32)
-    _, H, W = img_np.shape
-    if mask is None:
-        mask = scratch_mask(H, W, seed)
-    mask_np = np.ascontiguousarray(mask, np.float32)
-    if mask_np.ndim == 2:
-        mask_np = mask_np[None]
-    num_iter += 1                                                     # bayesian_optimization.py:2935
-    eng = _make_engine(method, H, W, "inp", K, input_depth, temp, sigma, lr, seed, net_kwargs, dict(weight_decay=weight_decay, dropout_p=dropout_p, gamma=gamma))
-    eng.set_target(torch.from_numpy(img_np), torch.from_numpy(mask_np))
-    book = _BookInp(eng, num_iter, img_np, mask_np)
-    n_snap = num_iter // show_every + 1
-    recons = np.zeros((n_snap, 3, H, W)); uncerts_epi = np.zeros((n_snap, 3, H, W)); uncerts_ale = np.zeros((n_snap, 1, H, W))
-    t0 = time.perf_counter()
-    for i in range(num_iter):
-        eng.step(after_forward=book.hook(eng, i, eng.chunk))
-        if i % show_every == 0:
-            var, ale, recon = book.snapshot()
-            uncerts_epi[i // show_every] = var; uncerts_ale[i // show_every, 0] = ale; recons[i // show_every] = recon
-            if verbose:
-                nll, kl, loss = eng.losses()
-                print("iter %6d  loss %.5f  nll %.5f  kl %.4e  (%.1f it/s)" % (i, loss, nll, kl, (i + 1) / (time.perf_counter() - t0)))
-    pred = _predict(eng, predict_samples, img_np, run_dir if save else None,
-                    calibration_bins=calibration_bins if calibration else 0) if predict_samples else None
-    cal = _calibrate(run_dir if save else None, img_np, recons, uncerts_epi, uncerts_ale, pred.pop("_calibration") if pred else None,
-                     calibration_bins, mask=mask_np) if calibration else None
-    torch.cuda.synchronize()
-    mse_corrupted, mse_gt, psnrs, ssims = book.results()
-    if save:
-        A.save_npz(run_dir, "inp", method, (img_np, mask_np), mse_corrupted, mse_gt, recons, uncerts_epi, uncerts_ale, psnrs, ssims)
-        with open(os.path.join(run_dir, "locals.txt"), "a") as f:
-            print("max psnr_gt_sm = %.4f, max ssim_gt_sm = %.4f" % (np.nanmax(psnrs[:, 2]), np.nanmax(ssims[:, 2])), file=f)
-            if plot:
-                A.plot_results({method: mse_corrupted}, {method: mse_gt}, {method: psnrs}, {method: ssims}, run_dir, f)
-        if plot:
-            A.snapshot_pngs(run_dir, method, num_iter - 1, mse_corrupted, mse_gt, psnrs, recons[-1], None if method == "dip" else uncerts_epi[-1],
-                            None if method == "dip" else uncerts_ale[-1])
-    res = dict(psnr=float(psnrs[-1, 2]), run_dir=run_dir if save else None, psnrs=psnrs, ssims=ssims, mse_corrupted=mse_corrupted, mse_gt=mse_gt,
-               recons=recons, uncerts=uncerts_epi, uncerts_ale=uncerts_ale, seconds=time.perf_counter() - t0, engine=eng)
-    if pred is not None:
-        res["predictive"] = pred
-    if cal is not None:
-        res["calibration"] = cal
-    return res
+    fields = dict(task="inp", imsize=imsize, num_iter=num_iter, lr=lr, temp=temp, sigma=sigma, input_depth=input_depth, seed=seed,
+                  show_every=show_every, K=K, save_path=save_path)
+
+    def prepare(n_it):
+        import torch
+        if isinstance(img, np.ndarray):
+            img_np = np.ascontiguousarray(img, np.float32)
+        else:
+            img_np = np.stack([_load_image(img, imsize, seed + c) for c in range(3)]).astype(np.float32)
+        _, H, W = img_np.shape
+        mask_np = np.ascontiguousarray(scratch_mask(H, W, seed) if mask is None else mask, np.float32)
+        if mask_np.ndim == 2:
+            mask_np = mask_np[None]
+        eng = _make_engine(method, H, W, "inp", K, input_depth, temp, sigma, lr, seed, net_kwargs, dict(weight_decay=weight_decay, dropout_p=dropout_p, gamma=gamma))
+        eng.set_target(torch.from_numpy(img_np), torch.from_numpy(mask_np))
+        return img_np, eng, _BookInp(eng, n_it, img_np, mask_np), (img_np, mask_np), mask_np, 3
+    return _fit("inp", method, fields, prepare, num_iter, show_every, plot, save, save_path, verbose, predict_samples, calibration, calibration_bins,
+                unused.get("downsampler", "nearest"))
 
 
 run_inp_dip = _sibling("inp", "dip", dict(input_depth=32, lr=2e-3))
@@ -588,6 +396,59 @@ def _save_bookkeeping(book, run_dir, heads):
         book.save_npz(f, fit_dir, heads[f])
 
 
+def _drive_batch(batch, gt, kind, keys, num_iter, show_every, save, save_path, verbose, track=None, heads=None, batch_predict_samples=0,
+                 batch_calibration_bins=0):
+    """What every batched run does with its batch once the targets are set.  kind: "batch" or "volume", the name of the
+    run directory's suffix and of the npz.  track: the keywords of batch.track (None: no bookkeeping), heads: per row the two head arrays of
+    its save.npz.  The loop: step(), the book's snapshot every show_every, and every show_every and at the last iteration losses() (kept as
+    the class returns it) and psnr(gt).  Then dead / final, <kind>.npz = the common keys + keys(losses) (the caller's own, evaluated after the
+    last iteration), _save_bookkeeping, _batch_predict -> the common keys of the result."""
+    n_it = num_iter + 1                                               # bayesian_optimization.py:1291, :2935
+    book = batch.track(gt, n_it, **track) if track is not None else None      # (DESIGN.md section 20)
+    at, psnrs, losses = [], [], []
+    t0 = time.perf_counter()
+    for i in range(n_it):
+        batch.step()
+        if book is not None and i % show_every == 0:
+            book.snapshot()
+        if i % show_every == 0 or i == n_it - 1:
+            losses.append(batch.losses()); at.append(i); psnrs.append(batch.psnr(gt))
+            if verbose:
+                print("iter %6d  psnr_gt_sm %s  (%.1f it/s x %d %s)" % (i, np.array2string(psnrs[-1], precision=2), (i + 1) / (time.perf_counter() - t0),
+                                                                       batch.n_rows, {"batch": "fits", "volume": "slices"}[kind]))
+    dead = batch.dead
+    final = np.where(dead != 0, np.nan, psnrs[-1])
+    run_dir = None
+    if save:
+        run_dir = os.path.join(save_path, "%s_%s" % (time.time(), kind))
+        os.makedirs(run_dir, exist_ok=False)
+        np.savez(os.path.join(run_dir, kind + ".npz"), K=np.int64(batch.K), seed=np.int64(batch.seed), num_iter=np.int64(num_iter), iterations=np.asarray(at),
+                 psnr_gt_sm=np.stack(psnrs), recon=batch.recon().cpu().numpy(), dead=dead, **keys(losses))
+        if book is not None:
+            _save_bookkeeping(book, run_dir, heads)
+    pred = _batch_predict(batch, batch_predict_samples, gt, run_dir, batch_calibration_bins) if batch_predict_samples else None
+    return dict(psnr=[float(x) for x in final], run_dir=run_dir, seconds=time.perf_counter() - t0, dead=dead, predictive=pred)
+
+
+def _nll_kl(losses):
+    """The recorded losses() of an ELBO batch, (nll, kl, loss) per record -> the nll and kl keys of its npz."""
+    return dict(nll=np.stack([l[0] for l in losses]), kl=np.stack([l[1] for l in losses]))
+
+
+def _den_sr_batch(task, jobs, imsize, seed, p_sigma, factor):
+    """The den / sr jobs of one batch -> (gt [F, H, W], targets, the keywords of track(), per fit the head arrays of its save.npz)."""
+    imgs = [_load_image(j["img"], imsize, seed) for j in jobs]
+    H, W = imgs[0].shape
+    if any(im.shape != (H, W) for im in imgs):
+        raise ValueError("the images of one batch must share their size")
+    gt = np.stack(imgs)
+    if task == "den":      # every job's noise as the single-fit runner draws it (same image and seed: the same noisy image)
+        targets = np.stack([np.clip(im + np.random.default_rng(seed + 1).normal(scale=p_sigma, size=im.shape), 0, 1).astype(np.float32) for im in imgs])
+        return gt, targets, dict(noisy=targets), [(g[None], t[None]) for g, t in zip(gt, targets)]
+    targets = np.ascontiguousarray(gt[:, ::factor, ::factor])
+    return gt, targets, dict(noisy=None), [(g[None], t) for g, t in zip(gt, targets)]
+
+
 def run_fit_batch(task, jobs, imsize=(256, 256), p_sigma=0.1, num_iter=5000, lr=3e-4, input_depth=16, seed=42, show_every=100, save=True,
                   save_path="../logs", K=1, factor=4, net_kwargs=None, verbose=False, autotune=True, batch_predict_samples=0,
                   batch_calibration_bins=0, batch_bookkeeping=False, **unused):
@@ -605,46 +466,15 @@ def run_fit_batch(task, jobs, imsize=(256, 256), p_sigma=0.1, num_iter=5000, lr=
         raise NotImplementedError("--fits-per-launch serves denoising and super-resolution, not %r" % (task,))
     if unused.get("downsampler", "nearest") != "nearest":
         raise NotImplementedError("batched fits project with [::f, ::f] only (downsampler='nearest'), not %r" % (unused["downsampler"],))
-    F = len(jobs)
-    imgs = [_load_image(j["img"], imsize, seed) for j in jobs]
-    H, W = imgs[0].shape
-    if any(im.shape != (H, W) for im in imgs):
-        raise ValueError("the images of one batch must share their size")
-    gt = np.stack(imgs)
-    if task == "den":      # every job's noise as the single-fit runner draws it (same image and seed: the same noisy image)
-        targets = np.stack([np.clip(im + np.random.default_rng(seed + 1).normal(scale=p_sigma, size=im.shape), 0, 1).astype(np.float32) for im in imgs])
-    else:
-        targets = np.ascontiguousarray(gt[:, ::factor, ::factor])
+    gt, targets, track, heads = _den_sr_batch(task, jobs, imsize, seed, p_sigma, factor)
     temps, sigmas, lrs = [j["temp"] for j in jobs], [j["sigma"] for j in jobs], [j.get("lr", lr) for j in jobs]
-    fb = FitBatch(H, W, F, task=task, K=K, input_depth=input_depth, temp=temps, sigma=sigmas, lr=lrs, seed=seed, sr_factor=factor,
+    fb = FitBatch(gt.shape[1], gt.shape[2], len(jobs), task=task, K=K, input_depth=input_depth, temp=temps, sigma=sigmas, lr=lrs, seed=seed, sr_factor=factor,
                   net_kwargs=net_kwargs, init="shared", autotune=autotune)      # the reference's candidates all start from one seed
     fb.set_targets(torch.from_numpy(targets))
-    n_it = num_iter + 1                                               # bayesian_optimization.py:1291
-    book = fb.track(gt, n_it, noisy=targets if task == "den" else None) if batch_bookkeeping else None      # 
-    at, psnrs, nlls, kls = [], [], [], []
-    t0 = time.perf_counter()
-    for i in range(n_it):
-        fb.step()
-        if book is not None and i % show_every == 0:
-            book.snapshot()
-        if i % show_every == 0 or i == n_it - 1:
-            nll, kl, _ = fb.losses()
-            at.append(i); psnrs.append(fb.psnr(gt)); nlls.append(nll); kls.append(kl)
-            if verbose:
-                print("iter %6d  psnr_gt_sm %s  (%.1f it/s x %d fits)" % (i, np.array2string(psnrs[-1], precision=2), (i + 1) / (time.perf_counter() - t0), F))
-    dead = fb.dead
-    final = np.where(dead != 0, np.nan, psnrs[-1])
-    run_dir = None
-    if save:
-        run_dir = os.path.join(save_path, "%s_batch" % time.time())
-        os.makedirs(run_dir, exist_ok=False)
-        np.savez(os.path.join(run_dir, "batch.npz"), task=task, temp=np.asarray(temps), sigma=np.asarray(sigmas), lr=np.asarray(lrs),
-                 prior_sigma=np.asarray(fb.prior_sigma), K=np.int64(K), seed=np.int64(seed), num_iter=np.int64(num_iter), iterations=np.asarray(at),
-                 psnr_gt_sm=np.stack(psnrs), nll=np.stack(nlls), kl=np.stack(kls), recon=fb.recon().cpu().numpy(), dead=dead)
-        if book is not None:
-            _save_bookkeeping(book, run_dir, [(gt[f][None], targets[f][None] if task == "den" else targets[f]) for f in range(F)])
-    pred = _batch_predict(fb, batch_predict_samples, gt, run_dir, batch_calibration_bins) if batch_predict_samples else None
-    return dict(psnr=[float(x) for x in final], run_dir=run_dir, seconds=time.perf_counter() - t0, batch=fb, dead=dead, predictive=pred)
+    keys = lambda losses: dict(task=task, temp=np.asarray(temps), sigma=np.asarray(sigmas), lr=np.asarray(lrs), prior_sigma=np.asarray(fb.prior_sigma),
+                               **_nll_kl(losses))
+    return dict(_drive_batch(fb, gt, "batch", keys, num_iter, show_every, save, save_path, verbose, track if batch_bookkeeping else None, heads,
+                             batch_predict_samples, batch_calibration_bins), batch=fb)
 
 
 def fit_batch_job(task, jobs, **kw):
@@ -658,11 +488,11 @@ def run_inpaint_batch(jobs, imsize=(256, 256), num_iter=5000, lr=2e-3, input_dep
     every job at once.  jobs: dicts with img ((3, H, W) array, or what run_inp_mfvi loads), temp, sigma and optionally mask ((1|3, H, W);
     absent: `mask`, the run_params' mask that run_inp_mfvi takes too, else that function's seeded scratch mask) and lr.
     Writes batch.npz with the keys of run_fit_batch plus mask, recon [F, 3, H, W] and
-    ale [F, H, W]; save.npz and the PNG artefacts stay with the single-fit runner.  Returns dict(psnr=[per fit, NaN for a dead fit], ...)."""
+    ale [F, H, W]; save.npz and the PNG artefacts stay with the single-fit runner (an InpaintBatch has no bookkeeping).  Returns
+    dict(psnr=[per fit, NaN for a dead fit], ...)."""
     import torch
     from .inpaintbatch import InpaintBatch
     _check_batch_predict(batch_predict_samples, batch_calibration_bins)
-    F = len(jobs)
     imgs = [np.ascontiguousarray(j["img"], np.float32) if isinstance(j["img"], np.ndarray) else
             np.stack([_load_image(j["img"], imsize, seed + c) for c in range(3)]).astype(np.float32) for j in jobs]
     _, H, W = imgs[0].shape
@@ -675,33 +505,15 @@ def run_inpaint_batch(jobs, imsize=(256, 256), num_iter=5000, lr=2e-3, input_dep
         masks.append(m[None] if m.ndim == 2 else m)
     if any(m.shape != masks[0].shape or m.shape[1:] != (H, W) for m in masks):
         raise ValueError("the masks of one batch must share their shape, (1|3, H, W) each")
-    gt, mask = np.stack(imgs), np.stack(masks)
+    gt = np.stack(imgs)
     temps, sigmas, lrs = [j["temp"] for j in jobs], [j["sigma"] for j in jobs], [j.get("lr", lr) for j in jobs]
-    ib = InpaintBatch(H, W, F, K=K, input_depth=input_depth, temp=temps, sigma=sigmas, lr=lrs, seed=seed, net_kwargs=net_kwargs, init="shared",
+    ib = InpaintBatch(H, W, len(jobs), K=K, input_depth=input_depth, temp=temps, sigma=sigmas, lr=lrs, seed=seed, net_kwargs=net_kwargs, init="shared",
                       autotune=autotune)                               # the reference's candidates all start from one seed
-    ib.set_targets(torch.from_numpy(gt), torch.from_numpy(mask))
-    n_it = num_iter + 1                                               # bayesian_optimization.py:2935
-    at, psnrs, nlls, kls = [], [], [], []
-    t0 = time.perf_counter()
-    for i in range(n_it):
-        ib.step()
-        if i % show_every == 0 or i == n_it - 1:
-            nll, kl, _ = ib.losses()
-            at.append(i); psnrs.append(ib.psnr(gt)); nlls.append(nll); kls.append(kl)
-            if verbose:
-                print("iter %6d  psnr_gt_sm %s  (%.1f it/s x %d fits)" % (i, np.array2string(psnrs[-1], precision=2), (i + 1) / (time.perf_counter() - t0), F))
-    dead = ib.dead
-    final = np.where(dead != 0, np.nan, psnrs[-1])
-    run_dir = None
-    if save:
-        run_dir = os.path.join(save_path, "%s_batch" % time.time())
-        os.makedirs(run_dir, exist_ok=False)
-        np.savez(os.path.join(run_dir, "batch.npz"), task="inp", temp=np.asarray(temps), sigma=np.asarray(sigmas), lr=np.asarray(lrs),
-                 prior_sigma=np.asarray(ib.prior_sigma), K=np.int64(K), seed=np.int64(seed), num_iter=np.int64(num_iter), iterations=np.asarray(at),
-                 psnr_gt_sm=np.stack(psnrs), nll=np.stack(nlls), kl=np.stack(kls), recon=ib.recon().cpu().numpy(), dead=dead,
-                 mask=ib.masks.cpu().numpy(), ale=ib.ale().cpu().numpy())
-    pred = _batch_predict(ib, batch_predict_samples, gt, run_dir, batch_calibration_bins) if batch_predict_samples else None      # (as batch.npz)
-    return dict(psnr=[float(x) for x in final], run_dir=run_dir, seconds=time.perf_counter() - t0, batch=ib, dead=dead, predictive=pred)
+    ib.set_targets(torch.from_numpy(gt), torch.from_numpy(np.stack(masks)))
+    keys = lambda losses: dict(task="inp", temp=np.asarray(temps), sigma=np.asarray(sigmas), lr=np.asarray(lrs), prior_sigma=np.asarray(ib.prior_sigma),
+                               **_nll_kl(losses), mask=ib.masks.cpu().numpy(), ale=ib.ale().cpu().numpy())
+    return dict(_drive_batch(ib, gt, "batch", keys, num_iter, show_every, save, save_path, verbose, batch_predict_samples=batch_predict_samples,
+                             batch_calibration_bins=batch_calibration_bins), batch=ib)
 
 
 def inpaint_batch_job(task, jobs, **kw):
@@ -729,46 +541,16 @@ def run_sibling_batch(task, method, jobs, imsize=None, p_sigma=0.1, num_iter=500
     imsize = imsize or dflt.get("imsize", (256, 256))
     lr = dflt.get("lr", 3e-4) if lr is None else lr
     input_depth = dflt.get("input_depth", 16) if input_depth is None else input_depth
-    F = len(jobs)
-    imgs = [_load_image(j["img"], imsize, seed) for j in jobs]
-    H, W = imgs[0].shape
-    if any(im.shape != (H, W) for im in imgs):
-        raise ValueError("the images of one batch must share their size")
-    gt = np.stack(imgs)
-    if task == "den":      # every job's noise as the single-fit runner draws it (same image and seed: the same noisy image)
-        targets = np.stack([np.clip(im + np.random.default_rng(seed + 1).normal(scale=p_sigma, size=im.shape), 0, 1).astype(np.float32) for im in imgs])
-    else:
-        targets = np.ascontiguousarray(gt[:, ::factor, ::factor])
+    gt, targets, track, heads = _den_sr_batch(task, jobs, imsize, seed, p_sigma, factor)
     hyper = {k: [j.get(k, dflt.get(k, d)) for j in jobs] for k, d in (("weight_decay", 0.0), ("dropout_p", 0.3), ("gamma", 0.996))}
     lrs = [j.get("lr", lr) for j in jobs]
-    sb = SiblingBatch(H, W, F, method, task=task, K=K, input_depth=input_depth, lr=lrs, seed=seed, sr_factor=factor, net_kwargs=net_kwargs,
-                      param_noise_sigma=param_noise_sigma, init="shared", autotune=autotune, **hyper)      # the reference's candidates all start from one seed
+    sb = SiblingBatch(gt.shape[1], gt.shape[2], len(jobs), method, task=task, K=K, input_depth=input_depth, lr=lrs, seed=seed, sr_factor=factor,
+                      net_kwargs=net_kwargs, param_noise_sigma=param_noise_sigma, init="shared", autotune=autotune, **hyper)      # (one seed, as above)
     sb.set_targets(torch.from_numpy(targets))
-    n_it = num_iter + 1                                               # bayesian_optimization.py:1291
-    book = sb.track(gt, n_it, noisy=targets if task == "den" else None) if batch_bookkeeping else None      # 
-    at, psnrs, losses = [], [], []
-    t0 = time.perf_counter()
-    for i in range(n_it):
-        sb.step()
-        if book is not None and i % show_every == 0:
-            book.snapshot()
-        if i % show_every == 0 or i == n_it - 1:
-            at.append(i); psnrs.append(sb.psnr(gt)); losses.append(sb.losses())
-            if verbose:
-                print("iter %6d  psnr_gt_sm %s  (%.1f it/s x %d fits)" % (i, np.array2string(psnrs[-1], precision=2), (i + 1) / (time.perf_counter() - t0), F))
-    dead = sb.dead
-    final = np.where(dead != 0, np.nan, psnrs[-1])
-    run_dir = None
-    if save:
-        run_dir = os.path.join(save_path, "%s_batch" % time.time())
-        os.makedirs(run_dir, exist_ok=False)
-        np.savez(os.path.join(run_dir, "batch.npz"), method=method, task=task, lr=np.asarray(lrs), weight_decay=np.asarray(sb.weight_decays),
-                 dropout_p=np.asarray(sb.dropout_ps), gamma=np.asarray(sb.gammas), K=np.int64(K), seed=np.int64(seed), num_iter=np.int64(num_iter),
-                 iterations=np.asarray(at), psnr_gt_sm=np.stack(psnrs), loss=np.stack(losses), recon=sb.recon().cpu().numpy(), dead=dead)
-        if book is not None:
-            _save_bookkeeping(book, run_dir, [(gt[f][None], targets[f][None] if task == "den" else targets[f]) for f in range(F)])
-    pred = _batch_predict(sb, batch_predict_samples, gt, run_dir, batch_calibration_bins) if batch_predict_samples else None
-    return dict(psnr=[float(x) for x in final], run_dir=run_dir, seconds=time.perf_counter() - t0, batch=sb, dead=dead, predictive=pred)
+    keys = lambda losses: dict(method=method, task=task, lr=np.asarray(lrs), weight_decay=np.asarray(sb.weight_decays), dropout_p=np.asarray(sb.dropout_ps),
+                               gamma=np.asarray(sb.gammas), loss=np.stack(losses))
+    return dict(_drive_batch(sb, gt, "batch", keys, num_iter, show_every, save, save_path, verbose, track if batch_bookkeeping else None, heads,
+                             batch_predict_samples, batch_calibration_bins), batch=sb)
 
 
 def sibling_batch_job(task, jobs, method="dip", **kw):
@@ -776,21 +558,17 @@ def sibling_batch_job(task, jobs, method="dip", **kw):
     return run_sibling_batch(task, method, jobs, **kw)["psnr"]
 
 
-def _sibling_batches(task, jobs, method="dip", **kw):
-    return run_sibling_batch(task, method, jobs, **kw)
+# the batching flags of the CLI: the function that runs one batch of jobs in this process (called with task=, jobs= and the run parameters; the
+# method of --sibling-fits rides in the run parameters) and the worker a device's fresh process resolves by name (fanout.run_jobs)
+BATCH_KINDS = {"fits_per_launch": (run_fit_batch, "mfvi_dip_mia_amd.runner:fit_batch_job"),
+               "inpaint_fits": (run_inpaint_batch, "mfvi_dip_mia_amd.runner:inpaint_batch_job"),
+               "sibling_fits": (run_sibling_batch, "mfvi_dip_mia_amd.runner:sibling_batch_job")}
 
 
-def _fit_batches(task, jobs, **kw):
-    return run_fit_batch(task, jobs, **kw)
-
-
-def _inpaint_batches(task, jobs, **kw):
-    return run_inpaint_batch(jobs, **kw)
-
-
-def _run_batches(task, jobs, n, rp, K, devices, verbose=False, batch_fn=_fit_batches, worker="mfvi_dip_mia_amd.runner:fit_batch_job"):
-    """jobs -> batches of up to n (fanout.group_jobs) -> one batch_fn(task, jobs, ...) each (a FitBatch, or an InpaintBatch), here or dealt
-    round-robin to one worker per device.  Returns (results [(job index, job, psnr)], dropped [(job index, job, why)], batches)."""
+def _run_batches(task, jobs, n, rp, K, devices, verbose=False, kind="fits_per_launch"):
+    """jobs -> batches of up to n (fanout.group_jobs) -> one batch of BATCH_KINDS[kind] each (a FitBatch, an InpaintBatch or a SiblingBatch), here
+    or dealt round-robin to one worker per device.  Returns (results [(job index, job, psnr)], dropped [(job index, job, why)], batches)."""
+    batch_fn, worker = BATCH_KINDS[kind]
     from .fanout import group_jobs, run_jobs
     shapes = {}      # (the size of an image file is known once it is read; every distinct image once)
     for j in jobs:
@@ -808,7 +586,7 @@ def _run_batches(task, jobs, n, rp, K, devices, verbose=False, batch_fn=_fit_bat
     else:
         for bi, bj in enumerate(bjobs):
             try:
-                per_batch[bi] = (batch_fn(task, bj["jobs"], K=K, verbose=verbose, **rp)["psnr"], None)
+                per_batch[bi] = (batch_fn(task=task, jobs=bj["jobs"], K=K, verbose=verbose, **rp)["psnr"], None)
             except (RuntimeError, ValueError) as e:
                 per_batch[bi] = (None, "%s: %s" % (type(e).__name__, e))
     results, dropped = [], []
@@ -864,46 +642,109 @@ def run_ct_volume(volume, temp, sigma, slices_per_launch=None, imsize=(256, 256)
     from .ctvolume import CtVolume
     _check_batch_predict(batch_predict_samples, batch_calibration_bins)
     gt = _load_volume(volume, imsize, seed)
-    D, S = gt.shape[0], gt.shape[1]
     theta = np.arange(0, 180.0, theta_step, dtype=np.float32)         # :545
-    vol = CtVolume(S, D, slices_per_launch=slices_per_launch, K=K, input_depth=input_depth, temp=temp, sigma=sigma, lr=lr, theta_deg=theta.tolist(),
-                   seed=seed, net_kwargs=net_kwargs, autotune=autotune)
+    vol = CtVolume(gt.shape[1], gt.shape[0], slices_per_launch=slices_per_launch, K=K, input_depth=input_depth, temp=temp, sigma=sigma, lr=lr,
+                   theta_deg=theta.tolist(), seed=seed, net_kwargs=net_kwargs, autotune=autotune)
     vol.set_volume(torch.from_numpy(gt))                              # img_radon = forward_radon(img_torch) (:547)
-    n_it = num_iter + 1                                               # as the single-fit runners count
-    book = vol.track(gt, n_it) if batch_bookkeeping else None          # 
-    at, psnrs, nlls, kls = [], [], [], []
-    t0 = time.perf_counter()
-    for i in range(n_it):
-        vol.step()
-        if book is not None and i % show_every == 0:
-            book.snapshot()
-        if i % show_every == 0 or i == n_it - 1:
-            nll, kl, _ = vol.losses()
-            at.append(i); psnrs.append(vol.psnr(gt)); nlls.append(nll); kls.append(kl)
-            if verbose:
-                print("iter %6d  psnr_gt_sm %s  (%.1f it/s x %d slices)" % (i, np.array2string(psnrs[-1], precision=2), (i + 1) / (time.perf_counter() - t0), D))
-    dead = vol.dead
-    final = np.where(dead != 0, np.nan, psnrs[-1])
-    run_dir = None
-    if save:
-        run_dir = os.path.join(save_path, "%s_volume" % time.time())
-        os.makedirs(run_dir, exist_ok=False)
-        np.savez(os.path.join(run_dir, "volume.npz"), theta=theta, sinograms=vol.sinos.cpu().numpy(), temp=np.asarray(vol.temps), sigma=np.asarray(vol.sigmas),
-                 lr=np.asarray(vol.lrs), prior_sigma=np.asarray(vol.prior_sigma), K=np.int64(K), seed=np.int64(seed), num_iter=np.int64(num_iter),
-                 slices_per_launch=np.int64(vol.F), iterations=np.asarray(at), psnr_gt_sm=np.stack(psnrs), nll=np.stack(nlls), kl=np.stack(kls),
-                 recon=vol.recon().cpu().numpy(), dead=dead)
-        if book is not None:      # heads as run_ct_mfvi writes them: img_gt (1, 1, S, S), img_radon (1, 1, T, S)
-            sinos = vol.sinos.cpu().numpy()
-            _save_bookkeeping(book, run_dir, [(gt[d][None, None], sinos[d][None, None]) for d in range(D)])
-    pred = _batch_predict(vol, batch_predict_samples, gt, run_dir, batch_calibration_bins) if batch_predict_samples else None
-    live = final[dead == 0]
-    return dict(psnr=[float(x) for x in final], mean_psnr=float(live.mean()) if live.size else float("nan"), run_dir=run_dir,
-                seconds=time.perf_counter() - t0, volume=vol, dead=dead, predictive=pred)
+    sinos = vol.sinos.cpu().numpy()
+    keys = lambda losses: dict(theta=theta, sinograms=sinos, temp=np.asarray(vol.temps), sigma=np.asarray(vol.sigmas), lr=np.asarray(vol.lrs),
+                               prior_sigma=np.asarray(vol.prior_sigma), slices_per_launch=np.int64(vol.F), **_nll_kl(losses))
+    heads = [(g[None, None], s[None, None]) for g, s in zip(gt, sinos)]      # as run_ct_mfvi writes them: img_gt (1, 1, S, S), img_radon (1, 1, T, S)
+    r = _drive_batch(vol, gt, "volume", keys, num_iter, show_every, save, save_path, verbose, {} if batch_bookkeeping else None, heads,
+                     batch_predict_samples, batch_calibration_bins)
+    live = np.asarray(r["psnr"])[r["dead"] == 0]
+    return dict(r, mean_psnr=float(live.mean()) if live.size else float("nan"), volume=vol)
 
 
 def fit_job(fn_name, **kw):
     """One independent fit in a worker process of the fan-out: run_<task>_<method>(**kw) -> PSNR (the reference's return value)."""
     return globals()[fn_name](**kw)["psnr"]
+
+
+def _check_cli(ap, a):
+    """What main() refuses from the parsed arguments alone, before the config is read and before anything loads the library.  The order is
+    behaviour (the first refusal that applies is the one reported; tests/golden/cli_refusals.json): --sr-downsampler, --batch-bookkeeping,
+    --batch-predict-samples / --batch-calibration, then --sibling-fits, --inpaint-fits, --ct-volume and --fits-per-launch each ahead of the
+    batching flags after it, then --calibration and --predict-samples of a single fit."""
+    on = {"--fits-per-launch": a.fits_per_launch, "--inpaint-fits": a.inpaint_fits, "--sibling-fits": a.sibling_fits, "--ct-volume": a.ct_volume is not None,
+          "--predict-samples": a.predict_samples, "--calibration": a.calibration, "--bo-rounds": a.bo_rounds}
+
+    def count(flag):
+        if on[flag] < 0:
+            ap.error("%s %d: 0 (off) or the number of fits per launch" % (flag, on[flag]))
+
+    def alone(flag, others, why):
+        for other in others:
+            if on[other]:
+                ap.error("%s does not combine with %s (%s)" % (flag, other, why))
+
+    def f32(flag):
+        if a.param_dtype != "f32":
+            ap.error("%s takes float32 parameters (--param-dtype f32)" % flag)
+    if a.sr_downsampler not in (None, "nearest"):
+        if a.task != "super-resolution" or a.bayes != "mfvi":
+            ap.error("--sr-downsampler %s belongs to --task super-resolution --bayes mfvi" % a.sr_downsampler)
+        if a.fits_per_launch:
+            ap.error("--sr-downsampler %s does not combine with --fits-per-launch (batched fits project with [::f, ::f])" % a.sr_downsampler)
+    if a.batch_bookkeeping and not (a.fits_per_launch > 0 or a.sibling_fits > 0 or a.ct_volume is not None):
+        ap.error("--batch-bookkeeping records every fit of a batch: it needs --fits-per-launch, --sibling-fits or --ct-volume (a single fit always "
+                 "keeps these records; --inpaint-fits has no batched bookkeeping)")
+    if a.batch_predict_samples or a.batch_calibration:
+        if a.batch_predict_samples < 0 or a.batch_predict_samples == 1:
+            ap.error("--batch-predict-samples %d: 0 (off) or at least 2" % a.batch_predict_samples)
+        if not (a.fits_per_launch > 0 or a.ct_volume is not None or a.inpaint_fits > 0 or a.sibling_fits > 0):
+            ap.error("--batch-predict-samples / --batch-calibration predict every fit of a batch: they need --fits-per-launch, --ct-volume, --inpaint-fits or "
+                     "--sibling-fits (a single fit takes --predict-samples / --calibration)")
+        if a.sibling_fits > 0 and a.bayes != "mcd":
+            ap.error("--batch-predict-samples / --batch-calibration with --sibling-fits need a posterior to draw from (--bayes mcd), not %s" % a.bayes)
+        if a.batch_calibration and not a.batch_predict_samples:
+            ap.error("--batch-calibration calibrates the posterior predictive maps of --batch-predict-samples N (N >= 2)")
+        if a.batch_calibration and not 1 <= a.calibration_bins <= L.UCE_MAX_BINS:
+            ap.error("--calibration-bins %d outside 1..%d" % (a.calibration_bins, L.UCE_MAX_BINS))
+    count("--sibling-fits")
+    if a.sibling_fits:
+        if a.bayes == "mfvi":
+            ap.error("--sibling-fits batches the DIP, MC-dropout and SGLD fits (--bayes dip, mcd or sgld); mean-field VI fits batch with --fits-per-launch")
+        if a.task not in ("denoising", "super-resolution"):
+            ap.error("--sibling-fits serves denoising and super-resolution, not %s" % a.task)
+        alone("--sibling-fits", ("--fits-per-launch", "--inpaint-fits", "--ct-volume", "--predict-samples", "--calibration"),
+              "SiblingBatch.to_engine(f) serves one fit of a batch")
+        f32("--sibling-fits")
+    count("--inpaint-fits")
+    if a.inpaint_fits:
+        alone("--inpaint-fits", ("--fits-per-launch", "--ct-volume", "--predict-samples", "--calibration"), "InpaintBatch.to_engine(f) serves one fit of a batch")
+        if a.task != "inpainting" or a.bayes != "mfvi":
+            ap.error("--inpaint-fits batches mean-field VI inpainting fits (--task inpainting --bayes mfvi), not --task %s --bayes %s" % (a.task, a.bayes))
+        f32("--inpaint-fits")
+    if a.slices_per_launch is not None and (a.ct_volume is None or a.slices_per_launch < 1):
+        ap.error("--slices-per-launch %d: at least 1, and only with --ct-volume" % a.slices_per_launch)
+    if a.ct_volume is not None:
+        try:
+            parse_ct_volume(a.ct_volume)
+        except ValueError as e:
+            ap.error(str(e))
+        if a.task != "ct" or a.bayes != "mfvi":
+            ap.error("--ct-volume fits a CT stack by mean-field VI (--task ct --bayes mfvi), not --task %s --bayes %s" % (a.task, a.bayes))
+        f32("--ct-volume")
+        alone("--ct-volume", ("--fits-per-launch", "--predict-samples", "--calibration", "--bo-rounds"), "CtVolume.to_engine(d) serves one slice of a volume")
+    count("--fits-per-launch")
+    if a.fits_per_launch:
+        if a.bayes != "mfvi":
+            ap.error("--fits-per-launch batches mean-field VI fits (--bayes mfvi), not %s" % a.bayes)
+        if a.task not in ("denoising", "super-resolution"):
+            ap.error("--fits-per-launch serves denoising and super-resolution, not %s" % a.task)
+        f32("--fits-per-launch")
+        alone("--fits-per-launch", ("--predict-samples",), "FitBatch.to_engine(f).predict serves one fit of a batch")
+        if a.calibration:
+            ap.error("--fits-per-launch does not combine with --calibration")
+    if a.calibration and a.bayes not in CALIBRATION_METHODS:
+        ap.error("--calibration needs uncertainty maps (--bayes mfvi, mcd or sgld), not %s" % a.bayes)
+    if a.calibration and not 1 <= a.calibration_bins <= L.UCE_MAX_BINS:
+        ap.error("--calibration-bins %d outside 1..%d" % (a.calibration_bins, L.UCE_MAX_BINS))
+    if a.predict_samples and a.bayes not in PREDICT_METHODS:
+        ap.error("--predict-samples needs a posterior to draw from (--bayes mfvi or mcd), not %s" % a.bayes)
+    if a.predict_samples < 0 or a.predict_samples == 1:
+        ap.error("--predict-samples %d: 0 (off) or at least 2" % a.predict_samples)
 
 
 def main(argv=None):
@@ -953,86 +794,7 @@ def main(argv=None):
                          "metrics; nearest = [::f, ::f] (default, or the config's run_params.downsampler), lanczos2 / lanczos3 = the "
                          "anti-aliasing Downsampler of the reference's models/downsampler.py")
     a = ap.parse_args(argv)
-    if a.sr_downsampler not in (None, "nearest"):      # refused before anything loads the library
-        if a.task != "super-resolution" or a.bayes != "mfvi":
-            ap.error("--sr-downsampler %s belongs to --task super-resolution --bayes mfvi" % a.sr_downsampler)
-        if a.fits_per_launch:
-            ap.error("--sr-downsampler %s does not combine with --fits-per-launch (batched fits project with [::f, ::f])" % a.sr_downsampler)
-    if a.batch_bookkeeping and not (a.fits_per_launch > 0 or a.sibling_fits > 0 or a.ct_volume is not None):      # refused before anything loads the library
-        ap.error("--batch-bookkeeping records every fit of a batch: it needs --fits-per-launch, --sibling-fits or --ct-volume (a single fit always "
-                 "keeps these records; --inpaint-fits has no batched bookkeeping)")
-    if a.batch_predict_samples or a.batch_calibration:      # refused before anything loads the library
-        if a.batch_predict_samples < 0 or a.batch_predict_samples == 1:
-            ap.error("--batch-predict-samples %d: 0 (off) or at least 2" % a.batch_predict_samples)
-        if not (a.fits_per_launch > 0 or a.ct_volume is not None or a.inpaint_fits > 0 or a.sibling_fits > 0):
-            ap.error("--batch-predict-samples / --batch-calibration predict every fit of a batch: they need --fits-per-launch, --ct-volume, --inpaint-fits or "
-                     "--sibling-fits (a single fit takes --predict-samples / --calibration)")
-        if a.sibling_fits > 0 and a.bayes != "mcd":
-            ap.error("--batch-predict-samples / --batch-calibration with --sibling-fits need a posterior to draw from (--bayes mcd), not %s" % a.bayes)
-        if a.batch_calibration and not a.batch_predict_samples:
-            ap.error("--batch-calibration calibrates the posterior predictive maps of --batch-predict-samples N (N >= 2)")
-        if a.batch_calibration and not 1 <= a.calibration_bins <= L.UCE_MAX_BINS:
-            ap.error("--calibration-bins %d outside 1..%d" % (a.calibration_bins, L.UCE_MAX_BINS))
-    if a.sibling_fits < 0:
-        ap.error("--sibling-fits %d: 0 (off) or the number of fits per launch" % a.sibling_fits)
-    if a.sibling_fits:      # refused before anything loads the library, and ahead of the other batching flags' own refusals
-        if a.bayes == "mfvi":
-            ap.error("--sibling-fits batches the DIP, MC-dropout and SGLD fits (--bayes dip, mcd or sgld); mean-field VI fits batch with --fits-per-launch")
-        if a.task not in ("denoising", "super-resolution"):
-            ap.error("--sibling-fits serves denoising and super-resolution, not %s" % a.task)
-        for flag, on in (("--fits-per-launch", a.fits_per_launch), ("--inpaint-fits", a.inpaint_fits), ("--ct-volume", a.ct_volume is not None),
-                         ("--predict-samples", a.predict_samples), ("--calibration", a.calibration)):
-            if on:
-                ap.error("--sibling-fits does not combine with %s (SiblingBatch.to_engine(f) serves one fit of a batch)" % flag)
-        if a.param_dtype != "f32":
-            ap.error("--sibling-fits takes float32 parameters (--param-dtype f32)")
-    if a.inpaint_fits < 0:
-        ap.error("--inpaint-fits %d: 0 (off) or the number of fits per launch" % a.inpaint_fits)
-    if a.inpaint_fits:      # refused before anything loads the library, and ahead of the other batching flags' own refusals
-        for flag, on in (("--fits-per-launch", a.fits_per_launch), ("--ct-volume", a.ct_volume is not None), ("--predict-samples", a.predict_samples),
-                         ("--calibration", a.calibration)):
-            if on:
-                ap.error("--inpaint-fits does not combine with %s (InpaintBatch.to_engine(f) serves one fit of a batch)" % flag)
-        if a.task != "inpainting" or a.bayes != "mfvi":
-            ap.error("--inpaint-fits batches mean-field VI inpainting fits (--task inpainting --bayes mfvi), not --task %s --bayes %s" % (a.task, a.bayes))
-        if a.param_dtype != "f32":
-            ap.error("--inpaint-fits takes float32 parameters (--param-dtype f32)")
-    if a.slices_per_launch is not None and (a.ct_volume is None or a.slices_per_launch < 1):
-        ap.error("--slices-per-launch %d: at least 1, and only with --ct-volume" % a.slices_per_launch)
-    if a.ct_volume is not None:      # refused before anything loads the library
-        try:
-            parse_ct_volume(a.ct_volume)
-        except ValueError as e:
-            ap.error(str(e))
-        if a.task != "ct" or a.bayes != "mfvi":
-            ap.error("--ct-volume fits a CT stack by mean-field VI (--task ct --bayes mfvi), not --task %s --bayes %s" % (a.task, a.bayes))
-        if a.param_dtype != "f32":
-            ap.error("--ct-volume takes float32 parameters (--param-dtype f32)")
-        for flag, on in (("--fits-per-launch", a.fits_per_launch), ("--predict-samples", a.predict_samples), ("--calibration", a.calibration),
-                         ("--bo-rounds", a.bo_rounds)):
-            if on:
-                ap.error("--ct-volume does not combine with %s (CtVolume.to_engine(d) serves one slice of a volume)" % flag)
-    if a.fits_per_launch < 0:
-        ap.error("--fits-per-launch %d: 0 (off) or the number of fits per launch" % a.fits_per_launch)
-    if a.fits_per_launch:      # refused before anything loads the library
-        if a.bayes != "mfvi":
-            ap.error("--fits-per-launch batches mean-field VI fits (--bayes mfvi), not %s" % a.bayes)
-        if a.task not in ("denoising", "super-resolution"):
-            ap.error("--fits-per-launch serves denoising and super-resolution, not %s" % a.task)
-        if a.param_dtype != "f32":
-            ap.error("--fits-per-launch takes float32 parameters (--param-dtype f32)")
-        if a.predict_samples:
-            ap.error("--fits-per-launch does not combine with --predict-samples (FitBatch.to_engine(f).predict serves one fit of a batch)")
-        if a.calibration:
-            ap.error("--fits-per-launch does not combine with --calibration")
-    if a.calibration and a.bayes not in CALIBRATION_METHODS:
-        ap.error("--calibration needs uncertainty maps (--bayes mfvi, mcd or sgld), not %s" % a.bayes)
-    if a.calibration and not 1 <= a.calibration_bins <= L.UCE_MAX_BINS:
-        ap.error("--calibration-bins %d outside 1..%d" % (a.calibration_bins, L.UCE_MAX_BINS))
-    if a.predict_samples and a.bayes not in PREDICT_METHODS:
-        ap.error("--predict-samples needs a posterior to draw from (--bayes mfvi or mcd), not %s" % a.bayes)
-    if a.predict_samples < 0 or a.predict_samples == 1:
-        ap.error("--predict-samples %d: 0 (off) or at least 2" % a.predict_samples)
+    _check_cli(ap, a)
     cands, rp, cfg_devices = load_config(a.config, a.bayes, with_devices=True)
     short = {"denoising": "den", "super-resolution": "sr", "ct": "ct", "inpainting": "inp"}[a.task]
     fn_name = "run_%s_%s" % (short, a.bayes)
@@ -1077,9 +839,9 @@ def main(argv=None):
     rp.pop("img", None)
     jobs = [dict(cand, img=im) for im in imgs for cand in cands]
     devices = a.devices.split(",") if a.devices else cfg_devices
-    batch_kw = dict(batch_fn=_inpaint_batches, worker="mfvi_dip_mia_amd.runner:inpaint_batch_job") if a.inpaint_fits else {}
+    kind = next((k for k in BATCH_KINDS if getattr(a, k)), None)      # (the batching flags exclude one another: _check_cli)
+    per = getattr(a, kind) if kind else 0
     if a.sibling_fits:      # the method rides in the run parameters to the batch function (here, or in a worker of the fan-out)
-        batch_kw = dict(batch_fn=_sibling_batches, worker="mfvi_dip_mia_amd.runner:sibling_batch_job")
         rp["method"] = a.bayes
     if a.bo_rounds > 0:
         # bo() of the reference (bayesian_optimization.py:3727-3880): rounds of [fits of the candidates over the devices -> GP -> new candidates]
@@ -1091,8 +853,8 @@ def main(argv=None):
 
         def evaluate(cand_list):
             jb = [dict(zip(keys, c), img=imgs[0]) for c in cand_list]
-            if a.fits_per_launch or a.inpaint_fits or a.sibling_fits:      # a round's candidates form batches
-                res, _, _ = _run_batches(short, jb, a.fits_per_launch or a.inpaint_fits or a.sibling_fits, rp, a.k, devices, **batch_kw)
+            if kind:      # a round's candidates form batches
+                res, _, _ = _run_batches(short, jb, per, rp, a.k, devices, kind=kind)
                 return [(tuple(job[k] for k in keys), y) for _, job, y in res]
             if devices:
                 from .fanout import run_jobs
@@ -1100,20 +862,15 @@ def main(argv=None):
                 return [(tuple(job[k] for k in keys), y) for _, job, y in res]
             return [(c, fn(K=a.k, verbose=False, **j, **rp)["psnr"]) for c, j in zip(cand_list, jb)]
         return _bo.bo(bo_params, evaluate, n_rounds=a.bo_rounds)
-    if a.fits_per_launch or a.inpaint_fits or a.sibling_fits:
-        from .fanout import print_table
-        per = a.fits_per_launch or a.inpaint_fits or a.sibling_fits
-        results, dropped, batches = _run_batches(short, jobs, per, rp, a.k, devices, verbose=True, **batch_kw)
-        print("%d fits in %d batches of up to %d" % (len(jobs), len(batches), per))
-        print_table(results, list(BO_KEYS[a.bayes]))
-        for i, job, why in dropped:
-            print("dropped fit %d %s: %s" % (i, {k: v for k, v in job.items() if k != "img"}, why))
-        return results
-    if devices:
-        # independent fits over the node's GPUs (bayesian_optimization.py:3760-3781, eval_result.py:27-53): no per-step communication,
-        # one final gather of (candidate, psnr), NaNs dropped
+    if kind or devices:
         from .fanout import run_jobs, print_table
-        results, dropped = run_jobs(jobs, devices, "mfvi_dip_mia_amd.runner:fit_job", dict(rp, fn_name=fn_name, K=a.k))
+        if kind:
+            results, dropped, batches = _run_batches(short, jobs, per, rp, a.k, devices, verbose=True, kind=kind)
+            print("%d fits in %d batches of up to %d" % (len(jobs), len(batches), per))
+        else:
+            # independent fits over the node's GPUs (bayesian_optimization.py:3760-3781, eval_result.py:27-53): no per-step communication,
+            # one final gather of (candidate, psnr), NaNs dropped
+            results, dropped = run_jobs(jobs, devices, "mfvi_dip_mia_amd.runner:fit_job", dict(rp, fn_name=fn_name, K=a.k))
         print_table(results, list(BO_KEYS[a.bayes]))
         for i, job, why in dropped:
             print("dropped fit %d %s: %s" % (i, {k: v for k, v in job.items() if k != "img"}, why))
