@@ -570,6 +570,30 @@ size_t mfvi_pair_metrics_scratch_bytes(int n_pairs, int H, int W);
 int mfvi_pair_metrics(const float* x, int64_t x_stride, const float* y, int64_t y_stride, int n_pairs, int H, int W, int want_ssim,
                       void* scratch, double* sums, int64_t sums_stride, void* stream);
 
+/* ---- total-variation regulariser (utils/sr_utils.py:84-94 tv_loss) ------------------------------------------------- */
+/* Per plane x[H][W] and every cell (i < H-1, j < W-1): dh = x[i][j+1] - x[i][j], dw = x[i+1][j] - x[i][j], u = dh^2 + dw^2,
+ *   TV_beta(x) = sum over the cells of u^beta                           (a sum, not a mean; beta = 0.5 is the isotropic TV)
+ *   dTV/dx[i][j] = g(i,j) (-dh(i,j) - dw(i,j)) + g(i,j-1) dh(i,j-1) + g(i-1,j) dw(i-1,j),        g = 2 beta u^(beta-1)
+ * The last row's horizontal and the last column's vertical differences belong to no cell, x[H-1][W-1] has gradient 0, and H == 1 or
+ * W == 1 gives 0 and a zero gradient.  ONE DEPARTURE from the reference: for beta < 1 its autograd returns NaN (inf * 0) at every pixel
+ * that touches a cell with u == 0; here g = 0 where u == 0.  The value is unaffected.
+ * out / dout [n_fits * S][C][H][W]; the term acts on channel `channel` of every sample, fit f owns the samples f S .. f S + S - 1:
+ *   dout[:, channel]  = (accumulate ? dout[:, channel] : 0) + grad_scale * weight[f * weight_stride] * dTV/dout     (dout may be NULL)
+ *   tv[f]            += sum over the fit's S samples of TV_beta, unweighted                                         (tv may be NULL)
+ * weight is read from DEVICE memory (weight_stride 1: one float per fit, 0: one for all): per-fit weights, the upstream gradient of an
+ * autograd backward without a host sync, and graph capture.  With accumulate, a fit whose grad_scale * weight is exactly 0 keeps its dout
+ * to the bit (nothing is added, not even 0 * NaN).  The other channels of dout are never touched.  The gradient is a gather over
+ * the three cells of a pixel in the order above: no atomics, bit-identical from call to call.  The value: fp32 per cell, fp64 sums; each
+ * block (a 16 x 64 tile of one plane) writes one partial to its own slot of scratch and a second launch with one block per fit adds the
+ * fit's partials in index order (skipped when tv is NULL): no floating-point atomics.  Fit f's results depend neither on n_fits nor on the
+ * other fits (a NaN stays in its fit).  beta == 0.5 and beta == 1 take cheap paths (rsqrt / none), any other beta > 0 uses powf.
+ * scratch: mfvi_tv_term_scratch_bytes(n_fits, S, H, W) bytes, 8-byte aligned (0 for a shape mfvi_tv_term refuses).  Null out, weight or
+ * scratch, dout and tv both NULL, n_fits * S outside 1..65535, channel outside 0..C-1, beta <= 0 or not finite, H or W < 1, weight_stride
+ * not 0 or 1: -1 and mfvi_last_error(), no launch. */
+size_t mfvi_tv_term_scratch_bytes(int n_fits, int S, int H, int W);
+int mfvi_tv_term(const float* out, int n_fits, int S, int C, int H, int W, int channel, float beta, const float* weight, int weight_stride,
+                 float grad_scale, int accumulate, float* dout, double* tv, void* scratch, void* stream);
+
 const char* mfvi_last_error(void);
 int mfvi_abi_version(void);
 

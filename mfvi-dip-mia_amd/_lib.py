@@ -124,6 +124,8 @@ SIGNATURES = {
     "mfvi_bookkeep_fits": (_I, [_P, _I, _I, _I, _I, _I, _P, _F, _I, _P, _P, _P, _P, _P, _P]),
     "mfvi_pair_metrics_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
     "mfvi_pair_metrics": (_I, [_P, _I64, _P, _I64, _I, _I, _I, _I, _P, _P, _I64, _P]),
+    "mfvi_tv_term_scratch_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "mfvi_tv_term": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _P, _I, _F, _I, _P, _P, _P, _P]),
     "mfvi_last_error": (C.c_char_p, []),
     "mfvi_abi_version": (_I, []),
 }

@@ -8,7 +8,7 @@ from . import runner
 from .nets import Concat, get_net, skip
 
 __all__ = ["build", "FitBatch", "Plan", "Program", "skip_program", "_lib", "engine", "sharding", "runner", "Concat", "get_net", "skip", "MeanFieldVI", "FusedNet", "Conv2dRT", "Conv2dLRT",
-           "gaussian_nll", "gaussian_nll_inpainting", "uncert_regression_gal", "uceloss", "Downsampler", "lanczos_taps", "FastRadonTransform", "CtVolume", "InpaintBatch", "SiblingBatch", "BatchBook"]
+           "gaussian_nll", "gaussian_nll_inpainting", "uncert_regression_gal", "uceloss", "Downsampler", "lanczos_taps", "FastRadonTransform", "CtVolume", "InpaintBatch", "SiblingBatch", "BatchBook", "tv_loss"]
 
 
 def __getattr__(name):          # bayes.py needs torch.nn at import: keep `import mfvi_dip_mia_amd` light
@@ -36,4 +36,7 @@ def __getattr__(name):          # bayes.py needs torch.nn at import: keep `impor
     if name == "BatchBook":
         from .batchbook import BatchBook
         return BatchBook
+    if name == "tv_loss":
+        from .tv import tv_loss
+        return tv_loss
     raise AttributeError(name)

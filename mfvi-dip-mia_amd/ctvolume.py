@@ -57,10 +57,12 @@ class CtVolume(ElboRowBatch):
     sinos = None
 
     def __init__(self, S, n_slices, slices_per_launch=None, K=1, input_depth=16, temp=1.0, sigma=0.1, lr=1e-3, theta_deg=None, seed=1,
-                 net_kwargs=None, init="per_fit", autotune=True):
+                 net_kwargs=None, init="per_fit", autotune=True, tv_weight=0.0, tv_beta=0.5):
         self.S, self.F, self.temps, self.sigmas, self.lrs, self.theta_list = check_args(S, n_slices, slices_per_launch, K, temp, sigma, lr,
                                                                                         theta_deg, init)
         self.D, self.T = int(n_slices), len(self.theta_list)
+        from .tv import check_tv
+        self.tv_weights, self.tv_beta = check_tv(tv_weight, tv_beta, "ct", n=self.D)      # a scalar, or one weight per slice
         self.net_kwargs = dict(net_kwargs or {})
         self._allocate(self.D, self.F, K, self.S, self.S, 1, input_depth, self.net_kwargs, seed, init, autotune)      # the CT net: n_channels = 1
 
@@ -100,7 +102,7 @@ class CtVolume(ElboRowBatch):
     def _make_engine(self, d, autotune):
         from .engine import ElboEngine
         return ElboEngine(self.S, self.S, task="ct", K=self.K, input_depth=self.input_depth, temp=self.temps[d], sigma=self.sigmas[d],
-                          lr=self.lrs[d], seed=self.seed, theta_deg=self.theta_list, net_kwargs=self.net_kwargs, autotune=autotune)
+                          lr=self.lrs[d], seed=self.seed, theta_deg=self.theta_list, net_kwargs=self.net_kwargs, autotune=autotune, **self._tv_kw(d))
 
     def _hand_target(self, eng, d):
         if self.sinos is not None:

@@ -27,7 +27,10 @@ INP_NET = dict(nd=(16, 32, 64, 128, 128, 128), nu=(16, 32, 64, 128, 128, 128), n
 class ElboEngine:
     def __init__(self, H, W, task=TASK_DEN, K=1, input_depth=16, temp=1.0, sigma=0.1, lr=1e-3, seed=1, sr_factor=4,
                  theta_deg=None, rank=0, world_size=1, process_group=None, samples_per_launch=None, net_kwargs=None,
-                 autotune=True, param_dtype="f32", downsampler="nearest"):
+                 autotune=True, param_dtype="f32", downsampler="nearest", tv_weight=0.0, tv_beta=0.5):
+        # the total-variation term on the image channel of every sample; refused before anything touches the library
+        from .tv import check_tv
+        self.tv_weight, self.tv_beta = check_tv(tv_weight, tv_beta, task)
         # the SR forward operator: "nearest" = out[..., ::f, ::f] (what the reference's MFVI runner uses), "lanczos2" / "lanczos3" = the
         # anti-aliasing Downsampler of models/downsampler.py; refused before anything touches the library
         if downsampler != "nearest":
@@ -84,7 +87,7 @@ class ElboEngine:
         self.z = torch.empty_like(self.z0)
         self.out = torch.empty((self.chunk, n_out, H, W), dtype=torch.float32, device=dev)
         self.dout = torch.empty_like(self.out)
-        self.acc = self._gbuf[4 * n_g:].view(torch.float64)                # [0] nll sum, [1] kl
+        self.acc = self._gbuf[4 * n_g:].view(torch.float64)                # [0] nll sum, [1] kl, [2] sum over the local samples of TV (tv_weight > 0)
         self.upd_scratch = torch.zeros(L.lib().mfvi_elbo_update_scratch_bytes(), dtype=torch.uint8, device=dev)
         self.t_applied = torch.zeros(1, dtype=torch.int32, device=dev)    # CT: optimizer steps actually taken (the NaN guard skips some)
         self.sr_factor = sr_factor
@@ -92,6 +95,10 @@ class ElboEngine:
             from .downsampler import c_taps
             self._ds_taps, self._ds_ntaps = c_taps(downsampler, sr_factor)
             self.ds_scratch = torch.empty(self.chunk * 2 * (H // sr_factor) * (W // sr_factor), dtype=torch.float32, device=dev)
+        self._tv = None
+        if self.tv_weight > 0.0:          # the weight on the device (the launch depends on no host value), the value in acc[2]
+            from .tv import TvTerm
+            self._tv = TvTerm([self.tv_weight], self.tv_beta, 1, self.chunk, H, W, acc=self.acc[2:3])
         self.theta = None
         if task == TASK_CT:
             th = theta_deg if theta_deg is not None else list(range(0, 180, 4))        # bayesian_optimization.py:545
@@ -258,6 +265,8 @@ class ElboEngine:
             n = min(self.chunk, self.K_local - c0)
             self.plan.forward(self.mu, self.rho, self.bn, zsrc, self.seed, step, self.k0 + c0, n, self.sample_weights, self.out)
             self._loss_and_dout(n)
+            if self._tv is not None:      # dout[:, 0] += tv_weight / K * dTV/dout[:, 0] behind the data term; acc[2] += the chunk's TV
+                self._tv.add(self.out[:n], self.dout[:n], 0, 1, n, 1.0 / self.K)
             if after_forward is not None and c0 + n >= self.K_local:
                 after_forward(n)       # self.out holds the n samples of the LAST launch, final in stream order here: work that only reads it can overlap the backward pass
             split = exchange and getattr(self, "_ov", None) is not None and c0 + n >= self.K_local      # the gradients are final after the LAST launch
@@ -309,6 +318,8 @@ class ElboEngine:
         """The single exchange of the K-sharded step: grads (+ the NLL scalar) summed over ranks."""
         torch, ov, n_vi = self.torch, getattr(self, "_ov", None), self.n_vi
         self.grads[self.n_params] = self.acc[0].float()
+        if self._tv is not None:          # the local TV sum rides in the second scalar slot
+            self.grads[self.n_params + 1] = self.acc[2].float()
         force = getattr(self, "_force_exchange", False)
         if ov is None:
             allreduce_sum_(self.grads, self.pg, force)
@@ -437,6 +448,15 @@ class ElboEngine:
             nll = float(self.acc[0]) / self.K
         kl = float(self.acc[1])
         return nll, kl, nll + self.temp * kl
+
+    def tv(self):
+        """Mean over the K samples of TV_beta(out_k[0]) at the last grad_only/step (0.0 with tv_weight = 0: the term did not run) — forces
+        a device sync.  The regulariser's share of the objective is tv_weight * tv(); losses() does not include it."""
+        if self._tv is None:
+            return 0.0
+        if self.world > 1:
+            return float(self.grads[self.n_params + 1]) / self.K
+        return float(self.acc[2]) / self.K
 
 
 METHOD_DIP, METHOD_MCD, METHOD_SGLD = "dip", "mcd", "sgld"

@@ -38,8 +38,10 @@ class FitBatch(ElboRowBatch):
     targets = None
 
     def __init__(self, H, W, n_fits, task="den", K=1, input_depth=16, temp=1.0, sigma=0.1, lr=1e-3, seed=1, sr_factor=4, net_kwargs=None,
-                 init="per_fit", autotune=True):
+                 init="per_fit", autotune=True, tv_weight=0.0, tv_beta=0.5):
         self.temps, self.sigmas, self.lrs = check_args(H, W, n_fits, task, K, temp, sigma, lr, init)
+        from .tv import check_tv
+        self.tv_weights, self.tv_beta = check_tv(tv_weight, tv_beta, task, n=int(n_fits))      # a scalar, or one weight per fit
         if task == "sr" and (sr_factor < 1 or H % sr_factor or W % sr_factor):
             raise ValueError("sr_factor %r does not divide %dx%d" % (sr_factor, H, W))
         self.task, self.F, self.sr_factor = task, int(n_fits), int(sr_factor)
@@ -66,7 +68,7 @@ class FitBatch(ElboRowBatch):
     def _make_engine(self, f, autotune):
         from .engine import ElboEngine
         return ElboEngine(self.H, self.W, task=self.task, K=self.K, input_depth=self.input_depth, temp=self.temps[f], sigma=self.sigmas[f],
-                          lr=self.lrs[f], seed=self.seed, sr_factor=self.sr_factor, net_kwargs=self.net_kwargs, autotune=autotune)
+                          lr=self.lrs[f], seed=self.seed, sr_factor=self.sr_factor, net_kwargs=self.net_kwargs, autotune=autotune, **self._tv_kw(f))
 
     def _hand_target(self, eng, f):
         if self.targets is not None:

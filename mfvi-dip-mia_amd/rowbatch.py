@@ -58,6 +58,9 @@ class RowBatch:
     sample_weights = True       # plan.forward / backward draw w = mu + softplus(rho) eps (False: w = mu, the point-weight siblings)
     shared_gt = True            # psnr(gt) takes one [H, W] ground truth for all rows
     row_name = "fit"            # what to_engine calls a row when it refuses one
+    tv_weights = None           # per-row weights of the total-variation term (tv.check_tv); None or all 0: the term does not exist
+    tv_beta = 0.5
+    _tv = None
 
     def _allocate(self, n_rows, rows_per_launch, K, H, W, C_out, input_depth, net_kwargs, seed, init, autotune):
         """Everything a batch of n_rows rows holds on the device, rows_per_launch of them per set of launches; then init_params(), the
@@ -81,10 +84,14 @@ class RowBatch:
         self.params, self.m, self.v = self._pbuf[:, :self.n_params], self._mbuf[:, :self.n_params], self._vbuf[:, :self.n_params]
         # gradients and the float64 data-term accumulators of ALL rows in one allocation: one fill launch clears both per iteration (the
         # generic kernels accumulate into the rows by atomics, so the rows must start from zero)
-        self._gbuf = torch.zeros(4 * R * self.stride + 8 * R, dtype=torch.uint8, device=dev)
+        tv_on = self.tv_weights is not None and any(w > 0.0 for w in self.tv_weights)      # its accumulators [n_rows] behind the data term's
+        self._gbuf = torch.zeros(4 * R * self.stride + 8 * R * (2 if tv_on else 1), dtype=torch.uint8, device=dev)
         self._grows = self._gbuf[:4 * R * self.stride].view(torch.float32).view(R, self.stride)
         self.grads = self._grows[:, :self.n_params]
-        self.nll_acc = self._gbuf[4 * R * self.stride:].view(torch.float64)
+        self.nll_acc = self._gbuf[4 * R * self.stride:4 * R * self.stride + 8 * R].view(torch.float64)
+        if tv_on:
+            from .tv import TvTerm
+            self._tv = TvTerm(self.tv_weights, self.tv_beta, F, K, H, W, acc=self._gbuf[4 * R * self.stride + 8 * R:].view(torch.float64))
         self.dead_dev = torch.zeros(R, dtype=torch.int32, device=dev)
         self.z0 = torch.empty((R, input_depth, H, W), dtype=torch.float32, device=dev)
         # what one group needs, shared by the groups like the plan's workspace
@@ -199,6 +206,8 @@ class RowBatch:
             out, dout = self.out[:n], self.dout[:n]
             self.plan.forward(mu, rho, bn, zsrc, self.seed, step, k0, n, sw, out)
             self._data_term(d0, nd, out, dout)
+            if self._tv is not None:     # dout[:, 0] += tv_weight[row] / K * dTV/dout[:, 0]; the rows' TV sums
+                self._tv.add(out, dout, d0, nd, self.K, 1.0 / self.K)
             if ema:
                 self._ema(d0, nd)
             self.plan.backward(mu, rho, bn, zsrc, self.seed, step, k0, n, dout, g[:nv], g[nv:], g[2 * nv:], sw)
@@ -221,6 +230,18 @@ class RowBatch:
     def dead(self):
         """[n_rows] int32: 1 for a row that met a non-finite data term (sticky; its parameters stopped there)."""
         return self.dead_dev.cpu().numpy()
+
+    def tv(self):
+        """[n_rows]: mean over a row's K samples of TV_beta(out_k[0]) at the last grad_only / step (zeros when no row has a weight: the
+        term did not run) -- forces a device sync.  A row's share of its objective is tv_weight[row] * tv()[row]; losses() leaves it out."""
+        import numpy as np
+        if self._tv is None:
+            return np.zeros(self.n_rows)
+        return self._tv.acc.cpu().numpy() / self.K
+
+    def _tv_kw(self, f):
+        """The keywords that hand row f's term to its standalone engine."""
+        return dict(tv_weight=self.tv_weights[f], tv_beta=self.tv_beta) if self.tv_weights is not None else {}
 
     def recon(self):
         """clip(ema[:, 0], 0, 1) [n_rows, H, W]: the smoothed reconstruction of every row."""

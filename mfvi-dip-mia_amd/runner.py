@@ -84,6 +84,14 @@ def _check_downsampler(task, method, downsampler, factor=4):
     check_geometry(downsampler, factor)
 
 
+def _tv_fields(tv_weight, tv_beta, task):
+    """The total-variation term of a single-fit run, refused before anything is written or loaded -> the keywords
+    of the engine and the extra locals.txt fields: both empty with the term off."""
+    from .tv import check_tv
+    w, b = check_tv(tv_weight, tv_beta, task)
+    return dict(tv_weight=w, tv_beta=b) if w > 0.0 else {}
+
+
 def _check_predict(method, predict_samples):
     if predict_samples and method not in PREDICT_METHODS:
         raise ValueError("predict_samples=%d: posterior predictive sampling needs a posterior to draw from (mfvi, mcd), not %r"
@@ -189,7 +197,8 @@ def _fit(task, method, fields, prepare, num_iter, show_every, plot, save, save_p
             uncerts_epi[i // show_every] = var; uncerts_ale[i // show_every, 0] = ale; recons[i // show_every] = recon
             if verbose:
                 nll, kl, loss = eng.losses()
-                print("iter %6d  loss %.5f  nll %.5f  kl %.4e  (%.1f it/s)" % (i, loss, nll, kl, (i + 1) / (time.perf_counter() - t0)))
+                tv = "  tv %.5f (weight %g)" % (eng.tv(), eng.tv_weight) if eng.tv_weight > 0.0 else ""
+                print("iter %6d  loss %.5f  nll %.5f  kl %.4e%s  (%.1f it/s)" % (i, loss, nll, kl, tv, (i + 1) / (time.perf_counter() - t0)))
             if plot and save and task != "inp":
                 pngs(i, book.results()[:3], recon.reshape(C, H, W), var.reshape(C, H, W), ale[None])
     pred = _predict(eng, predict_samples, gt, run_dir if save else None, drop_ale=task == "ct",
@@ -219,17 +228,18 @@ def _fit(task, method, fields, prepare, num_iter, show_every, plot, save, save_p
 
 def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, seed, show_every, plot, save, save_path, K, factor=4,
          theta_step=4.0, verbose=False, net_kwargs=None, method="mfvi", weight_decay=0.0, dropout_p=0.3, gamma=0.996, param_dtype="f32", predict_samples=0,
-         calibration=False, calibration_bins=15, downsampler="nearest", **unused):
+         calibration=False, calibration_bins=15, downsampler="nearest", tv_weight=0.0, tv_beta=0.5, **unused):
     """What _fit needs of a den / sr / ct run: its locals.txt fields and, once the run directory stands, the image, the task's target and engine,
     the _Book and the two head arrays as the reference writes them per task: den img_gt / img_noisy (:1438), sr img_hr / img_lr (:2258), ct
     img_gt / img_radon (:643) with the reference's shapes (get_image() arrays are (1, H, W), img_lr is squeezed, the CT tensors keep
     (1, 1, ., .))."""
     sib = dict(weight_decay=weight_decay, dropout_p=dropout_p, gamma=gamma)
+    tv = _tv_fields(tv_weight, tv_beta, task)      # tv_weight * mean_k TV_beta(out_k[0]) joins the objective (all four methods); off: nothing changes
     hyper = dict(temp=temp, sigma=sigma) if method == "mfvi" else {"dip": {}, "mcd": dict(dropout_p=dropout_p, weight_decay=weight_decay),
                                                                   "sgld": dict(gamma=gamma, weight_decay=weight_decay)}.get(method, {})
     fields = dict(task=task, method=method, img=img if not isinstance(img, np.ndarray) else "<array>", imsize=imsize, p_sigma=p_sigma,
                   num_iter=num_iter, lr=lr, input_depth=input_depth, seed=seed, show_every=show_every, K=K, save_path=save_path,
-                  **(dict(downsampler=downsampler) if task == "sr" else {}), **hyper)
+                  **(dict(downsampler=downsampler) if task == "sr" else {}), **hyper, **tv)
 
     def prepare(n_it):
         import torch
@@ -240,20 +250,21 @@ def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, see
             rng = np.random.default_rng(seed + 1)
             noisy = np.clip(img_np + rng.normal(scale=p_sigma, size=img_np.shape), 0, 1).astype(np.float32)      # denoising_utils.py:11
             target, head = noisy, (img_np[None], noisy[None])
-            eng = _make_engine(method, H, W, "den", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, param_dtype=param_dtype)
+            eng = _make_engine(method, H, W, "den", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, param_dtype=param_dtype, **tv)
         elif task == "sr":
             if downsampler != "nearest":      # img_small = downsampler(img_hr) with the run's operator (models/downsampler.py)
                 from .downsampler import downsample
                 eng = _make_engine(method, H, W, "sr", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, sr_factor=factor, param_dtype=param_dtype,
-                                   downsampler=downsampler)
+                                   downsampler=downsampler, **tv)
                 target = downsample(torch.from_numpy(img_np).cuda(), downsampler, factor).cpu().numpy()
             else:
                 target = np.ascontiguousarray(img_np[::factor, ::factor])    # nearest /factor decimation (:2095-2099)
-                eng = _make_engine(method, H, W, "sr", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, sr_factor=factor, param_dtype=param_dtype)
+                eng = _make_engine(method, H, W, "sr", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, sr_factor=factor, param_dtype=param_dtype,
+                                   **tv)
             head = (img_np[None], target)
         else:
             theta = np.arange(0, 180.0, theta_step, dtype=np.float32)     # :545
-            eng = _make_engine(method, H, W, "ct", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, theta_deg=theta.tolist())
+            eng = _make_engine(method, H, W, "ct", K, input_depth, temp, sigma, lr, seed, net_kwargs, sib, theta_deg=theta.tolist(), **tv)
             target = torch.empty((len(theta), W), device="cuda")
             gt_d = torch.from_numpy(img_np).cuda()
             L.check(L.lib().mfvi_radon_forward(L.ptr(gt_d), L.ptr(eng.theta), 1, H, W, len(theta), L.ptr(target), L.stream_ptr()))
@@ -334,6 +345,7 @@ def run_inp_mfvi(img="phantom", mask=None, imsize=(256, 256), num_iter=5000, lr=
     the colour channels, masked Gaussian NLL.  img: (3, H, W) array in [0, 1] or 'phantom' (three synthetic planes); mask: (1|3, H, W),
     1 = known pixel (the reference ships its masks in data/inpainting/).  save.npz carries the reference's keys for this task
     (img_inpainting, img_mask, mse_corrupted, mse_gt, recons, uncerts, uncerts_ale, psnrs, ssims)."""
+    _tv_fields(unused.get("tv_weight", 0.0), unused.get("tv_beta", 0.5), "inp")      # refused with a weight > 0: the term is not built for inpainting
     fields = dict(task="inp", imsize=imsize, num_iter=num_iter, lr=lr, temp=temp, sigma=sigma, input_depth=input_depth, seed=seed,
                   show_every=show_every, K=K, save_path=save_path)
 
@@ -405,7 +417,8 @@ def _drive_batch(batch, gt, kind, keys, num_iter, show_every, save, save_path, v
     last iteration), _save_bookkeeping, _batch_predict -> the common keys of the result."""
     n_it = num_iter + 1                                               # bayesian_optimization.py:1291, :2935
     book = batch.track(gt, n_it, **track) if track is not None else None      # (DESIGN.md section 20)
-    at, psnrs, losses = [], [], []
+    at, psnrs, losses, tvs = [], [], [], []
+    tv_on = getattr(batch, "_tv", None) is not None                  # the total-variation term (DESIGN.md section 23): recorded like nll, and only then
     t0 = time.perf_counter()
     for i in range(n_it):
         batch.step()
@@ -413,9 +426,13 @@ def _drive_batch(batch, gt, kind, keys, num_iter, show_every, save, save_path, v
             book.snapshot()
         if i % show_every == 0 or i == n_it - 1:
             losses.append(batch.losses()); at.append(i); psnrs.append(batch.psnr(gt))
+            if tv_on:
+                tvs.append(batch.tv())
             if verbose:
-                print("iter %6d  psnr_gt_sm %s  (%.1f it/s x %d %s)" % (i, np.array2string(psnrs[-1], precision=2), (i + 1) / (time.perf_counter() - t0),
-                                                                       batch.n_rows, {"batch": "fits", "volume": "slices"}[kind]))
+                print("iter %6d  psnr_gt_sm %s%s  (%.1f it/s x %d %s)" % (i, np.array2string(psnrs[-1], precision=2),
+                                                                         "  tv %s" % np.array2string(tvs[-1], precision=3) if tv_on else "",
+                                                                         (i + 1) / (time.perf_counter() - t0), batch.n_rows,
+                                                                         {"batch": "fits", "volume": "slices"}[kind]))
     dead = batch.dead
     final = np.where(dead != 0, np.nan, psnrs[-1])
     run_dir = None
@@ -423,7 +440,8 @@ def _drive_batch(batch, gt, kind, keys, num_iter, show_every, save, save_path, v
         run_dir = os.path.join(save_path, "%s_%s" % (time.time(), kind))
         os.makedirs(run_dir, exist_ok=False)
         np.savez(os.path.join(run_dir, kind + ".npz"), K=np.int64(batch.K), seed=np.int64(batch.seed), num_iter=np.int64(num_iter), iterations=np.asarray(at),
-                 psnr_gt_sm=np.stack(psnrs), recon=batch.recon().cpu().numpy(), dead=dead, **keys(losses))
+                 psnr_gt_sm=np.stack(psnrs), recon=batch.recon().cpu().numpy(), dead=dead, **keys(losses),
+                 **(dict(tv_weight=np.asarray(batch.tv_weights), tv_beta=np.float64(batch.tv_beta), tv=np.stack(tvs)) if tv_on else {}))
         if book is not None:
             _save_bookkeeping(book, run_dir, heads)
     pred = _batch_predict(batch, batch_predict_samples, gt, run_dir, batch_calibration_bins) if batch_predict_samples else None
@@ -451,10 +469,12 @@ def _den_sr_batch(task, jobs, imsize, seed, p_sigma, factor):
 
 def run_fit_batch(task, jobs, imsize=(256, 256), p_sigma=0.1, num_iter=5000, lr=3e-4, input_depth=16, seed=42, show_every=100, save=True,
                   save_path="../logs", K=1, factor=4, net_kwargs=None, verbose=False, autotune=True, batch_predict_samples=0,
-                  batch_calibration_bins=0, batch_bookkeeping=False, **unused):
+                  batch_calibration_bins=0, batch_bookkeeping=False, tv_weight=0.0, tv_beta=0.5, **unused):
     """The (image, temp, sigma) jobs of one batch as ONE FitBatch (--fits-per-launch): the loop of run_den_mfvi /
     run_sr_mfvi for every job at once, every fit with the noise of its own RNG samples.  jobs: dicts with img, temp, sigma (and optionally
-    lr).  Writes batch.npz (hyper-parameters; per fit psnr_gt_sm, nll and kl every show_every iterations, the final reconstruction, dead);
+    lr and tv_weight; tv_weight / tv_beta: the run-wide total-variation term, DESIGN.md section 23 -- with a weight > 0 batch.npz also
+    holds tv_weight, tv_beta and tv, per record as nll).  Writes batch.npz (hyper-parameters; per fit psnr_gt_sm, nll and kl every
+    show_every iterations, the final reconstruction, dead);
     save.npz and the PNG artefacts stay with the single-fit runners.  batch_predict_samples >= 2: predictive_batch.npz (and with
     batch_calibration_bins calibration_batch.npz) beside it (_batch_predict).  batch_bookkeeping: the per-iteration records of every fit
     (BatchBook) -> bookkeeping_batch.npz and fit_%03d/save.npz beside it (_save_bookkeeping).  Returns dict(psnr=[per fit, NaN for a dead
@@ -469,7 +489,8 @@ def run_fit_batch(task, jobs, imsize=(256, 256), p_sigma=0.1, num_iter=5000, lr=
     gt, targets, track, heads = _den_sr_batch(task, jobs, imsize, seed, p_sigma, factor)
     temps, sigmas, lrs = [j["temp"] for j in jobs], [j["sigma"] for j in jobs], [j.get("lr", lr) for j in jobs]
     fb = FitBatch(gt.shape[1], gt.shape[2], len(jobs), task=task, K=K, input_depth=input_depth, temp=temps, sigma=sigmas, lr=lrs, seed=seed, sr_factor=factor,
-                  net_kwargs=net_kwargs, init="shared", autotune=autotune)      # the reference's candidates all start from one seed
+                  net_kwargs=net_kwargs, init="shared", autotune=autotune,      # the reference's candidates all start from one seed
+                  tv_weight=[j.get("tv_weight", tv_weight) for j in jobs], tv_beta=tv_beta)
     fb.set_targets(torch.from_numpy(targets))
     keys = lambda losses: dict(task=task, temp=np.asarray(temps), sigma=np.asarray(sigmas), lr=np.asarray(lrs), prior_sigma=np.asarray(fb.prior_sigma),
                                **_nll_kl(losses))
@@ -493,6 +514,8 @@ def run_inpaint_batch(jobs, imsize=(256, 256), num_iter=5000, lr=2e-3, input_dep
     import torch
     from .inpaintbatch import InpaintBatch
     _check_batch_predict(batch_predict_samples, batch_calibration_bins)
+    for w in [unused.get("tv_weight", 0.0)] + [j.get("tv_weight", 0.0) for j in jobs]:      # (an InpaintBatch has no total-variation term)
+        _tv_fields(w, unused.get("tv_beta", 0.5), "inp")
     imgs = [np.ascontiguousarray(j["img"], np.float32) if isinstance(j["img"], np.ndarray) else
             np.stack([_load_image(j["img"], imsize, seed + c) for c in range(3)]).astype(np.float32) for j in jobs]
     _, H, W = imgs[0].shape
@@ -523,7 +546,7 @@ def inpaint_batch_job(task, jobs, **kw):
 
 def run_sibling_batch(task, method, jobs, imsize=None, p_sigma=0.1, num_iter=5000, lr=None, input_depth=None, seed=42, show_every=100, save=True,
                       save_path="../logs", K=1, factor=4, net_kwargs=None, verbose=False, autotune=True, param_noise_sigma=2.0,
-                      batch_predict_samples=0, batch_calibration_bins=0, batch_bookkeeping=False, **unused):
+                      batch_predict_samples=0, batch_calibration_bins=0, batch_bookkeeping=False, tv_weight=0.0, tv_beta=0.5, **unused):
     """The (image, candidate) jobs of one batch as ONE SiblingBatch (--sibling-fits): the loop of run_<task>_<method> for
     every job at once.  jobs: dicts with img and, per method, dropout_p / weight_decay (mcd) or gamma / weight_decay (sgld), optionally lr;
     what a job leaves out takes the default of run_<task>_<method>.  Writes batch.npz (hyper-parameters; per fit psnr_gt_sm and the data
@@ -545,7 +568,8 @@ def run_sibling_batch(task, method, jobs, imsize=None, p_sigma=0.1, num_iter=500
     hyper = {k: [j.get(k, dflt.get(k, d)) for j in jobs] for k, d in (("weight_decay", 0.0), ("dropout_p", 0.3), ("gamma", 0.996))}
     lrs = [j.get("lr", lr) for j in jobs]
     sb = SiblingBatch(gt.shape[1], gt.shape[2], len(jobs), method, task=task, K=K, input_depth=input_depth, lr=lrs, seed=seed, sr_factor=factor,
-                      net_kwargs=net_kwargs, param_noise_sigma=param_noise_sigma, init="shared", autotune=autotune, **hyper)      # (one seed, as above)
+                      net_kwargs=net_kwargs, param_noise_sigma=param_noise_sigma, init="shared", autotune=autotune, **hyper,      # (one seed, as above)
+                      tv_weight=[j.get("tv_weight", tv_weight) for j in jobs], tv_beta=tv_beta)      # (the total-variation term as run_fit_batch takes it)
     sb.set_targets(torch.from_numpy(targets))
     keys = lambda losses: dict(method=method, task=task, lr=np.asarray(lrs), weight_decay=np.asarray(sb.weight_decays), dropout_p=np.asarray(sb.dropout_ps),
                                gamma=np.asarray(sb.gammas), loss=np.stack(losses))
@@ -632,9 +656,10 @@ def _load_volume(volume, imsize, seed):
 
 def run_ct_volume(volume, temp, sigma, slices_per_launch=None, imsize=(256, 256), num_iter=5000, lr=3e-4, input_depth=16, seed=42, show_every=100,
                   save=True, save_path="../logs", K=1, theta_step=4.0, net_kwargs=None, verbose=False, autotune=True, batch_predict_samples=0,
-                  batch_calibration_bins=0, batch_bookkeeping=False, **unused):
+                  batch_calibration_bins=0, batch_bookkeeping=False, tv_weight=0.0, tv_beta=0.5, **unused):
     """The loop of run_ct_mfvi (bayesian_optimization.py:442-648) for every slice of a stack at once, as ONE CtVolume (--ct-volume; DESIGN.md
-    section 16).  volume: [D, S, S] array, .npy path or 'phantom:D'; temp / sigma / lr: scalars or one value per slice.  Writes volume.npz
+    section 16).  volume: [D, S, S] array, .npy path or 'phantom:D'; temp / sigma / lr / tv_weight: scalars or one value per slice
+    (tv_weight > 0: volume.npz also holds tv_weight, tv_beta and tv).  Writes volume.npz
     (angles, sinograms, hyper-parameters; per slice psnr_gt_sm, nll and kl every show_every iterations, the reconstruction, dead); the ring
     buffers, SSIM curves, save.npz and PNG artefacts stay with the single-fit runner unless batch_bookkeeping (bookkeeping_batch.npz and
     fit_%03d/save.npz per slice, _save_bookkeeping; no PNGs).  Returns dict(psnr=[per slice, NaN for a dead one], ...)."""
@@ -644,7 +669,7 @@ def run_ct_volume(volume, temp, sigma, slices_per_launch=None, imsize=(256, 256)
     gt = _load_volume(volume, imsize, seed)
     theta = np.arange(0, 180.0, theta_step, dtype=np.float32)         # :545
     vol = CtVolume(gt.shape[1], gt.shape[0], slices_per_launch=slices_per_launch, K=K, input_depth=input_depth, temp=temp, sigma=sigma, lr=lr,
-                   theta_deg=theta.tolist(), seed=seed, net_kwargs=net_kwargs, autotune=autotune)
+                   theta_deg=theta.tolist(), seed=seed, net_kwargs=net_kwargs, autotune=autotune, tv_weight=tv_weight, tv_beta=tv_beta)
     vol.set_volume(torch.from_numpy(gt))                              # img_radon = forward_radon(img_torch) (:547)
     sinos = vol.sinos.cpu().numpy()
     keys = lambda losses: dict(theta=theta, sinograms=sinos, temp=np.asarray(vol.temps), sigma=np.asarray(vol.sigmas), lr=np.asarray(vol.lrs),
@@ -665,7 +690,7 @@ def _check_cli(ap, a):
     """What main() refuses from the parsed arguments alone, before the config is read and before anything loads the library.  The order is
     behaviour (the first refusal that applies is the one reported; tests/golden/cli_refusals.json): --sr-downsampler, --batch-bookkeeping,
     --batch-predict-samples / --batch-calibration, then --sibling-fits, --inpaint-fits, --ct-volume and --fits-per-launch each ahead of the
-    batching flags after it, then --calibration and --predict-samples of a single fit."""
+    batching flags after it, then --calibration and --predict-samples of a single fit, then --tv-weight / --tv-beta."""
     on = {"--fits-per-launch": a.fits_per_launch, "--inpaint-fits": a.inpaint_fits, "--sibling-fits": a.sibling_fits, "--ct-volume": a.ct_volume is not None,
           "--predict-samples": a.predict_samples, "--calibration": a.calibration, "--bo-rounds": a.bo_rounds}
 
@@ -745,6 +770,13 @@ def _check_cli(ap, a):
         ap.error("--predict-samples needs a posterior to draw from (--bayes mfvi or mcd), not %s" % a.bayes)
     if a.predict_samples < 0 or a.predict_samples == 1:
         ap.error("--predict-samples %d: 0 (off) or at least 2" % a.predict_samples)
+    # the total-variation term, behind every older check (their order is pinned)
+    if a.tv_weight is not None and not 0.0 <= a.tv_weight < float("inf"):
+        ap.error("--tv-weight %r: finite and >= 0" % a.tv_weight)
+    if a.tv_beta is not None and not 0.0 < a.tv_beta < float("inf"):
+        ap.error("--tv-beta %r: finite and > 0" % a.tv_beta)
+    if a.tv_weight and a.task == "inpainting":
+        ap.error("--tv-weight %g does not combine with --task inpainting (the total-variation term serves denoising, super-resolution and ct)" % a.tv_weight)
 
 
 def main(argv=None):
@@ -793,6 +825,10 @@ def main(argv=None):
                     help="super-resolution (mfvi): the forward operator of the data term, the low-resolution target and the low-resolution "
                          "metrics; nearest = [::f, ::f] (default, or the config's run_params.downsampler), lanczos2 / lanczos3 = the "
                          "anti-aliasing Downsampler of the reference's models/downsampler.py")
+    ap.add_argument("--tv-weight", type=float, default=None, help="> 0: add G * TV_beta of the reconstruction (the image channel of every MC sample) "
+                                                                  "to the objective of every fit (all four methods; denoising, super-resolution, "
+                                                                  "ct; default: the config's run_params.tv_weight, else off)")
+    ap.add_argument("--tv-beta", type=float, default=None, help="the exponent of --tv-weight's term, (dh^2 + dw^2)^B per cell (default 0.5: isotropic TV)")
     a = ap.parse_args(argv)
     _check_cli(ap, a)
     cands, rp, cfg_devices = load_config(a.config, a.bayes, with_devices=True)
@@ -824,6 +860,10 @@ def main(argv=None):
         rp["batch_calibration_bins"] = a.calibration_bins if a.batch_calibration else 0
     if a.batch_bookkeeping:
         rp["batch_bookkeeping"] = True
+    if a.tv_weight is not None:
+        rp["tv_weight"] = a.tv_weight
+    if a.tv_beta is not None:
+        rp["tv_beta"] = a.tv_beta
     if a.ct_volume is not None:      # one volume fit per candidate of the config
         from .fanout import print_table
         vrp = {k: v for k, v in rp.items() if k not in ("img", "plot", "p_sigma")}

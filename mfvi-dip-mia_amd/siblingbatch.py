@@ -62,11 +62,14 @@ class SiblingBatch(RowBatch):
     targets = None
 
     def __init__(self, H, W, n_fits, method, task="den", K=1, input_depth=16, lr=1e-3, weight_decay=0.0, dropout_p=0.3, gamma=0.996,
-                 param_noise_sigma=2.0, seed=1, sr_factor=4, net_kwargs=None, init="per_fit", autotune=True, param_dtype="f32"):
+                 param_noise_sigma=2.0, seed=1, sr_factor=4, net_kwargs=None, init="per_fit", autotune=True, param_dtype="f32", tv_weight=0.0,
+                 tv_beta=0.5):
         self.lr0s, self.weight_decays, self.dropout_ps, self.gammas = check_args(H, W, n_fits, method, task, K, lr, weight_decay, dropout_p, gamma,
                                                                                  init, param_dtype)
         if task == "sr" and (sr_factor < 1 or H % sr_factor or W % sr_factor):
             raise ValueError("sr_factor %r does not divide %dx%d" % (sr_factor, H, W))
+        from .tv import check_tv
+        self.tv_weights, self.tv_beta = check_tv(tv_weight, tv_beta, task, n=int(n_fits))      # a scalar, or one weight per fit
         self.method, self.task, self.F, self.sr_factor = method, task, int(n_fits), int(sr_factor)
         self.param_noise_sigma = float(param_noise_sigma)
         self.net_kwargs = dict(net_kwargs or {})
@@ -168,7 +171,7 @@ class SiblingBatch(RowBatch):
         from .engine import SiblingEngine
         eng = SiblingEngine(self.H, self.W, method=self.method, task=self.task, weight_decay=self.weight_decays[f], dropout_p=self.dropout_ps[f],
                             gamma=self.gammas[f], param_noise_sigma=self.param_noise_sigma, net_kwargs=self.net_kwargs, K=self.K,
-                            input_depth=self.input_depth, lr=self.lr0s[f], seed=self.seed, sr_factor=self.sr_factor, autotune=autotune)
+                            input_depth=self.input_depth, lr=self.lr0s[f], seed=self.seed, sr_factor=self.sr_factor, autotune=autotune, **self._tv_kw(f))
         eng.lr = float(self.lrs()[f]); eng.lr0 = self.lr0s[f]        # the copy continues the fit's schedule
         return eng
 
