@@ -68,6 +68,11 @@ CONV_CASES = [
     (16, 16, 3, 2, 8, 8), (32, 32, 3, 2, 8, 24), (16, 24, 3, 2, 72, 40), (64, 16, 3, 2, 24, 136),
     # 5x5 filters of the inpainting variant (bayesian_optimization.py:2970-2998): reflection pad 2, stride 1 and 2
     (16, 16, 5, 2, 20, 20), (8, 12, 5, 1, 12, 16), (32, 16, 5, 1, 8, 8), (5, 7, 5, 2, 9, 13), (16, 32, 5, 2, 3, 3),
+    # an odd number of rows on the matrix-core kernels (Cin % 4 == 0 and W % 4 == 0, or an even Wo at stride 2): stride-2 forward, zero-stuffed
+    # (Wo = 6, 22, 14) and phase-decomposed (Wo = 8, 24) backward-data with unequal row phases, W = 15 with the forward on the generic kernel and
+    # backward-data on the phase kernel, 3x3 / 5x5 / 1x1 at stride 1 (tests/test_gpu_oddmaps.py asserts the kernel families of these shapes)
+    (16, 8, 3, 2, 9, 12), (16, 8, 3, 2, 9, 16), (16, 8, 3, 2, 9, 15), (16, 8, 3, 2, 35, 48), (16, 8, 3, 2, 35, 44), (16, 16, 5, 2, 9, 12),
+    (16, 16, 5, 2, 21, 28), (16, 16, 3, 1, 9, 12), (36, 16, 3, 1, 35, 48), (16, 16, 5, 1, 9, 12), (16, 4, 1, 1, 9, 12),
 ]
 
 
@@ -128,7 +133,21 @@ NET_CASES = {
     # 44 -> 22 -> 11 -> 6 columns; 35 x 45 is odd from the first scale on
     "crop_three_scale_36x44": dict(H=36, W=44, input_depth=8, n_out=2, nd=(8, 16, 16), nu=(8, 16, 16), ns=(4, 4, 4)),
     "crop_two_scale_35x45": dict(H=35, W=45, input_depth=4, n_out=1, nd=(8, 12), nu=(8, 12), ns=(4, 2)),
+    # odd heights on the float4 / tiled concat kernels and the wider concat-backward tiles (tests/test_gpu_oddmaps.py takes the same switches
+    # one at a time).  35x48 -> 18x24 -> 9x12: float4 forward with the last row cropped and the 32x32 backward tile at the top scale, an even 18x24 scale below it
+    "crop_two_scale_35x48": dict(H=35, W=48, input_depth=4, n_out=2, nd=(8, 16), nu=(8, 16), ns=(4, 4)),
+    # 35x132 -> 18x66 -> 9x33 -> 5x17: tiled forward with a row crop and ragged tiles (16x64 backward tiles) at the top scale, the scalar
+    # forward (66 % 4 == 2) with a 32x32 backward tile and no crop at 18x66, a row + column crop with element loads (16x16 tile) at 9x33
+    "crop_three_scale_35x132": dict(H=35, W=132, input_depth=4, n_out=2, nd=(8, 8, 16), nu=(8, 8, 16), ns=(4, 2, 4)),
+    # 21x99 -> 11x50 -> 6x25: a crop at both scales, scalar forward at both (99 odd, 50 % 4 == 2); 16x64 backward tiles with element loads at
+    # the top scale, a row crop with pairs on the 32x32 tile (low-res 6x25) at 11x50
+    "crop_two_scale_21x99": dict(H=21, W=99, input_depth=4, n_out=1, nd=(8, 12), nu=(8, 12), ns=(4, 2)),
 }
+# Seeds other than 77.  At seed 77 the 35x132 net has a BN output of 6.3e-7 (of 5.4) under a LeakyReLU in sample 4: the GPU and the oracle take
+# different slopes there and the gradients differ by 2.3e-3 (the same net agrees to 2e-6 in every forward tensor).  The new nets take the
+# first seed at which every BN output under a LeakyReLU is at least 2e-6 of its tensor's scale away from zero
+# (tests/test_skip_restatement_host.py checks that on the host); 35x48 keeps 77.
+NET_SEEDS = {"crop_three_scale_35x132": 127, "crop_two_scale_21x99": 102}
 
 
 @pytest.mark.parametrize("name", list(NET_CASES))
@@ -137,7 +156,7 @@ def test_small_nets_fwd_bwd(M, name):
     fold, BN backward on load, multi-consumer gradient sum) against the oracle, n MC samples with k0 > 0."""
     kw = NET_CASES[name]
     net = O.make_net(**kw)
-    seed, step, k0, n = 77, 9, 2, 3
+    seed, step, k0, n = NET_SEEDS.get(name, 77), 9, 2, 3
     mu, rho, bnp = _net_params(net, seed)
     P, zin, out_id, names = M.skip_program(kw["H"], kw["W"], kw["input_depth"], kw["n_out"], kw["nd"], kw["nu"], kw["ns"])
     conv, bn, n_vi, n_bnp = O.net_table(net)
