@@ -295,6 +295,21 @@ int mfvi_kl(const float* mu, const float* rho, int64_t n, float prior_mu, float 
 /* dmu += scale * dKL/dmu, drho += scale * dKL/drho */
 int mfvi_kl_backward(const float* mu, const float* rho, int64_t n, float prior_mu, float prior_sigma, float scale,
                      float* dmu, float* drho, void* stream);
+/* The direction of the KL term.  The reference's VIModule carries a kl_type (BayTorch/modules/module.py:17, 40, 64-80; handed down by
+ * MeanFieldVI, freq_to_bayes.py:9-16), named the opposite way round from what one would guess:
+ *   MFVI_KL_REVERSE  kl_type == 'reverse' (the default, what all runners use): kl_divergence(prior, posterior) = KL(p || q), the term above;
+ *   MFVI_KL_FORWARD  any other kl_type: kl_divergence(posterior, prior) = KL(q || p), the KL term of the textbook ELBO.  Per (mu, rho) pair,
+ *                    s = softplus(rho), d = mu - m0:
+ *                        kl = log(s0) - log(s) + (s^2 + d^2) / (2 s0^2) - 1/2,   dkl/dmu = d / s0^2,   dkl/drho = (s / s0^2 - 1 / s) sigmoid(rho)
+ * float32 per element, summed in float64 in the order of the reverse kernels.  Each *_typed entry is its twin below / above with the
+ * direction as an argument: MFVI_KL_REVERSE runs the twin itself (bit-identical), MFVI_KL_FORWARD the forward kernels with the same
+ * launches, scratch and reduction order.  Refused with -1 and mfvi_last_error() before any launch: kl_type outside {0, 1}, prior_sigma
+ * not finite or <= 0, for forward a prior_sigma^2 that is not a normal float32, null pointers, n < 1. */
+#define MFVI_KL_REVERSE 0
+#define MFVI_KL_FORWARD 1
+int mfvi_kl_typed(const float* mu, const float* rho, int64_t n, float prior_mu, float prior_sigma, int kl_type, double* kl_out, void* stream);
+int mfvi_kl_backward_typed(const float* mu, const float* rho, int64_t n, float prior_mu, float prior_sigma, float scale, int kl_type,
+                           float* dmu, float* drho, void* stream);
 
 /* ---- optimizer (torch.optim.AdamW(lr, weight_decay=0): bayesian_optimization.py:1356-1357,1372) --------- */
 int mfvi_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
@@ -329,6 +344,16 @@ int mfvi_f32_to_bf16(const float* src, int64_t n, void* dst, void* stream);
 int mfvi_elbo_update_guarded(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, float prior_mu, float prior_sigma,
                              float temp, float lr, float beta1, float beta2, float eps, int32_t* t_applied, const double* loss_d,
                              const float* loss_f, double* kl_out, void* scratch, void* stream);
+/* mfvi_elbo_update / _guarded / _bf16 with the direction of the KL term (MFVI_KL_REVERSE / MFVI_KL_FORWARD above; BayTorch/modules/module.py:64-80)
+ * as a by-value argument behind temp: the same launches and scratch, so the device-resident and the captured iteration take it as they are. */
+int mfvi_elbo_update_typed(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, float prior_mu, float prior_sigma,
+                           float temp, int kl_type, float lr, float beta1, float beta2, float eps, int t, double* kl_out, void* scratch, void* stream);
+int mfvi_elbo_update_guarded_typed(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, float prior_mu, float prior_sigma,
+                                   float temp, int kl_type, float lr, float beta1, float beta2, float eps, int32_t* t_applied, const double* loss_d,
+                                   const float* loss_f, double* kl_out, void* scratch, void* stream);
+int mfvi_elbo_update_bf16_typed(void* mu_bf16, void* rho_bf16, float* bn, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, float prior_mu,
+                                float prior_sigma, float temp, int kl_type, float lr, float beta1, float beta2, float eps, int t, uint64_t seed,
+                                double* kl_out, void* scratch, void* stream);
 int mfvi_adamw_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                             const int32_t* t_applied, const double* loss_d, const float* loss_f, float weight_decay, void* stream);
 int mfvi_step_advance(int32_t* t_applied, const double* loss_d, const float* loss_f, void* stream);
@@ -492,6 +517,12 @@ int64_t mfvi_elbo_update_fits_scratch_bytes(int n_fits);
 int mfvi_elbo_update_fits(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, int64_t param_stride, int64_t grad_stride,
                           int n_fits, const mfvi_fit_hyper* hyper_dev, float beta1, float beta2, float eps, int t, const double* nll, int32_t* dead,
                           double* kl_out, void* scratch, void* stream);
+/* mfvi_elbo_update_fits with the direction of every fit's KL term (BayTorch/modules/module.py:64-80): kl_type_dev[n_fits] in DEVICE memory,
+ * MFVI_KL_REVERSE or MFVI_KL_FORWARD per fit, chosen once per block; NULL = all reverse (mfvi_elbo_update_fits itself).  A value outside
+ * {0, 1} cannot be refused on the host: that fit is marked dead (dead[f] = 1) and nothing else is written for it, kl_out[f] included. */
+int mfvi_elbo_update_fits_typed(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, int64_t param_stride, int64_t grad_stride,
+                                int n_fits, const mfvi_fit_hyper* hyper_dev, const int32_t* kl_type_dev, float beta1, float beta2, float eps, int t,
+                                const double* nll, int32_t* dead, double* kl_out, void* scratch, void* stream);
 /* The EMA part of mfvi_bookkeep per fit: sample means of out[:, 0] and exp(-out[:, 1]) over the fit's S samples (out [n_fits * S][C][H][W],
  * C = 1 or 2) and ema[f] = first ? mean : ema[f] * weight + mean * (1 - weight); ema [n_fits][C][H][W]. */
 int mfvi_ema_fits(const float* out, int n_fits, int S, int C, int H, int W, float* ema, float weight, int first, void* stream);

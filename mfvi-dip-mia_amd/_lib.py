@@ -11,6 +11,7 @@ DOMAIN_EPS, DOMAIN_INPUT, DOMAIN_INIT, DOMAIN_UNIFORM, DOMAIN_SGLD, DOMAIN_DROPO
 PARAM_F32, PARAM_BF16 = 0, 1
 PRED_RAW, PRED_LOGPREC, PRED_INP, PRED_MEAN_ONLY = 0, 1, 2, 3             # MFVI_PRED_* (posterior predictive statistics)
 MASKED_SQ_ERR_BLOCKS = 64                                                 # MFVI_MASKED_SQ_ERR_BLOCKS (mfvi_masked_sq_err_fits scratch)
+KL_REVERSE, KL_FORWARD = 0, 1                                             # MFVI_KL_* (the direction of the KL term)
 UCE_MAX_BINS = 256                                                        # MFVI_UCE_MAX_BINS (uncertainty calibration)
 
 
@@ -69,10 +70,15 @@ SIGNATURES = {
     "mfvi_radon_backproject": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "mfvi_kl": (_I, [_P, _P, _I64, _F, _F, _P, _P]),
     "mfvi_kl_backward": (_I, [_P, _P, _I64, _F, _F, _F, _P, _P, _P]),
+    "mfvi_kl_typed": (_I, [_P, _P, _I64, _F, _F, _I, _P, _P]),
+    "mfvi_kl_backward_typed": (_I, [_P, _P, _I64, _F, _F, _F, _I, _P, _P, _P]),
     "mfvi_adam_step": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _I, _P]),
     "mfvi_elbo_update_scratch_bytes": (_I64, []),
     "mfvi_elbo_update": (_I, [_P, _P, _P, _P, _I64, _I64, _F, _F, _F, _F, _F, _F, _F, _I, _P, _P, _P]),
     "mfvi_elbo_update_guarded": (_I, [_P, _P, _P, _P, _I64, _I64, _F, _F, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P]),
+    "mfvi_elbo_update_typed": (_I, [_P, _P, _P, _P, _I64, _I64, _F, _F, _F, _I, _F, _F, _F, _F, _I, _P, _P, _P]),
+    "mfvi_elbo_update_guarded_typed": (_I, [_P, _P, _P, _P, _I64, _I64, _F, _F, _F, _I, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P]),
+    "mfvi_elbo_update_bf16_typed": (_I, [_P, _P, _P, _P, _P, _P, _I64, _I64, _F, _F, _F, _I, _F, _F, _F, _F, _I, _U64, _P, _P, _P]),
     "mfvi_adamw_step_guarded": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _P, _P, _P, _F, _P]),
     "mfvi_step_advance": (_I, [_P, _P, _P, _P]),
     "mfvi_decimate": (_I, [_P, _I, _I, _I, _P, _P]),
@@ -112,6 +118,7 @@ SIGNATURES = {
     "mfvi_gaussian_nll_fits": (_I, [_P, _P, _I64, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "mfvi_elbo_update_fits_scratch_bytes": (_I64, [_I]),
     "mfvi_elbo_update_fits": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _F, _F, _F, _I, _P, _P, _P, _P, _P]),
+    "mfvi_elbo_update_fits_typed": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _P, _F, _F, _F, _I, _P, _P, _P, _P, _P]),
     "mfvi_ema_fits": (_I, [_P, _I, _I, _I, _I, _I, _P, _F, _I, _P]),
     "mfvi_gaussian_nll_inpainting_fits": (_I, [_P, _P, _I64, _P, _I64, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "mfvi_ema_inpainting_fits": (_I, [_P, _I, _I, _I, _I, _P, _F, _I, _P]),
@@ -156,9 +163,19 @@ def check(rc):
         raise MfviError("libmfvi_hip error %d: %s" % (rc, lib().mfvi_last_error().decode()))
 
 
+class _TensorPtr(C.c_void_p):
+    """A device pointer that owns a reference to its tensor: a temporary passed as ptr(x.cuda()) lives until the call that takes the pointer
+    has enqueued its launch, not until the next allocation reuses its block."""
+    __slots__ = ("tensor",)
+
+
 def ptr(t):
-    """Device pointer of a torch tensor (or None)."""
-    return None if t is None else C.c_void_p(t.data_ptr())
+    """Device pointer of a torch tensor (or None); the pointer keeps the tensor alive as long as it lives itself."""
+    if t is None:
+        return None
+    p = _TensorPtr(t.data_ptr())
+    p.tensor = t
+    return p
 
 
 def stream_ptr():

@@ -40,7 +40,7 @@ class Conv2dRT(nn.Module):
 
     @property
     def _kl(self):
-        """KL(prior || posterior) of this layer (modules/module.py:64-74), computed by the HIP reduction."""
+        """The KL term of this layer in the direction of kl_type (modules/module.py:64-80), computed by the HIP reduction."""
         return self.__dict__['_owner']._layer_kl(self)
 
     def forward(self, x):
@@ -108,7 +108,11 @@ class _KLFunctionFlat(torch.autograd.Function):
 class MeanFieldVI(nn.Module):
     def __init__(self, net, prior=None, posteriors=None, kl_type='reverse', reparam='local', replace_layers='all',
                  device=torch.device('cpu'), seed=None, n_samples=1, autotune=True, flat_parameters=False):
-        """Arguments as BayTorch/freq_to_bayes.py:9-16, plus seed / n_samples / autotune and
+        """Arguments as BayTorch/freq_to_bayes.py:9-16, plus seed / n_samples / autotune and flat_parameters.
+        kl_type: 'reverse' (the default, what all runners use) is kl_divergence(prior, posterior) = KL(p || q); EVERY other string is the
+        forward direction kl_divergence(posterior, prior) = KL(q || p), the textbook ELBO's term -- exactly what modules/module.py:76-80
+        does (`if self.kl_type == 'reverse' ... else ...`), so 'forward', 'fwd' and a typo alike select it.  net.kl(), its backward and
+        every layer's `_kl` follow the direction; each layer carries `.kl_type`.
         flat_parameters (default False: `.parameters()` yields the reference's 254 leaf Parameters W_mu, W_rho, bias_mu, bias_rho, BN
         weight / bias, and autograd delivers a .grad to each — exact torch semantics, ~3 ms of per-Parameter Python / autograd /
         optimizer work per iteration).  True: `.parameters()` yields ONE Parameter, the flat [MU | RHO | BN] buffer all of those are
@@ -123,8 +127,7 @@ class MeanFieldVI(nn.Module):
         self._lrt = reparam == 'local'
         if replace_layers != 'all':
             raise NotImplementedError("replace_layers=%r: only 'all' (the runners' setting) is built" % (replace_layers,))
-        if kl_type != 'reverse':
-            raise NotImplementedError("kl_type=%r: only 'reverse' (the default, used by all runners) is built" % (kl_type,))
+        self._klt = L.KL_REVERSE if kl_type == 'reverse' else L.KL_FORWARD      # modules/module.py:76-80: anything but 'reverse' is forward
         prior = {'mu': 0, 'sigma': 0.1} if prior is None else prior                         # modules/module.py:23-30
         posteriors = {'mu': (0, 0.1), 'rho': (-3., 0.1)} if posteriors is None else posteriors
         if 'pi' in prior:
@@ -396,7 +399,8 @@ class MeanFieldVI(nn.Module):
         return self
 
     def kl(self):
-        """Sum of the layers' KL(prior || posterior) as a tensor of shape [1] (freq_to_bayes.py:43-48)."""
+        """Sum of the layers' KL terms (kl_type 'reverse': KL(prior || posterior), else KL(posterior || prior)) as a tensor of shape [1]
+        (freq_to_bayes.py:43-48)."""
         m = self._vi[0]
         if getattr(self, "_flat_mode", False):
             return _KLFunctionFlat.apply(self, 0, self.n_vi, m.prior_mu, m.prior_sigma, next(self.parameters()))
@@ -533,8 +537,8 @@ class MeanFieldVI(nn.Module):
     def _hip_kl(self, lo, hi, prior_mu, prior_sigma):
         mu, rho, _ = self._blocks()
         acc = torch.zeros(1, dtype=torch.float64, device=self.device)
-        L.check(L.lib().mfvi_kl(L.ptr(mu[lo:hi]), L.ptr(rho[lo:hi]), hi - lo, prior_mu, float(torch.tensor(prior_sigma, dtype=torch.float32)),
-                                L.ptr(acc), L.stream_ptr()))
+        L.check(L.lib().mfvi_kl_typed(L.ptr(mu[lo:hi]), L.ptr(rho[lo:hi]), hi - lo, prior_mu, float(torch.tensor(prior_sigma, dtype=torch.float32)),
+                                      self._klt, L.ptr(acc), L.stream_ptr()))
         return acc.float()                                   # FloatTensor of shape [1], as the reference returns
 
     def _hip_kl_backward(self, lo, hi, prior_mu, prior_sigma, gout, flat=False):
@@ -542,9 +546,9 @@ class MeanFieldVI(nn.Module):
         n = self.n_vi
         g = torch.zeros(2 * n + (self.n_bn if flat else 0), dtype=torch.float32, device=self.device)
         scale = float(gout.reshape(-1)[0])
-        L.check(L.lib().mfvi_kl_backward(L.ptr(mu[lo:hi]), L.ptr(rho[lo:hi]), hi - lo, prior_mu,
-                                         float(torch.tensor(prior_sigma, dtype=torch.float32)), scale, L.ptr(g[lo:hi]), L.ptr(g[n + lo:n + hi]),
-                                         L.stream_ptr()))
+        L.check(L.lib().mfvi_kl_backward_typed(L.ptr(mu[lo:hi]), L.ptr(rho[lo:hi]), hi - lo, prior_mu,
+                                               float(torch.tensor(prior_sigma, dtype=torch.float32)), scale, self._klt, L.ptr(g[lo:hi]),
+                                               L.ptr(g[n + lo:n + hi]), L.stream_ptr()))
         if flat:
             return g
         grads = []

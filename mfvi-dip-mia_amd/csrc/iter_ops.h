@@ -102,6 +102,46 @@ __device__ __forceinline__ double elbo_update_share(float* __restrict__ p, float
     return acc;
 }
 
+// ---- the forward direction, KL(posterior || prior) (modules/module.py:76-80 with kl_type != 'reverse'; the textbook ELBO's term), of ONE
+// (mu, rho) pair: returns the term, float32 pieces added in float64 as the reverse kernels add theirs; gmu / grho = its two derivatives.
+// Every forward kernel takes its arithmetic from here, and every operation of it is rounded on its own (no fma contraction: which products
+// fuse would depend on what the kernel around it keeps of the three results, and the fused and the unfused KL would part in the ninth digit) ----
+__device__ __forceinline__ double kl_forward_terms(float mu, float r, float m0, float log_s0, float s0sq, float& gmu, float& grho)
+{
+#pragma clang fp contract(off)
+    const float s = softplus_f(r), d = mu - m0;
+    gmu = d / s0sq;
+    grho = (s / s0sq - 1.f / s) * sigmoid_f(r);
+    return (double)(log_s0 - logf(s)) + (double)((s * s + d * d) / (2.f * s0sq)) - 0.5;
+}
+
+// ---- elbo_update_share with the forward KL term: the same loops, the same Adam, the same order of the sum ----
+__device__ __forceinline__ double elbo_update_share_fwd(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                        long long n_vi, long long n_bn, float m0, float s0, float temp, float b1, float b2, float eps,
+                                                        float step_size, float inv_sqrt_bc2, bool skip)
+{
+    const float log_s0 = logf(s0), s0sq = s0 * s0;
+    auto adam = [&](long long i, float gi) {
+        const float mi = b1 * m[i] + (1.f - b1) * gi;
+        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        m[i] = mi; v[i] = vi;
+        p[i] = p[i] - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
+    };
+    double acc = 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_vi; i += (long long)gridDim.x * 256) {
+        float dkm, dkr;
+        acc += kl_forward_terms(p[i], p[n_vi + i], m0, log_s0, s0sq, dkm, dkr);
+        if (skip) continue;
+        const float gmu = g[i] + temp * dkm;
+        const float grho = g[n_vi + i] + temp * dkr;
+        g[i] = gmu; g[n_vi + i] = grho;
+        adam(i, gmu); adam(n_vi + i, grho);
+    }
+    if (!skip)
+        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_bn; i += (long long)gridDim.x * 256) adam(2 * n_vi + i, g[2 * n_vi + i]);
+    return acc;
+}
+
 // ---- out[j] = (base ? base[j] : a) + b * N(0,1), element j = lane j & 3 of Philox block j >> 2 of the key's stream (grid x strides over the blocks) ----
 __device__ __forceinline__ void normal_fill_share(const RngKey& key, long long n, float a, float b, const float* __restrict__ base, float* __restrict__ out)
 {

@@ -5,6 +5,7 @@
 #include "common.h"
 #include "iter_ops.h"
 #include <algorithm>
+#include <cmath>
 #include <type_traits>
 #include "../../include/mfvi_hip.h"
 
@@ -175,6 +176,33 @@ __global__ __launch_bounds__(256) void kl_bwd_kernel(const float* __restrict__ m
     }
 }
 
+// the forward direction KL(posterior || prior) (kl_forward_terms, iter_ops.h): the grids and the order of the sum of the two kernels above
+__global__ __launch_bounds__(256) void kl_fwd_kernel(const float* __restrict__ mu, const float* __restrict__ rho, long long n,
+                                                     float m0, float s0, double* __restrict__ kl_out)
+{
+    __shared__ double s_red[8];
+    double acc = 0;
+    const float log_s0 = logf(s0), s0sq = s0 * s0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        float gmu, grho;
+        acc += kl_forward_terms(mu[i], rho[i], m0, log_s0, s0sq, gmu, grho);
+    }
+    block_atomic_add(acc, kl_out, s_red);
+}
+
+__global__ __launch_bounds__(256) void kl_fwd_bwd_kernel(const float* __restrict__ mu, const float* __restrict__ rho, long long n,
+                                                         float m0, float s0, float scale, float* __restrict__ dmu,
+                                                         float* __restrict__ drho)
+{
+    const float log_s0 = logf(s0), s0sq = s0 * s0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        float gmu, grho;
+        (void)kl_forward_terms(mu[i], rho[i], m0, log_s0, s0sq, gmu, grho);
+        dmu[i] += scale * gmu;
+        drho[i] += scale * grho;
+    }
+}
+
 // ---- AdamW -----------------------------------------------------------------------------------------
 // NaN guard of the CT runners (bayesian_optimization.py:380, 581-582, 792, 994: `if not torch.isnan(loss): optimizer.step()`) without a
 // host sync: the data-term scalar of this iteration is read on the device (double accumulator and / or the float that rode the
@@ -235,6 +263,20 @@ __global__ __launch_bounds__(256) void elbo_update_kernel(float* __restrict__ p,
     const bool skip = guard_skip(guard);             // NaN data term: KL is still reported, nothing is written
     adam_bias(guard, lr, b1, b2, s_bc, step_size, inv_sqrt_bc2);
     const double acc = elbo_update_share(p, g, m, v, n_vi, n_bn, m0, s0, temp, b1, b2, eps, step_size, inv_sqrt_bc2, skip);
+    const double tot = block_sum_d(acc, s_red);
+    if (threadIdx.x == 0) sc->partial[blockIdx.x] = tot;
+}
+// elbo_update_kernel with the forward KL term (elbo_update_share_fwd): same grid, same partials, the finish kernel below
+__global__ __launch_bounds__(256) void elbo_update_fwd_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                              long long n_vi, long long n_bn, float m0, float s0, float temp, float b1, float b2,
+                                                              float eps, float step_size, float inv_sqrt_bc2, ElboUpdateScratch* __restrict__ sc, float lr,
+                                                              StepGuard guard)
+{
+    __shared__ double s_red[8];
+    __shared__ float s_bc[2];
+    const bool skip = guard_skip(guard);
+    adam_bias(guard, lr, b1, b2, s_bc, step_size, inv_sqrt_bc2);
+    const double acc = elbo_update_share_fwd(p, g, m, v, n_vi, n_bn, m0, s0, temp, b1, b2, eps, step_size, inv_sqrt_bc2, skip);
     const double tot = block_sum_d(acc, s_red);
     if (threadIdx.x == 0) sc->partial[blockIdx.x] = tot;
 }
@@ -647,6 +689,57 @@ __global__ __launch_bounds__(256) void elbo_update_bf16_kernel(bf16_t* __restric
     if (threadIdx.x == 0) sc->partial[blockIdx.x] = tot;
 }
 
+// elbo_update_bf16_kernel with the forward KL term: the same quads, rounding words and Adam
+__global__ __launch_bounds__(256) void elbo_update_bf16_fwd_kernel(bf16_t* __restrict__ pm, bf16_t* __restrict__ pr, float* __restrict__ bn, float* __restrict__ g,
+                                                                   float* __restrict__ m, float* __restrict__ v, long long n_vi, long long n_bn, float m0, float s0,
+                                                                   float temp, float b1, float b2, float eps, float step_size, float inv_sqrt_bc2, RngKey key,
+                                                                   ElboUpdateScratch* __restrict__ sc)
+{
+    key = key_now(key);
+    __shared__ double s_red[8];
+    const float log_s0 = logf(s0), s0sq = s0 * s0;
+    auto adam = [&](long long i, float gi, float pi) -> float {
+        const float mi = b1 * m[i] + (1.f - b1) * gi;
+        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        m[i] = mi; v[i] = vi;
+        return pi - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
+    };
+    double acc = 0;
+    const long long nq = (n_vi + 3) >> 2;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long long)gridDim.x * 256) {
+        uint32_t rm[4], rr[4];
+        RngKey k0 = key; k0.stream = ((uint32_t)DOMAIN_ROUND << 24) | 0u;
+        philox4x32_10((uint32_t)q, k0.stream, k0.sample, k0.step, k0.k0, k0.k1, rm);
+        philox4x32_10((uint32_t)q, k0.stream | 1u, k0.sample, k0.step, k0.k0, k0.k1, rr);
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            const long long i = 4 * q + l;
+            if (i >= n_vi) break;
+            const float mu = bf16_to_f32(pm[i]), r = bf16_to_f32(pr[i]);
+            float dkm, dkr;
+            acc += kl_forward_terms(mu, r, m0, log_s0, s0sq, dkm, dkr);
+            const float gmu = g[i] + temp * dkm;
+            const float grho = g[n_vi + i] + temp * dkr;
+            g[i] = gmu; g[n_vi + i] = grho;
+            pm[i] = f32_to_bf16_sr(adam(i, gmu, mu), rm[l] >> 16);
+            pr[i] = f32_to_bf16_sr(adam(n_vi + i, grho, r), rr[l] >> 16);
+        }
+    }
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_bn; i += (long long)gridDim.x * 256) bn[i] = adam(2 * n_vi + i, g[2 * n_vi + i], bn[i]);
+    const double tot = block_sum_d(acc, s_red);
+    if (threadIdx.x == 0) sc->partial[blockIdx.x] = tot;
+}
+
+// what every *_typed entry refuses of its direction and prior scale before any launch -> nullptr, or what is wrong
+const char* kl_type_refusal(int kl_type, float prior_sigma)
+{
+    if (kl_type != MFVI_KL_REVERSE && kl_type != MFVI_KL_FORWARD) return "kl_type outside {MFVI_KL_REVERSE, MFVI_KL_FORWARD}";
+    if (!std::isfinite(prior_sigma) || !(prior_sigma > 0.f)) return "prior_sigma not finite or <= 0";
+    const float s0sq = prior_sigma * prior_sigma;      // the divisor of every forward term
+    if (kl_type == MFVI_KL_FORWARD && !std::isnormal(s0sq)) return "forward: prior_sigma^2 is not a normal float32";
+    return nullptr;
+}
+
 }  // namespace
 
 int launch_dropout_masks(const DropEntry* table_dev, int n_entries, RngKey key, int n_samples, float* arena, hipStream_t st, const float* fit_p, int fit_s,
@@ -761,6 +854,29 @@ int mfvi_kl_backward(const float* mu, const float* rho, int64_t n, float prior_m
     return (int)hipGetLastError();
 }
 
+int mfvi_kl_typed(const float* mu, const float* rho, int64_t n, float prior_mu, float prior_sigma, int kl_type, double* kl_out, void* stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const char* why = kl_type_refusal(kl_type, prior_sigma);
+    if (!why && (!mu || !rho || !kl_out || n < 1)) why = "null pointer or n < 1";
+    if (why) { set_error("kl_typed: %s", why); return -1; }
+    if (kl_type == MFVI_KL_REVERSE) return mfvi_kl(mu, rho, n, prior_mu, prior_sigma, kl_out, stream);
+    hipError_t e = hipMemsetAsync(kl_out, 0, sizeof(double), st); if (e) return (int)e;
+    hipLaunchKernelGGL(kl_fwd_kernel, dim3(nblocks(n, 96)), dim3(256), 0, st, mu, rho, (long long)n, prior_mu, prior_sigma, kl_out);
+    return (int)hipGetLastError();
+}
+
+int mfvi_kl_backward_typed(const float* mu, const float* rho, int64_t n, float prior_mu, float prior_sigma, float scale, int kl_type, float* dmu,
+                           float* drho, void* stream)
+{
+    const char* why = kl_type_refusal(kl_type, prior_sigma);
+    if (!why && (!mu || !rho || !dmu || !drho || n < 1)) why = "null pointer or n < 1";
+    if (why) { set_error("kl_backward_typed: %s", why); return -1; }
+    if (kl_type == MFVI_KL_REVERSE) return mfvi_kl_backward(mu, rho, n, prior_mu, prior_sigma, scale, dmu, drho, stream);
+    hipLaunchKernelGGL(kl_fwd_bwd_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, mu, rho, (long long)n, prior_mu, prior_sigma, scale, dmu, drho);
+    return (int)hipGetLastError();
+}
+
 int mfvi_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, int t,
                    void* stream)
 {
@@ -805,6 +921,44 @@ int mfvi_elbo_update_guarded(float* params, float* grads, float* m, float* v, in
     return (int)hipGetLastError();
 }
 
+int mfvi_elbo_update_typed(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, float prior_mu, float prior_sigma, float temp,
+                           int kl_type, float lr, float beta1, float beta2, float eps, int t, double* kl_out, void* scratch, void* stream)
+{
+    if (const char* why = kl_type_refusal(kl_type, prior_sigma)) { set_error("elbo_update_typed: %s", why); return -1; }
+    if (kl_type == MFVI_KL_REVERSE)
+        return mfvi_elbo_update(params, grads, m, v, n_vi, n_bn, prior_mu, prior_sigma, temp, lr, beta1, beta2, eps, t, kl_out, scratch, stream);
+    if (!params || !grads || !m || !v || !kl_out || !scratch || n_vi < 0 || n_bn < 0 || t < 1) {
+        set_error("elbo_update_typed: bad arguments (t is 1-based, scratch of mfvi_elbo_update_scratch_bytes() bytes)"); return -1; }
+    const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
+    const long long work = n_vi > n_bn ? n_vi : n_bn;
+    const int nb = nblocks(work, ELBO_UPDATE_MAX_BLOCKS);
+    hipLaunchKernelGGL(elbo_update_fwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, (long long)n_vi, (long long)n_bn,
+                       prior_mu, prior_sigma, temp, beta1, beta2, eps, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)), (ElboUpdateScratch*)scratch, lr,
+                       StepGuard{nullptr, nullptr, nullptr});
+    hipLaunchKernelGGL(elbo_update_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const ElboUpdateScratch*)scratch, nb, kl_out, (int*)nullptr,
+                       StepGuard{nullptr, nullptr, nullptr});
+    return (int)hipGetLastError();
+}
+
+int mfvi_elbo_update_guarded_typed(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, float prior_mu, float prior_sigma, float temp,
+                                   int kl_type, float lr, float beta1, float beta2, float eps, int32_t* t_applied, const double* loss_d, const float* loss_f,
+                                   double* kl_out, void* scratch, void* stream)
+{
+    if (const char* why = kl_type_refusal(kl_type, prior_sigma)) { set_error("elbo_update_guarded_typed: %s", why); return -1; }
+    if (kl_type == MFVI_KL_REVERSE)
+        return mfvi_elbo_update_guarded(params, grads, m, v, n_vi, n_bn, prior_mu, prior_sigma, temp, lr, beta1, beta2, eps, t_applied, loss_d, loss_f, kl_out,
+                                        scratch, stream);
+    if (!params || !grads || !m || !v || !kl_out || !scratch || !t_applied || n_vi < 0 || n_bn < 0) {
+        set_error("elbo_update_guarded_typed: bad arguments (t_applied: device counter of applied updates)"); return -1; }
+    const long long work = n_vi > n_bn ? n_vi : n_bn;
+    const int nb = nblocks(work, ELBO_UPDATE_MAX_BLOCKS);
+    const StepGuard guard{t_applied, loss_d, loss_f};
+    hipLaunchKernelGGL(elbo_update_fwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, (long long)n_vi, (long long)n_bn,
+                       prior_mu, prior_sigma, temp, beta1, beta2, eps, 0.f, 0.f, (ElboUpdateScratch*)scratch, lr, guard);
+    hipLaunchKernelGGL(elbo_update_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const ElboUpdateScratch*)scratch, nb, kl_out, t_applied, guard);
+    return (int)hipGetLastError();
+}
+
 int mfvi_adamw_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                             const int32_t* t_applied, const double* loss_d, const float* loss_f, float weight_decay, void* stream)
 {
@@ -840,6 +994,27 @@ int mfvi_elbo_update_bf16(void* mu_bf16, void* rho_bf16, float* bn, float* grads
     const long long work = std::max<long long>((n_vi + 3) / 4, n_bn);
     const int nb = nblocks(work, ELBO_UPDATE_MAX_BLOCKS);
     hipLaunchKernelGGL(elbo_update_bf16_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (bf16_t*)mu_bf16, (bf16_t*)rho_bf16, bn, grads, m, v, (long long)n_vi,
+                       (long long)n_bn, prior_mu, prior_sigma, temp, beta1, beta2, eps, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)),
+                       make_key(seed, DOMAIN_ROUND, 0, 0, (uint32_t)t), (ElboUpdateScratch*)scratch);
+    hipLaunchKernelGGL(elbo_update_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const ElboUpdateScratch*)scratch, nb, kl_out, (int*)nullptr,
+                       StepGuard{nullptr, nullptr, nullptr});
+    return (int)hipGetLastError();
+}
+
+int mfvi_elbo_update_bf16_typed(void* mu_bf16, void* rho_bf16, float* bn, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, float prior_mu,
+                                float prior_sigma, float temp, int kl_type, float lr, float beta1, float beta2, float eps, int t, uint64_t seed, double* kl_out,
+                                void* scratch, void* stream)
+{
+    if (const char* why = kl_type_refusal(kl_type, prior_sigma)) { set_error("elbo_update_bf16_typed: %s", why); return -1; }
+    if (kl_type == MFVI_KL_REVERSE)
+        return mfvi_elbo_update_bf16(mu_bf16, rho_bf16, bn, grads, m, v, n_vi, n_bn, prior_mu, prior_sigma, temp, lr, beta1, beta2, eps, t, seed, kl_out, scratch,
+                                     stream);
+    if (!mu_bf16 || !rho_bf16 || !grads || !m || !v || !kl_out || !scratch || n_vi < 0 || n_bn < 0 || (n_bn > 0 && !bn) || t < 1) {
+        set_error("elbo_update_bf16_typed: bad arguments (t is 1-based)"); return -1; }
+    const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
+    const long long work = std::max<long long>((n_vi + 3) / 4, n_bn);
+    const int nb = nblocks(work, ELBO_UPDATE_MAX_BLOCKS);
+    hipLaunchKernelGGL(elbo_update_bf16_fwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (bf16_t*)mu_bf16, (bf16_t*)rho_bf16, bn, grads, m, v, (long long)n_vi,
                        (long long)n_bn, prior_mu, prior_sigma, temp, beta1, beta2, eps, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)),
                        make_key(seed, DOMAIN_ROUND, 0, 0, (uint32_t)t), (ElboUpdateScratch*)scratch);
     hipLaunchKernelGGL(elbo_update_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const ElboUpdateScratch*)scratch, nb, kl_out, (int*)nullptr,

@@ -27,7 +27,12 @@ INP_NET = dict(nd=(16, 32, 64, 128, 128, 128), nu=(16, 32, 64, 128, 128, 128), n
 class ElboEngine:
     def __init__(self, H, W, task=TASK_DEN, K=1, input_depth=16, temp=1.0, sigma=0.1, lr=1e-3, seed=1, sr_factor=4,
                  theta_deg=None, rank=0, world_size=1, process_group=None, samples_per_launch=None, net_kwargs=None,
-                 autotune=True, param_dtype="f32", downsampler="nearest", tv_weight=0.0, tv_beta=0.5):
+                 autotune=True, param_dtype="f32", downsampler="nearest", tv_weight=0.0, tv_beta=0.5, kl_type="reverse"):
+        # the direction of the KL term: 'reverse' = KL(prior || posterior), what the reference's runners use, 'forward' =
+        # KL(posterior || prior), the textbook ELBO's; refused before anything touches the library
+        from .rowbatch import KL_TYPES, check_kl_type
+        self.kl_type = check_kl_type(kl_type)
+        self._klt = KL_TYPES.index(self.kl_type)      # MFVI_KL_REVERSE / MFVI_KL_FORWARD, a by-value argument of every launch that forms the KL
         # the total-variation term on the image channel of every sample; refused before anything touches the library
         from .tv import check_tv
         self.tv_weight, self.tv_beta = check_tv(tv_weight, tv_beta, task)
@@ -293,9 +298,10 @@ class ElboEngine:
             mu, rho = self.mu, self.rho
             if self.param_dtype == "bf16":      # the KL of the float32 values the bf16 parameters denote (step() fuses this into the update)
                 mu, rho = self.params_f32()[:2]
-            L.check(lib.mfvi_kl(L.ptr(mu), L.ptr(rho), self.n_vi, 0.0, self.prior_sigma, L.ptr(self.acc[1:]), sp))
-            L.check(lib.mfvi_kl_backward(L.ptr(mu), L.ptr(rho), self.n_vi, 0.0, self.prior_sigma, self.temp,
-                                         L.ptr(self.dmu), L.ptr(self.drho), sp))
+            kl, kt = self._kl_entry("mfvi_kl")
+            L.check(kl(L.ptr(mu), L.ptr(rho), self.n_vi, 0.0, self.prior_sigma, *kt, L.ptr(self.acc[1:]), sp))
+            kl_bwd, kt = self._kl_entry("mfvi_kl_backward")
+            L.check(kl_bwd(L.ptr(mu), L.ptr(rho), self.n_vi, 0.0, self.prior_sigma, self.temp, *kt, L.ptr(self.dmu), L.ptr(self.drho), sp))
 
     def set_allreduce_overlap(self, enabled, tail_fraction=0.9):
         """K sharded over ranks: start the exchange under the tail of the backward pass.  The weight gradients of the deep / up-path ops —
@@ -373,9 +379,9 @@ class ElboEngine:
         lib, sp = L.lib(), L.stream_ptr()
         self.grad_only(0, with_kl=False, after_forward=after_forward)
         guard = self._guard() if self.task == TASK_CT else (None, None)
-        L.check(lib.mfvi_elbo_update_guarded(L.ptr(self.params), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi, self.n_bn, 0.0,
-                                             self.prior_sigma, self.temp, self.lr, 0.9, 0.999, 1e-8, L.ptr(self.t_applied), *guard,
-                                             L.ptr(self.acc[1:]), L.ptr(self.upd_scratch), sp))
+        update, kt = self._kl_entry("mfvi_elbo_update_guarded")
+        L.check(update(L.ptr(self.params), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi, self.n_bn, 0.0, self.prior_sigma, self.temp, *kt,
+                       self.lr, 0.9, 0.999, 1e-8, L.ptr(self.t_applied), *guard, L.ptr(self.acc[1:]), L.ptr(self.upd_scratch), sp))
         self.step_dev.add_(1)
 
     def enable_graph(self, warmup=3, side_stream=None):
@@ -419,19 +425,25 @@ class ElboEngine:
         self.grad_only(self.t, with_kl=False, after_forward=after_forward)
         self.t += 1
         if self.param_dtype == "bf16":
-            L.check(lib.mfvi_elbo_update_bf16(L.ptr(self.mu), L.ptr(self.rho), L.ptr(self.bn), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi,
-                                              self.n_bn, 0.0, self.prior_sigma, self.temp, self.lr, 0.9, 0.999, 1e-8, self.t, self.seed,
-                                              L.ptr(self.acc[1:]), L.ptr(self.upd_scratch), sp))
+            update, kt = self._kl_entry("mfvi_elbo_update_bf16")
+            L.check(update(L.ptr(self.mu), L.ptr(self.rho), L.ptr(self.bn), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi, self.n_bn, 0.0,
+                           self.prior_sigma, self.temp, *kt, self.lr, 0.9, 0.999, 1e-8, self.t, self.seed, L.ptr(self.acc[1:]), L.ptr(self.upd_scratch), sp))
             return
         if self.task == TASK_CT:
             # `if not torch.isnan(loss): optimizer.step()` (bayesian_optimization.py:581-582) decided on the device: no host sync
-            L.check(lib.mfvi_elbo_update_guarded(L.ptr(self.params), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi, self.n_bn, 0.0,
-                                                 self.prior_sigma, self.temp, self.lr, 0.9, 0.999, 1e-8, L.ptr(self.t_applied), *self._guard(),
-                                                 L.ptr(self.acc[1:]), L.ptr(self.upd_scratch), sp))
+            update, kt = self._kl_entry("mfvi_elbo_update_guarded")
+            L.check(update(L.ptr(self.params), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi, self.n_bn, 0.0, self.prior_sigma, self.temp, *kt,
+                           self.lr, 0.9, 0.999, 1e-8, L.ptr(self.t_applied), *self._guard(), L.ptr(self.acc[1:]), L.ptr(self.upd_scratch), sp))
             return
-        L.check(lib.mfvi_elbo_update(L.ptr(self.params), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi, self.n_bn, 0.0,
-                                     self.prior_sigma, self.temp, self.lr, 0.9, 0.999, 1e-8, self.t, L.ptr(self.acc[1:]),
-                                     L.ptr(self.upd_scratch), sp))
+        update, kt = self._kl_entry("mfvi_elbo_update")
+        L.check(update(L.ptr(self.params), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi, self.n_bn, 0.0, self.prior_sigma, self.temp, *kt,
+                       self.lr, 0.9, 0.999, 1e-8, self.t, L.ptr(self.acc[1:]), L.ptr(self.upd_scratch), sp))
+
+    def _kl_entry(self, name):
+        """(entry point, its direction argument) of a launch that forms the KL: 'reverse' calls the entry itself, as before the direction
+        existed; 'forward' calls name_typed, which takes MFVI_KL_FORWARD by value behind the scale of the term."""
+        lib = L.lib()
+        return (getattr(lib, name), ()) if self._klt == L.KL_REVERSE else (getattr(lib, name + "_typed"), (self._klt,))
 
     def _guard(self):
         """(loss_d, loss_f) of the NaN guard: the local double accumulator, or the float that rode the all-reduce when K is sharded
@@ -441,7 +453,7 @@ class ElboEngine:
         return L.ptr(self.acc), None
 
     def losses(self):
-        """(nll, kl, loss) of the last grad_only/step — forces a device sync."""
+        """(nll, kl, loss) of the last grad_only/step, kl in the engine's direction (kl_type) — forces a device sync."""
         if self.world > 1:
             nll = float(self.grads[self.n_params]) / self.K
         else:
@@ -484,6 +496,8 @@ class SiblingEngine(ElboEngine):
         if method == METHOD_MCD:
             nk.update(drop_down=float(dropout_p), drop_up=float(dropout_p))
         kw.pop("temp", None); kw.pop("sigma", None)
+        if "kl_type" in kw:
+            raise TypeError("SiblingEngine has no KL term: kl_type belongs to ElboEngine")
         super().__init__(H, W, task=task, temp=0.0, sigma=0.0, net_kwargs=nk, **kw)
         self.lr0 = self.lr                    # add_noise keeps using the initial rate (LR, not the scheduler's)
 

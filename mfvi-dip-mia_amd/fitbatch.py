@@ -11,7 +11,7 @@ forward, data term, EMA on a second stream beside the backward pass, backward, t
 as its data term, whatever F is.  RNG identity: fit f owns the global samples f * K .. f * K + K - 1 of eps and sample f of the INIT, z0 and input
 perturbation domains, so fit 0 of a batch is the standalone ElboEngine(seed, K)."""
 from . import _lib as L
-from .rowbatch import EXP_WEIGHT, TASKS, ElboRowBatch, per_fit, prior_sigmas      # (re-exported: the helpers' home is rowbatch.py)
+from .rowbatch import EXP_WEIGHT, TASKS, ElboRowBatch, check_kl_type, per_fit, prior_sigmas      # (re-exported: the helpers' home is rowbatch.py)
 
 
 def check_args(H, W, n_fits, task, K, temp, sigma, lr, init):
@@ -38,8 +38,9 @@ class FitBatch(ElboRowBatch):
     targets = None
 
     def __init__(self, H, W, n_fits, task="den", K=1, input_depth=16, temp=1.0, sigma=0.1, lr=1e-3, seed=1, sr_factor=4, net_kwargs=None,
-                 init="per_fit", autotune=True, tv_weight=0.0, tv_beta=0.5):
+                 init="per_fit", autotune=True, tv_weight=0.0, tv_beta=0.5, kl_type="reverse"):
         self.temps, self.sigmas, self.lrs = check_args(H, W, n_fits, task, K, temp, sigma, lr, init)
+        self.kl_types = check_kl_type(kl_type, int(n_fits))      # a name, or one per fit: one batch can run both directions on one image
         from .tv import check_tv
         self.tv_weights, self.tv_beta = check_tv(tv_weight, tv_beta, task, n=int(n_fits))      # a scalar, or one weight per fit
         if task == "sr" and (sr_factor < 1 or H % sr_factor or W % sr_factor):
@@ -68,7 +69,7 @@ class FitBatch(ElboRowBatch):
     def _make_engine(self, f, autotune):
         from .engine import ElboEngine
         return ElboEngine(self.H, self.W, task=self.task, K=self.K, input_depth=self.input_depth, temp=self.temps[f], sigma=self.sigmas[f],
-                          lr=self.lrs[f], seed=self.seed, sr_factor=self.sr_factor, net_kwargs=self.net_kwargs, autotune=autotune, **self._tv_kw(f))
+                          lr=self.lrs[f], seed=self.seed, sr_factor=self.sr_factor, net_kwargs=self.net_kwargs, autotune=autotune, **self._tv_kw(f), **self._kl_kw(f))
 
     def _hand_target(self, eng, f):
         if self.targets is not None:

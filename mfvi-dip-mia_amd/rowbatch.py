@@ -35,6 +35,23 @@ def per_fit(value, n_fits, name):
     return vals
 
 
+KL_TYPES = ("reverse", "forward")      # MFVI_KL_REVERSE, MFVI_KL_FORWARD: a name's index is its value in the C ABI
+
+
+def check_kl_type(kl_type, n=None, name="kl_type"):
+    """The direction of the KL term, refused without the library: 'reverse' = KL(prior || posterior), what the
+    reference's runners use, or 'forward' = KL(posterior || prior), the textbook ELBO's.  n None: one name -> the name; else one name, or
+    one per row -> the list of n names."""
+    names = [kl_type] * (n or 1) if isinstance(kl_type, str) or not hasattr(kl_type, "__iter__") else list(kl_type)
+    if len(names) != (n or 1):
+        raise ValueError("%s: %d values for %s (a name, or one name per fit)" % (name, len(names), "%d fits" % n if n else "one fit"))
+    for k in names:
+        if k not in KL_TYPES:
+            raise ValueError("%s=%r: 'reverse' or 'forward'" % (name, k))
+    names = [str(k) for k in names]
+    return names[0] if n is None else names
+
+
 def prior_sigmas(temps, sigmas):
     """Per fit, exactly as ElboEngine computes it (bayesian_optimization.py:1335-1336 + modules/module.py:38, rounded to fp32)."""
     import numpy as np
@@ -243,6 +260,11 @@ class RowBatch:
         """The keywords that hand row f's term to its standalone engine."""
         return dict(tv_weight=self.tv_weights[f], tv_beta=self.tv_beta) if self.tv_weights is not None else {}
 
+    def _kl_kw(self, f):
+        """The keyword that hands row f's direction of the KL term to its standalone engine (none where the class has no KL term)."""
+        kl = getattr(self, "kl_types", None)
+        return dict(kl_type=kl[f]) if kl is not None else {}
+
     def recon(self):
         """clip(ema[:, 0], 0, 1) [n_rows, H, W]: the smoothed reconstruction of every row."""
         self._wait_ema()
@@ -289,8 +311,10 @@ class RowBatch:
 
 
 class ElboRowBatch(RowBatch):
-    """The mean-field VI layer: per-row temp / prior sigma / lr, the KL term and Adam in one launch over all rows.  The subclass sets
-    temps, sigmas and lrs (its check_args) before _allocate."""
+    """The mean-field VI layer: per-row temp / prior sigma / lr / direction of the KL term, the KL term and Adam in one launch over all rows.
+    The subclass sets temps, sigmas, lrs (its check_args) and kl_types (check_kl_type) before _allocate."""
+    kl_types = None             # per row 'reverse' or 'forward' (DESIGN.md section 25)
+    _kl_dev = None              # the directions on the device (int32 [n_rows]) once a row is forward; all reverse: nothing, and the untyped update
 
     def _alloc_own(self):
         import numpy as np
@@ -299,14 +323,23 @@ class ElboRowBatch(RowBatch):
         self.kl = torch.zeros(R, dtype=torch.float64, device="cuda")
         self.hyper = torch.tensor(np.array([[0.0, ps, t, r] for ps, t, r in zip(self.prior_sigma, self.temps, self.lrs)], np.float32), device="cuda")   # mfvi_fit_hyper[n_rows]
         self.upd_scratch = torch.zeros(L.lib().mfvi_elbo_update_fits_scratch_bytes(R), dtype=torch.uint8, device="cuda")
+        if self.kl_types is None:
+            self.kl_types = ["reverse"] * R
+        if any(k != "reverse" for k in self.kl_types):
+            self._kl_dev = torch.tensor([KL_TYPES.index(k) for k in self.kl_types], dtype=torch.int32, device="cuda")
 
     def _update(self):
+        if self._kl_dev is not None:      # some row is forward: the same two launches, the direction read per row on the device
+            L.check(L.lib().mfvi_elbo_update_fits_typed(L.ptr(self._pbuf), L.ptr(self._grows), L.ptr(self._mbuf), L.ptr(self._vbuf), self.n_vi, self.n_bn,
+                                                        self.stride, self.stride, self.n_rows, L.ptr(self.hyper), L.ptr(self._kl_dev), 0.9, 0.999, 1e-8, self.t,
+                                                        L.ptr(self.nll_acc), L.ptr(self.dead_dev), L.ptr(self.kl), L.ptr(self.upd_scratch), L.stream_ptr()))
+            return
         L.check(L.lib().mfvi_elbo_update_fits(L.ptr(self._pbuf), L.ptr(self._grows), L.ptr(self._mbuf), L.ptr(self._vbuf), self.n_vi, self.n_bn, self.stride,
                                               self.stride, self.n_rows, L.ptr(self.hyper), 0.9, 0.999, 1e-8, self.t, L.ptr(self.nll_acc), L.ptr(self.dead_dev),
                                               L.ptr(self.kl), L.ptr(self.upd_scratch), L.stream_ptr()))
 
     def losses(self):
-        """(nll[n_rows], kl[n_rows], loss[n_rows]) of the last step (kl: of the parameters that step started from) -- forces a device sync.
+        """(nll[n_rows], kl[n_rows], loss[n_rows]) of the last step (kl: of the parameters that step started from, in the row's direction) -- forces a device sync.
         After grad_only alone kl is stale: the KL term is part of the update launch."""
         import numpy as np
         nll = self.nll_acc.cpu().numpy() / self.K
