@@ -354,6 +354,41 @@ int mfvi_elbo_update_guarded_typed(float* params, float* grads, float* m, float*
 int mfvi_elbo_update_bf16_typed(void* mu_bf16, void* rho_bf16, float* bn, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, float prior_mu,
                                 float prior_sigma, float temp, int kl_type, float lr, float beta1, float beta2, float eps, int t, uint64_t seed,
                                 double* kl_out, void* scratch, void* stream);
+/* ---- scale-mixture prior: the Monte-Carlo KL term -------------------------------------------------------------
+ * With prior = {'mu': [...], 'sigma': [...], 'pi': [...]} the reference's layers carry p(w) = sum_j pi_j N(w; m_j, sigma_j^2)
+ * (MixtureNormal, BayTorch/modules/module.py:32-35, distributions/distributions.py:6-28; the pi as given, not normalised) and, with a
+ * kl_type other than 'reverse', estimate KL(q || p) from ONE reparametrised draw per weight (mc_kl_divergence, distributions.py:30-35).
+ * Per (mu, rho, eps), s = softplus(rho), w = mu + s eps:
+ *     a_j = log pi_j - log sigma_j - (w - m_j)^2 / (2 sigma_j^2)        L = max_j a_j + log sum_j exp(a_j - max)
+ *     term = (-eps^2 / 2 - log s) - L        r_j = exp(a_j - L)        G = sum_j r_j (w - m_j) / sigma_j^2
+ *     dterm/dmu = G        dterm/drho = (G eps - 1 / s) sigmoid(rho)
+ * float32 per element, summed in float64.  The log-sum-exp keeps the term finite where the reference's literal log(sum pi_j exp(..))
+ * underflows.  sigma holds the FINAL scales (the reference's prior['sigma'] + 1e-6, rounded to float32).
+ * The draw: RNG domain 8 (KLMC), stream 0; element i of the flat MU block is lane i & 3 of Philox block i >> 2; sample = the row of a
+ * batch (0 for one fit), step = the iteration's counter word.  Nothing of the rank or of K enters the key.
+ * Refused with -1 and mfvi_last_error() before any launch: null pointers, n < 1, i0 < 0, prior->n outside 1..MFVI_MIXTURE_MAX, a pi or
+ * sigma that is not finite or not > 0, a 1 / sigma^2 that is not a normal float32, an m that is not finite.
+ * The reverse direction against a mixture is not built: the reference's MixtureNormal.rsample (distributions.py:17-22) yields one scalar
+ * shared by all weights that is no draw from the mixture. */
+#define MFVI_MIXTURE_MAX 4
+typedef struct { int32_t n; float pi[MFVI_MIXTURE_MAX], mu[MFVI_MIXTURE_MAX], sigma[MFVI_MIXTURE_MAX]; } mfvi_mixture_prior;
+/* The unfused pair on n (mu, rho) pairs that are elements i0 .. i0 + n - 1 of the stream: a layer's slice of the flat block draws what the
+ * whole block draws there.  prior: a HOST pointer, copied into the launch.  eps: n normals in device memory to use instead, or NULL to
+ * draw.  kl_out (device double) is overwritten; dmu += scale * dterm/dmu, drho += scale * dterm/drho. */
+int mfvi_kl_mixture(const float* mu, const float* rho, int64_t n, int64_t i0, const mfvi_mixture_prior* prior, const float* eps, uint64_t seed,
+                    uint32_t sample, uint32_t step, double* kl_out, void* stream);
+int mfvi_kl_mixture_backward(const float* mu, const float* rho, int64_t n, int64_t i0, const mfvi_mixture_prior* prior, const float* eps, uint64_t seed,
+                             uint32_t sample, uint32_t step, float scale, float* dmu, float* drho, void* stream);
+/* mfvi_elbo_update / mfvi_elbo_update_guarded with the mixture term in place of the Gaussian KL: the same Adam, partial sums, finish kernel
+ * and scratch.  The counter word of the draw is step + (step_dev ? *step_dev : 0), step_dev read on the device (the convention of
+ * mfvi_perturb_input_dev), so the device-resident iteration and a captured graph replay with a fresh draw. */
+int mfvi_elbo_update_mixture(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, const mfvi_mixture_prior* prior, float temp,
+                             float lr, float beta1, float beta2, float eps, int t, uint64_t seed, uint32_t sample, uint32_t step, const int32_t* step_dev,
+                             double* kl_out, void* scratch, void* stream);
+int mfvi_elbo_update_guarded_mixture(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, const mfvi_mixture_prior* prior,
+                                     float temp, float lr, float beta1, float beta2, float eps, int32_t* t_applied, const double* loss_d,
+                                     const float* loss_f, uint64_t seed, uint32_t sample, uint32_t step, const int32_t* step_dev, double* kl_out,
+                                     void* scratch, void* stream);
 int mfvi_adamw_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                             const int32_t* t_applied, const double* loss_d, const float* loss_f, float weight_decay, void* stream);
 int mfvi_step_advance(int32_t* t_applied, const double* loss_d, const float* loss_f, void* stream);
@@ -523,6 +558,15 @@ int mfvi_elbo_update_fits(float* params, float* grads, float* m, float* v, int64
 int mfvi_elbo_update_fits_typed(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, int64_t param_stride, int64_t grad_stride,
                                 int n_fits, const mfvi_fit_hyper* hyper_dev, const int32_t* kl_type_dev, float beta1, float beta2, float eps, int t,
                                 const double* nll, int32_t* dead, double* kl_out, void* scratch, void* stream);
+/* mfvi_elbo_update_fits_typed with a prior table: mix_dev[n_fits] in DEVICE memory.  A row with n == 0 runs its Gaussian prior of hyper_dev
+ * in its direction of kl_type_dev (NULL: reverse), exactly as _typed does; a row with n in 1..MFVI_MIXTURE_MAX runs the mixture term
+ * (temp and lr still from hyper_dev; its kl_type entry is not read) and draws with sample sample0 + f and counter word
+ * step + (step_dev ? *step_dev : 0).  The choice is made once per block.  mix_dev == NULL calls _typed itself.  A row whose table entry
+ * mfvi_kl_mixture would refuse can only be met on the device: it writes nothing and gets dead[f] = 1. */
+int mfvi_elbo_update_fits_mixture(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, int64_t param_stride, int64_t grad_stride,
+                                  int n_fits, const mfvi_fit_hyper* hyper_dev, const int32_t* kl_type_dev, const mfvi_mixture_prior* mix_dev, uint64_t seed,
+                                  uint32_t sample0, uint32_t step, const int32_t* step_dev, float beta1, float beta2, float eps, int t, const double* nll,
+                                  int32_t* dead, double* kl_out, void* scratch, void* stream);
 /* The EMA part of mfvi_bookkeep per fit: sample means of out[:, 0] and exp(-out[:, 1]) over the fit's S samples (out [n_fits * S][C][H][W],
  * C = 1 or 2) and ema[f] = first ? mean : ema[f] * weight + mean * (1 - weight); ema [n_fits][C][H][W]. */
 int mfvi_ema_fits(const float* out, int n_fits, int S, int C, int H, int W, float* ema, float weight, int first, void* stream);

@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MFVI_LIB_PATH") or os.path.join(HERE, "libmfvi_hip.so")      # MFVI_LIB_PATH: an experimental build (A/B timing)
 
 OP_CONV, OP_CONCAT_UP, OP_CONV_LRT = 1, 2, 3
-DOMAIN_EPS, DOMAIN_INPUT, DOMAIN_INIT, DOMAIN_UNIFORM, DOMAIN_SGLD, DOMAIN_DROPOUT, DOMAIN_ROUND, DOMAIN_LRT = 0, 1, 2, 3, 4, 5, 6, 7
+DOMAIN_EPS, DOMAIN_INPUT, DOMAIN_INIT, DOMAIN_UNIFORM, DOMAIN_SGLD, DOMAIN_DROPOUT, DOMAIN_ROUND, DOMAIN_LRT, DOMAIN_KLMC = 0, 1, 2, 3, 4, 5, 6, 7, 8
 PARAM_F32, PARAM_BF16 = 0, 1
 PRED_RAW, PRED_LOGPREC, PRED_INP, PRED_MEAN_ONLY = 0, 1, 2, 3             # MFVI_PRED_* (posterior predictive statistics)
 MASKED_SQ_ERR_BLOCKS = 64                                                 # MFVI_MASKED_SQ_ERR_BLOCKS (mfvi_masked_sq_err_fits scratch)
@@ -23,6 +23,14 @@ class TensorDesc(C.Structure):
 class OpDesc(C.Structure):
     _fields_ = [("type", C.c_int32), ("in0", C.c_int32), ("in1", C.c_int32), ("out", C.c_int32), ("ksize", C.c_int32),
                 ("stride", C.c_int32), ("layer_id", C.c_int32), ("up_mode", C.c_int32), ("w_off", C.c_int64), ("b_off", C.c_int64)]
+
+
+MIXTURE_MAX = 4                                                           # MFVI_MIXTURE_MAX (components of a scale-mixture prior)
+
+
+class MixturePrior(C.Structure):
+    """mfvi_mixture_prior: sigma holds the final scales (1e-6 already added)."""
+    _fields_ = [("n", C.c_int32), ("pi", C.c_float * MIXTURE_MAX), ("mu", C.c_float * MIXTURE_MAX), ("sigma", C.c_float * MIXTURE_MAX)]
 
 
 class MfviError(RuntimeError):
@@ -72,6 +80,11 @@ SIGNATURES = {
     "mfvi_kl_backward": (_I, [_P, _P, _I64, _F, _F, _F, _P, _P, _P]),
     "mfvi_kl_typed": (_I, [_P, _P, _I64, _F, _F, _I, _P, _P]),
     "mfvi_kl_backward_typed": (_I, [_P, _P, _I64, _F, _F, _F, _I, _P, _P, _P]),
+    "mfvi_kl_mixture": (_I, [_P, _P, _I64, _I64, _P, _P, _U64, _U32, _U32, _P, _P]),
+    "mfvi_kl_mixture_backward": (_I, [_P, _P, _I64, _I64, _P, _P, _U64, _U32, _U32, _F, _P, _P, _P]),
+    "mfvi_elbo_update_mixture": (_I, [_P, _P, _P, _P, _I64, _I64, _P, _F, _F, _F, _F, _F, _I, _U64, _U32, _U32, _P, _P, _P, _P]),
+    "mfvi_elbo_update_guarded_mixture": (_I, [_P, _P, _P, _P, _I64, _I64, _P, _F, _F, _F, _F, _F, _P, _P, _P, _U64, _U32, _U32, _P, _P, _P, _P]),
+    "mfvi_elbo_update_fits_mixture": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I, _P, _P, _P, _U64, _U32, _U32, _P, _F, _F, _F, _I, _P, _P, _P, _P, _P]),
     "mfvi_adam_step": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _I, _P]),
     "mfvi_elbo_update_scratch_bytes": (_I64, []),
     "mfvi_elbo_update": (_I, [_P, _P, _P, _P, _I64, _I64, _F, _F, _F, _F, _F, _F, _F, _I, _P, _P, _P]),

@@ -31,7 +31,11 @@ class Conv2dRT(nn.Module):
         self.kernel_size = tuple(kernel_size)
         self.kwargs = dict(stride=stride, padding=padding, dilation=dilation, groups=groups)
         self.kl_type = kl_type
-        self.prior_mu, self.prior_sigma = float(prior['mu']), float(prior['sigma']) + 1e-6          # module.py:38
+        if 'pi' in prior:      # a scale mixture (module.py:32-35), checked by the owner: the components' weights, means and final scales
+            mix = owner._mix
+            self.prior_pi, self.prior_mu, self.prior_sigma = list(mix['pi']), list(mix['mu']), list(mix['scale'])
+        else:
+            self.prior_mu, self.prior_sigma = float(prior['mu']), float(prior['sigma']) + 1e-6      # module.py:38
         self.posterior_mu_initial, self.posterior_rho_initial = posteriors['mu'], posteriors['rho']
         for name in ('W_mu', 'W_rho', 'bias_mu', 'bias_rho'):          # filled with views of the flat buffer by the owner
             self.register_parameter(name, None)
@@ -93,6 +97,20 @@ class _KLFunction(torch.autograd.Function):
         return (None, None, None, None, None) + tuple(owner._hip_kl_backward(lo, hi, pm, ps, g))
 
 
+class _KLMixFunction(torch.autograd.Function):
+    """The Monte-Carlo term against a scale-mixture prior: the backward uses the draw (counter word `step`) of the call that made it."""
+    @staticmethod
+    def forward(ctx, owner, lo, hi, step, flat, eps, *params):
+        ctx.args = (owner, lo, hi, step, flat, eps)
+        return owner._hip_kl_mix(lo, hi, step, eps)
+
+    @staticmethod
+    def backward(ctx, g):
+        owner, lo, hi, step, flat, eps = ctx.args
+        grads = owner._hip_kl_mix_backward(lo, hi, step, g, flat=flat, eps=eps)
+        return (None, None, None, None, None, None) + ((grads,) if flat else tuple(grads))
+
+
 class _KLFunctionFlat(torch.autograd.Function):
     @staticmethod
     def forward(ctx, owner, lo, hi, prior_mu, prior_sigma, flat):
@@ -130,8 +148,22 @@ class MeanFieldVI(nn.Module):
         self._klt = L.KL_REVERSE if kl_type == 'reverse' else L.KL_FORWARD      # modules/module.py:76-80: anything but 'reverse' is forward
         prior = {'mu': 0, 'sigma': 0.1} if prior is None else prior                         # modules/module.py:23-30
         posteriors = {'mu': (0, 0.1), 'rho': (-3., 0.1)} if posteriors is None else posteriors
+        self._mix = None
         if 'pi' in prior:
-            raise NotImplementedError("scale-mixture priors (MixtureNormal) are not used by the runners and not built")
+            # a scale mixture of Gaussians (modules/module.py:32-35): with kl_type != 'reverse' the KL term is the reference's one-draw
+            # Monte-Carlo estimate log q(w) - log p(w) (distributions.py:30-35)
+            import numpy as np
+            if any(np.ndim(prior.get(k, 0)) == 0 for k in ('pi', 'mu', 'sigma')):
+                raise NotImplementedError("a scale-mixture prior takes one SEQUENCE each for 'pi', 'mu' and 'sigma': with a scalar the reference's own "
+                                          "MixtureNormal fails with a TypeError (len() of a 0-d tensor, BayTorch/distributions/distributions.py:8-9)")
+            if kl_type == 'reverse':
+                raise NotImplementedError("a scale-mixture prior with kl_type='reverse' is not built: the reference's estimate of that direction takes "
+                                          "its \"sample\" from MixtureNormal.rsample (BayTorch/distributions/distributions.py:17-22), one scalar shared by "
+                                          "all weights that is no draw from the mixture; pass another kl_type (the forward direction)")
+            from .rowbatch import check_prior_mixture, mixture_struct
+            self._mix = check_prior_mixture({k: prior[k] for k in ('pi', 'mu', 'sigma')}, "prior")
+            self._mix_struct = mixture_struct(self._mix)
+            self._kl_step = 0      # the counter word of the next KL draw: its own counter, so the eps of the forward passes do not move
         device = torch.device(device)
         if device.type != 'cuda':
             raise NotImplementedError("this implementation runs on the GPU only (device=%s); there is no CPU path" % device)
@@ -398,10 +430,23 @@ class MeanFieldVI(nn.Module):
         self._sampling = bool(enabled)
         return self
 
-    def kl(self):
+    def kl(self, eps=None):
         """Sum of the layers' KL terms (kl_type 'reverse': KL(prior || posterior), else KL(posterior || prior)) as a tensor of shape [1]
-        (freq_to_bayes.py:43-48)."""
+        (freq_to_bayes.py:43-48).  With a scale-mixture prior: the one-draw Monte-Carlo estimate, a fresh draw per call; eps (mixture
+        only): n_vi normals in the flat block's order (layer after layer, W | bias) to use instead of the draw."""
         m = self._vi[0]
+        if eps is not None and self._mix is None:
+            raise ValueError("eps is the draw of the Monte-Carlo KL term of a scale-mixture prior; this net's KL term is closed-form")
+        if self._mix is not None:      # one fresh draw per call (RNG domain 8); the backward of this call uses the same draw
+            if eps is not None:
+                eps = eps.detach().to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+                if eps.numel() != self.n_vi:
+                    raise ValueError("eps of %d elements, expected n_vi = %d" % (eps.numel(), self.n_vi))
+            step = self._next_kl_step()
+            if getattr(self, "_flat_mode", False):
+                return _KLMixFunction.apply(self, 0, self.n_vi, step, True, eps, next(self.parameters()))
+            vi_params = [p for q in self._vi for p in ([q.W_mu, q.W_rho] + ([q.bias_mu, q.bias_rho] if q._has_bias else []))]
+            return _KLMixFunction.apply(self, 0, self.n_vi, step, False, eps, *vi_params)
         if getattr(self, "_flat_mode", False):
             return _KLFunctionFlat.apply(self, 0, self.n_vi, m.prior_mu, m.prior_sigma, next(self.parameters()))
         vi_params = [p for q in self._vi for p in ([q.W_mu, q.W_rho] + ([q.bias_mu, q.bias_rho] if q._has_bias else []))]
@@ -409,7 +454,14 @@ class MeanFieldVI(nn.Module):
 
     def _layer_kl(self, m):
         hi = (m._b_off + m.out_channels) if m._has_bias else m._w_off + m.W_mu.numel()
+        if self._mix is not None:      # the layer's slice of the flat block's stream, at a fresh counter value
+            return self._hip_kl_mix(m._w_off, hi, self._next_kl_step())[0]
         return self._hip_kl(m._w_off, hi, m.prior_mu, m.prior_sigma)[0]
+
+    def _next_kl_step(self):
+        step = self._kl_step
+        self._kl_step = (step + 1) & 0xffffffff
+        return step
 
     # ------------------------------------------------------------------ HIP calls
     def _hip_forward(self, x):
@@ -541,6 +593,25 @@ class MeanFieldVI(nn.Module):
                                       self._klt, L.ptr(acc), L.stream_ptr()))
         return acc.float()                                   # FloatTensor of shape [1], as the reference returns
 
+    def _hip_kl_mix(self, lo, hi, step, eps=None):
+        """The Monte-Carlo mixture term of elements lo .. hi - 1 of the flat MU block with the draw of counter word `step` (or eps[lo:hi])."""
+        import ctypes
+        mu, rho, _ = self._blocks()
+        acc = torch.zeros(1, dtype=torch.float64, device=self.device)
+        L.check(L.lib().mfvi_kl_mixture(L.ptr(mu[lo:hi]), L.ptr(rho[lo:hi]), hi - lo, lo, ctypes.byref(self._mix_struct),
+                                        L.ptr(eps[lo:hi]) if eps is not None else None, self.seed, 0, step, L.ptr(acc),
+                                        L.stream_ptr()))
+        return acc.float()
+
+    def _hip_kl_mix_backward(self, lo, hi, step, gout, flat=False, eps=None):
+        import ctypes
+        mu, rho, _ = self._blocks()
+        n = self.n_vi
+        g = torch.zeros(2 * n + (self.n_bn if flat else 0), dtype=torch.float32, device=self.device)
+        L.check(L.lib().mfvi_kl_mixture_backward(L.ptr(mu[lo:hi]), L.ptr(rho[lo:hi]), hi - lo, lo, ctypes.byref(self._mix_struct),
+                                                 L.ptr(eps[lo:hi]) if eps is not None else None, self.seed, 0, step, float(gout.reshape(-1)[0]), L.ptr(g[lo:hi]), L.ptr(g[n + lo:n + hi]), L.stream_ptr()))
+        return g if flat else self._vi_grads(g)
+
     def _hip_kl_backward(self, lo, hi, prior_mu, prior_sigma, gout, flat=False):
         mu, rho, _ = self._blocks()
         n = self.n_vi
@@ -551,6 +622,11 @@ class MeanFieldVI(nn.Module):
                                                L.ptr(g[n + lo:n + hi]), L.stream_ptr()))
         if flat:
             return g
+        return self._vi_grads(g)
+
+    def _vi_grads(self, g):
+        """The per-Parameter views (W_mu, W_rho, bias_mu, bias_rho layer after layer) of a flat [MU | RHO] gradient."""
+        n = self.n_vi
         grads = []
         for m in self._vi:
             nw = m.W_mu.numel()

@@ -113,7 +113,7 @@ __device__ __forceinline__ void spec_boxmuller(uint32_t a, uint32_t b, float& z0
     z1 = rad * sn;
 }
 
-enum { DOMAIN_EPS = 0, DOMAIN_INPUT = 1, DOMAIN_INIT = 2, DOMAIN_UNIFORM = 3, DOMAIN_SGLD = 4, DOMAIN_DROPOUT = 5, DOMAIN_ROUND = 6, DOMAIN_LRT = 7 };
+enum { DOMAIN_EPS = 0, DOMAIN_INPUT = 1, DOMAIN_INIT = 2, DOMAIN_UNIFORM = 3, DOMAIN_SGLD = 4, DOMAIN_DROPOUT = 5, DOMAIN_ROUND = 6, DOMAIN_LRT = 7, DOMAIN_KLMC = 8 };
 
 struct RngKey {              // everything but the block index
     uint32_t k0, k1;         // seed lo/hi

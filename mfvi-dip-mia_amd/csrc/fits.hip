@@ -100,6 +100,56 @@ __global__ __launch_bounds__(256) void elbo_update_fits_typed_finish_kernel(cons
     if (threadIdx.x == 0) { kl_out[fit] = t; if (!isfinite(nll[fit])) dead[fit] = 1; }
 }
 
+// the typed pair with every fit's prior table entry, read once per block: n == 0 runs the Gaussian prior in the fit's direction, as above;
+// n in 1..MFVI_MIXTURE_MAX the Monte-Carlo mixture term with sample sample0 + fit of the draw's stream.  An entry the host entries would
+// refuse can only be met here: the fit's blocks write nothing and its finish block marks it dead.
+__device__ __forceinline__ bool fit_row_runs(const mfvi_mixture_prior& mix, int kt)
+{
+    return mix.n == 0 ? (kt == MFVI_KL_REVERSE || kt == MFVI_KL_FORWARD) : mix_prior_fault(mix) == MIX_OK;
+}
+__global__ __launch_bounds__(256) void elbo_update_fits_mix_kernel(float* __restrict__ params, float* __restrict__ grads, float* __restrict__ m, float* __restrict__ v,
+                                                                   long long n_vi, long long n_bn, long long param_stride, long long grad_stride,
+                                                                   const mfvi_fit_hyper* __restrict__ hyper, const int32_t* __restrict__ kl_type,
+                                                                   const mfvi_mixture_prior* __restrict__ mix_tab, RngKey key, float b1, float b2, float eps,
+                                                                   double bc1, float inv_sqrt_bc2, const double* __restrict__ nll,
+                                                                   const int32_t* __restrict__ dead, double* __restrict__ partial)
+{
+    __shared__ double s_red[8];
+    key = key_now(key);
+    const int fit = blockIdx.y;
+    const int kt = kl_type ? kl_type[fit] : MFVI_KL_REVERSE;
+    const mfvi_mixture_prior mix = mix_tab[fit];
+    if (!fit_row_runs(mix, kt)) return;
+    const mfvi_fit_hyper h = hyper[fit];
+    const bool skip = dead[fit] != 0 || !isfinite(nll[fit]);
+    const float step_size = (float)((double)h.lr / bc1);
+    const long long po = (long long)fit * param_stride;
+    float* __restrict__ g = grads + (long long)fit * grad_stride;
+    double acc;
+    if (mix.n != 0) {
+        key.sample += (uint32_t)fit;
+        acc = elbo_update_share_mix(params + po, g, m + po, v + po, n_vi, n_bn, mix_prepare(mix), key, h.temp, b1, b2, eps, step_size, inv_sqrt_bc2, skip);
+    } else {
+        acc = kt == MFVI_KL_FORWARD
+            ? elbo_update_share_fwd(params + po, g, m + po, v + po, n_vi, n_bn, h.prior_mu, h.prior_sigma, h.temp, b1, b2, eps, step_size, inv_sqrt_bc2, skip)
+            : elbo_update_share(params + po, g, m + po, v + po, n_vi, n_bn, h.prior_mu, h.prior_sigma, h.temp, b1, b2, eps, step_size, inv_sqrt_bc2, skip);
+    }
+    const double tot = block_sum_d(acc, s_red);
+    if (threadIdx.x == 0) partial[(long long)fit * UPDATE_MAX_BLOCKS + blockIdx.x] = tot;
+}
+__global__ __launch_bounds__(256) void elbo_update_fits_mix_finish_kernel(const double* __restrict__ partial, int n_blocks, const double* __restrict__ nll,
+                                                                          const int32_t* __restrict__ kl_type, const mfvi_mixture_prior* __restrict__ mix_tab,
+                                                                          int32_t* __restrict__ dead, double* __restrict__ kl_out)
+{
+    __shared__ double s_red[8];
+    const int fit = blockIdx.x;
+    if (!fit_row_runs(mix_tab[fit], kl_type ? kl_type[fit] : MFVI_KL_REVERSE)) { if (threadIdx.x == 0) dead[fit] = 1; return; }
+    double t = 0;
+    for (int b = threadIdx.x; b < n_blocks; b += 256) t += partial[(long long)fit * UPDATE_MAX_BLOCKS + b];
+    t = block_sum_d(t, s_red);
+    if (threadIdx.x == 0) { kl_out[fit] = t; if (!isfinite(nll[fit])) dead[fit] = 1; }
+}
+
 __global__ __launch_bounds__(256) void ema_fits_kernel(const float* __restrict__ out, int S, int C, long long HW, float* __restrict__ ema, float w, int first)
 {
     const float* __restrict__ o = out + (long long)blockIdx.y * S * C * HW;
@@ -227,6 +277,30 @@ int mfvi_elbo_update_fits_typed(float* params, float* grads, float* m, float* v,
                        (long long)param_stride, (long long)grad_stride, hyper_dev, kl_type_dev, beta1, beta2, eps, bc1, (float)(1.0 / sqrt(bc2)), nll,
                        (const int32_t*)dead, (double*)scratch);
     hipLaunchKernelGGL(elbo_update_fits_typed_finish_kernel, dim3(n_fits), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, nb, nll, kl_type_dev, dead,
+                       kl_out);
+    return (int)hipGetLastError();
+}
+
+int mfvi_elbo_update_fits_mixture(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, int64_t param_stride, int64_t grad_stride,
+                                  int n_fits, const mfvi_fit_hyper* hyper_dev, const int32_t* kl_type_dev, const mfvi_mixture_prior* mix_dev, uint64_t seed,
+                                  uint32_t sample0, uint32_t step, const int32_t* step_dev, float beta1, float beta2, float eps, int t, const double* nll,
+                                  int32_t* dead, double* kl_out, void* scratch, void* stream)
+{
+    if (!mix_dev)          // no row has a mixture: the entry above, as it is
+        return mfvi_elbo_update_fits_typed(params, grads, m, v, n_vi, n_bn, param_stride, grad_stride, n_fits, hyper_dev, kl_type_dev, beta1, beta2, eps, t, nll, dead,
+                                           kl_out, scratch, stream);
+    if (!params || !grads || !m || !v || !hyper_dev || !nll || !dead || !kl_out || !scratch || n_vi < 0 || n_bn < 0 || t < 1 || n_fits < 1 || n_fits > 65535 ||
+        param_stride < 2 * n_vi + n_bn || grad_stride < 2 * n_vi + n_bn || n_vi > ((int64_t)1 << 34)) {
+        set_error("elbo_update_fits_mixture: bad arguments (t is 1-based, strides >= 2 n_vi + n_bn, scratch of mfvi_elbo_update_fits_scratch_bytes(n_fits) bytes)");
+        return -1; }
+    const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
+    const long long work = n_vi > n_bn ? n_vi : n_bn;
+    const int nb = nblocks(work, UPDATE_MAX_BLOCKS);
+    const RngKey key = klmc_key(seed, sample0, step, step_dev);
+    hipLaunchKernelGGL(elbo_update_fits_mix_kernel, dim3(nb, n_fits), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, (long long)n_vi, (long long)n_bn,
+                       (long long)param_stride, (long long)grad_stride, hyper_dev, kl_type_dev, mix_dev, key, beta1, beta2, eps, bc1, (float)(1.0 / sqrt(bc2)), nll,
+                       (const int32_t*)dead, (double*)scratch);
+    hipLaunchKernelGGL(elbo_update_fits_mix_finish_kernel, dim3(n_fits), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, nb, nll, kl_type_dev, mix_dev, dead,
                        kl_out);
     return (int)hipGetLastError();
 }

@@ -2,6 +2,7 @@
 // many independent fits in one launch (fits.hip): the arithmetic of a fit in a batch is the single-fit arithmetic by construction.
 #pragma once
 #include "common.h"
+#include "../../include/mfvi_hip.h"
 
 __device__ __forceinline__ void block_atomic_add(double v, double* dst, double* red)
 {
@@ -136,6 +137,130 @@ __device__ __forceinline__ double elbo_update_share_fwd(float* __restrict__ p, f
         const float grho = g[n_vi + i] + temp * dkr;
         g[i] = gmu; g[n_vi + i] = grho;
         adam(i, gmu); adam(n_vi + i, grho);
+    }
+    if (!skip)
+        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_bn; i += (long long)gridDim.x * 256) adam(2 * n_vi + i, g[2 * n_vi + i]);
+    return acc;
+}
+
+// ---- the scale-mixture prior p(w) = sum_j pi_j N(w; m_j, sigma_j^2), J <= 4 (MixtureNormal, BayTorch/distributions/distributions.py:6-28;
+// DESIGN.md section 26).  The KL term against it has no closed form: the reference estimates it with ONE draw w = mu + s eps per weight
+// (mc_kl_divergence, :30-35, through VIModule._kl with kl_type != 'reverse') as log q(w) - log p(w) ----
+// the ONE statement of what is wrong with a prior: an entry point refuses it on the host with the fault's name (mix_fault_name), a per-fit
+// kernel meets it on the device (that row is marked dead).  A NaN fails every comparison.
+enum { MIX_OK = 0, MIX_BAD_N, MIX_BAD_PI, MIX_BAD_SIGMA, MIX_BAD_IV, MIX_BAD_MU };
+__host__ __device__ __forceinline__ int mix_prior_fault(const mfvi_mixture_prior& p)
+{
+    if (p.n < 1 || p.n > MFVI_MIXTURE_MAX) return MIX_BAD_N;
+    for (int j = 0; j < p.n; ++j) {
+        if (!(p.pi[j] > 0.f && p.pi[j] <= 3.40282347e38f)) return MIX_BAD_PI;
+        if (!(p.sigma[j] > 0.f && p.sigma[j] <= 3.40282347e38f)) return MIX_BAD_SIGMA;
+        const float iv = 1.f / (p.sigma[j] * p.sigma[j]);      // the factor of every squared distance: a normal float32
+        if (!(iv >= 1.17549435e-38f && iv <= 3.40282347e38f)) return MIX_BAD_IV;
+        if (!(p.mu[j] >= -3.40282347e38f && p.mu[j] <= 3.40282347e38f)) return MIX_BAD_MU;
+    }
+    return MIX_OK;
+}
+inline const char* mix_fault_name(int fault)
+{
+    static const char* const names[] = {nullptr, "prior->n outside 1..MFVI_MIXTURE_MAX", "a pi not finite or <= 0", "a sigma not finite or <= 0",
+                                        "a 1 / sigma^2 that is not a normal float32", "a component mean not finite"};
+    return names[fault];
+}
+// the key of the term's draw: RNG domain KLMC, stream 0; step_dev: the device-resident part of the counter word (key_now), or nullptr
+inline RngKey klmc_key(uint64_t seed, uint32_t sample, uint32_t step, const int32_t* step_dev)
+{
+    RngKey k; k.k0 = (uint32_t)seed; k.k1 = (uint32_t)(seed >> 32); k.stream = (uint32_t)DOMAIN_KLMC << 24; k.sample = sample; k.step = step; k.step_dev = step_dev;
+    return k;
+}
+// the per-component constants, formed once per block: c_j = log pi_j - log sigma_j, iv_j = 1 / sigma_j^2.  A component past the prior's n
+// has c = -inf and iv = 0: its a_j is -inf, its weight exp(a_j - max) and its share of G are exactly 0, so the loops over the compile-time
+// maximum need no branch on n.  That holds while (w - m_j)^2 is finite, |w| below ~1.8e19: beyond it inf * 0 is NaN, and where every real
+// component's a_j is -inf (a squared distance times iv that overflows) a_j - max is NaN too.  Both need parameters that have long
+// diverged; the NaN then shows in the term and the gradients as any overflow of the Gaussian kernels does.
+struct MixPrep { float c[MFVI_MIXTURE_MAX], m[MFVI_MIXTURE_MAX], iv[MFVI_MIXTURE_MAX]; };
+__device__ __forceinline__ MixPrep mix_prepare(const mfvi_mixture_prior& p)
+{
+#pragma clang fp contract(off)
+    MixPrep q;
+#pragma unroll
+    for (int j = 0; j < MFVI_MIXTURE_MAX; ++j) {
+        const bool on = j < p.n;
+        q.c[j] = on ? logf(p.pi[j]) - logf(p.sigma[j]) : -INFINITY;
+        q.m[j] = on ? p.mu[j] : 0.f;
+        q.iv[j] = on ? 1.f / (p.sigma[j] * p.sigma[j]) : 0.f;
+    }
+    return q;
+}
+// ONE (mu, rho, eps) triple: returns the term (the two 1/2 log 2 pi cancel), float32 pieces added in float64; gmu / grho = its two derivatives
+// with w = mu + s eps differentiated through (the reparametrised draw).  The mixture density goes through a log-sum-exp, so the term is
+// finite where the reference's log(sum pi_j exp(log_prob_j)) underflows to log 0; the responsibilities are r_j = e_j / sum e_j with
+// e_j = exp(a_j - max), the same numbers as exp(a_j - L) without a second round of exponentials.  d log q / d mu is identically 0 (the
+// reference's autograd forms it as eps / s - eps / s and keeps the rounding).  Every mixture kernel takes its arithmetic from here, every
+// operation rounded on its own, as kl_forward_terms.
+__device__ __forceinline__ double kl_mixture_terms(float mu, float r, float eps, const MixPrep& q, float& gmu, float& grho)
+{
+#pragma clang fp contract(off)
+    const float s = softplus_f(r), w = mu + s * eps;
+    float a[MFVI_MIXTURE_MAX], d[MFVI_MIXTURE_MAX], mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < MFVI_MIXTURE_MAX; ++j) {
+        d[j] = w - q.m[j];
+        a[j] = q.c[j] - (d[j] * d[j]) * (0.5f * q.iv[j]);
+        mx = fmaxf(mx, a[j]);
+    }
+    float se = 0.f, ge = 0.f;
+#pragma unroll
+    for (int j = 0; j < MFVI_MIXTURE_MAX; ++j) {
+        const float e = expf(a[j] - mx);
+        se = se + e;
+        ge = ge + e * (d[j] * q.iv[j]);
+    }
+    const float G = ge / se, L = mx + logf(se);
+    gmu = G;
+    grho = (G * eps - 1.f / s) * sigmoid_f(r);
+    return (double)(-0.5f * (eps * eps) - logf(s)) - (double)L;
+}
+
+// ---- elbo_update_share with the Monte-Carlo mixture term: the same Adam and BN loop; the (mu, rho) pairs go in quads, element i = lane
+// i & 3 of Philox block i >> 2 of the key's stream (RNG domain KLMC), so a weight's draw costs a quarter of a Philox block and no memory.
+// A quad's four pairs and gradients are requested before any is used, with clamped indices (no branch around a load); the stores and the
+// Adam of a lane past n_vi are predicated ----
+__device__ __forceinline__ double elbo_update_share_mix(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                        long long n_vi, long long n_bn, const MixPrep& prior, const RngKey& key, float temp, float b1,
+                                                        float b2, float eps, float step_size, float inv_sqrt_bc2, bool skip)
+{
+    auto adam = [&](long long i, float gi) {
+        const float mi = b1 * m[i] + (1.f - b1) * gi;
+        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        m[i] = mi; v[i] = vi;
+        p[i] = p[i] - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
+    };
+    double acc = 0;
+    const long long nq = (n_vi + 3) >> 2;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long long)gridDim.x * 256) {
+        float z[4], mu4[4], r4[4], gm4[4], gr4[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            const long long ic = 4 * q + l < n_vi ? 4 * q + l : n_vi - 1;
+            mu4[l] = p[ic]; r4[l] = p[n_vi + ic]; gm4[l] = g[ic]; gr4[l] = g[n_vi + ic];
+        }
+        spec_normal4(key, (uint32_t)q, z);
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            const long long i = 4 * q + l;
+            float dkm, dkr;
+            const double term = kl_mixture_terms(mu4[l], r4[l], z[l], prior, dkm, dkr);
+            if (i < n_vi) {
+                acc += term;
+                if (!skip) {
+                    const float gmu = gm4[l] + temp * dkm;
+                    const float grho = gr4[l] + temp * dkr;
+                    g[i] = gmu; g[n_vi + i] = grho;
+                    adam(i, gmu); adam(n_vi + i, grho);
+                }
+            }
+        }
     }
     if (!skip)
         for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_bn; i += (long long)gridDim.x * 256) adam(2 * n_vi + i, g[2 * n_vi + i]);

@@ -203,6 +203,42 @@ __global__ __launch_bounds__(256) void kl_fwd_bwd_kernel(const float* __restrict
     }
 }
 
+// the Monte-Carlo term against a scale-mixture prior (kl_mixture_terms, iter_ops.h) on n pairs that are elements i0 .. i0 + n - 1 of the
+// draw's stream: a thread takes the quads of Philox blocks i0 >> 2 .. (i0 + n - 1) >> 2, a lane outside the slice loads a clamped index and
+// adds / stores nothing.  EPS: the normals come from `eps` instead of the draw (a template argument: no run-time branch around the load).
+template <bool BWD, bool EPS>
+__global__ __launch_bounds__(256) void kl_mix_kernel(const float* __restrict__ mu, const float* __restrict__ rho, long long n, long long i0,
+                                                     mfvi_mixture_prior prior, const float* __restrict__ eps, RngKey key, float scale,
+                                                     float* __restrict__ dmu, float* __restrict__ drho, double* __restrict__ kl_out)
+{
+    __shared__ double s_red[8];
+    const MixPrep pr = mix_prepare(prior);
+    const long long q0 = i0 >> 2, nq = ((i0 + n - 1) >> 2) - q0 + 1;
+    double acc = 0;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long long)gridDim.x * 256) {
+        float z[4], mu4[4], r4[4];
+        long long j4[4];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            j4[l] = 4 * (q0 + q) + l - i0;
+            const long long jc = j4[l] < 0 ? 0 : (j4[l] < n ? j4[l] : n - 1);
+            mu4[l] = mu[jc]; r4[l] = rho[jc];
+            if (EPS) z[l] = eps[jc];
+        }
+        if (!EPS) spec_normal4(key, (uint32_t)(q0 + q), z);
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            float gmu, grho;
+            const double term = kl_mixture_terms(mu4[l], r4[l], z[l], pr, gmu, grho);
+            if (j4[l] >= 0 && j4[l] < n) {
+                if (BWD) { dmu[j4[l]] += scale * gmu; drho[j4[l]] += scale * grho; }
+                else acc += term;
+            }
+        }
+    }
+    if (!BWD) block_atomic_add(acc, kl_out, s_red);
+}
+
 // ---- AdamW -----------------------------------------------------------------------------------------
 // NaN guard of the CT runners (bayesian_optimization.py:380, 581-582, 792, 994: `if not torch.isnan(loss): optimizer.step()`) without a
 // host sync: the data-term scalar of this iteration is read on the device (double accumulator and / or the float that rode the
@@ -277,6 +313,22 @@ __global__ __launch_bounds__(256) void elbo_update_fwd_kernel(float* __restrict_
     const bool skip = guard_skip(guard);
     adam_bias(guard, lr, b1, b2, s_bc, step_size, inv_sqrt_bc2);
     const double acc = elbo_update_share_fwd(p, g, m, v, n_vi, n_bn, m0, s0, temp, b1, b2, eps, step_size, inv_sqrt_bc2, skip);
+    const double tot = block_sum_d(acc, s_red);
+    if (threadIdx.x == 0) sc->partial[blockIdx.x] = tot;
+}
+// elbo_update_kernel with the Monte-Carlo mixture term (elbo_update_share_mix): same partials, the finish kernel below; the draw's counter
+// word is resolved on the device (key_now)
+__global__ __launch_bounds__(256) void elbo_update_mix_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                              long long n_vi, long long n_bn, mfvi_mixture_prior prior, RngKey key, float temp, float b1,
+                                                              float b2, float eps, float step_size, float inv_sqrt_bc2, ElboUpdateScratch* __restrict__ sc,
+                                                              float lr, StepGuard guard)
+{
+    key = key_now(key);
+    __shared__ double s_red[8];
+    __shared__ float s_bc[2];
+    const bool skip = guard_skip(guard);
+    adam_bias(guard, lr, b1, b2, s_bc, step_size, inv_sqrt_bc2);
+    const double acc = elbo_update_share_mix(p, g, m, v, n_vi, n_bn, mix_prepare(prior), key, temp, b1, b2, eps, step_size, inv_sqrt_bc2, skip);
     const double tot = block_sum_d(acc, s_red);
     if (threadIdx.x == 0) sc->partial[blockIdx.x] = tot;
 }
@@ -740,6 +792,21 @@ const char* kl_type_refusal(int kl_type, float prior_sigma)
     return nullptr;
 }
 
+// what every *_mixture entry refuses of its prior before any launch -> nullptr, or what is wrong
+const char* mixture_refusal(const mfvi_mixture_prior* p)
+{
+    return p ? mix_fault_name(mix_prior_fault(*p)) : "null prior";      // (mix_prior_fault, iter_ops.h: the rule the per-fit kernel applies)
+}
+// the unfused pair's arguments; the Philox block index is a 32-bit word
+const char* kl_mixture_refusal(const float* mu, const float* rho, int64_t n, int64_t i0, const mfvi_mixture_prior* prior)
+{
+    if (const char* why = mixture_refusal(prior)) return why;
+    if (!mu || !rho || n < 1) return "null pointer or n < 1";
+    if (i0 < 0) return "i0 < 0";
+    if (n > ((int64_t)1 << 34) || i0 > ((int64_t)1 << 34) - n) return "i0 + n beyond the 2^34 elements of a stream";
+    return nullptr;
+}
+
 }  // namespace
 
 int launch_dropout_masks(const DropEntry* table_dev, int n_entries, RngKey key, int n_samples, float* arena, hipStream_t st, const float* fit_p, int fit_s,
@@ -877,6 +944,34 @@ int mfvi_kl_backward_typed(const float* mu, const float* rho, int64_t n, float p
     return (int)hipGetLastError();
 }
 
+int mfvi_kl_mixture(const float* mu, const float* rho, int64_t n, int64_t i0, const mfvi_mixture_prior* prior, const float* eps, uint64_t seed,
+                    uint32_t sample, uint32_t step, double* kl_out, void* stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const char* why = kl_mixture_refusal(mu, rho, n, i0, prior);
+    if (!why && !kl_out) why = "null pointer or n < 1";
+    if (why) { set_error("kl_mixture: %s", why); return -1; }
+    hipError_t e = hipMemsetAsync(kl_out, 0, sizeof(double), st); if (e) return (int)e;
+    const long long nq = ((i0 + n - 1) >> 2) - (i0 >> 2) + 1;
+    const auto kernel = eps ? kl_mix_kernel<false, true> : kl_mix_kernel<false, false>;
+    hipLaunchKernelGGL(kernel, dim3(nblocks(nq, 96)), dim3(256), 0, st, mu, rho, (long long)n, (long long)i0, *prior, eps, klmc_key(seed, sample, step, nullptr), 0.f,
+                       (float*)nullptr, (float*)nullptr, kl_out);
+    return (int)hipGetLastError();
+}
+
+int mfvi_kl_mixture_backward(const float* mu, const float* rho, int64_t n, int64_t i0, const mfvi_mixture_prior* prior, const float* eps, uint64_t seed,
+                             uint32_t sample, uint32_t step, float scale, float* dmu, float* drho, void* stream)
+{
+    const char* why = kl_mixture_refusal(mu, rho, n, i0, prior);
+    if (!why && (!dmu || !drho)) why = "null pointer or n < 1";
+    if (why) { set_error("kl_mixture_backward: %s", why); return -1; }
+    const long long nq = ((i0 + n - 1) >> 2) - (i0 >> 2) + 1;
+    const auto kernel = eps ? kl_mix_kernel<true, true> : kl_mix_kernel<true, false>;
+    hipLaunchKernelGGL(kernel, dim3(nblocks(nq)), dim3(256), 0, (hipStream_t)stream, mu, rho, (long long)n, (long long)i0, *prior, eps,
+                       klmc_key(seed, sample, step, nullptr), scale, dmu, drho, (double*)nullptr);
+    return (int)hipGetLastError();
+}
+
 int mfvi_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, int t,
                    void* stream)
 {
@@ -955,6 +1050,41 @@ int mfvi_elbo_update_guarded_typed(float* params, float* grads, float* m, float*
     const StepGuard guard{t_applied, loss_d, loss_f};
     hipLaunchKernelGGL(elbo_update_fwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, (long long)n_vi, (long long)n_bn,
                        prior_mu, prior_sigma, temp, beta1, beta2, eps, 0.f, 0.f, (ElboUpdateScratch*)scratch, lr, guard);
+    hipLaunchKernelGGL(elbo_update_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const ElboUpdateScratch*)scratch, nb, kl_out, t_applied, guard);
+    return (int)hipGetLastError();
+}
+
+int mfvi_elbo_update_mixture(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, const mfvi_mixture_prior* prior, float temp,
+                             float lr, float beta1, float beta2, float eps, int t, uint64_t seed, uint32_t sample, uint32_t step, const int32_t* step_dev,
+                             double* kl_out, void* scratch, void* stream)
+{
+    if (const char* why = mixture_refusal(prior)) { set_error("elbo_update_mixture: %s", why); return -1; }
+    if (!params || !grads || !m || !v || !kl_out || !scratch || n_vi < 0 || n_bn < 0 || t < 1 || n_vi > ((int64_t)1 << 34)) {
+        set_error("elbo_update_mixture: bad arguments (t is 1-based, scratch of mfvi_elbo_update_scratch_bytes() bytes)"); return -1; }
+    const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
+    const long long work = n_vi > n_bn ? n_vi : n_bn;      // the grid of mfvi_elbo_update (and of a row of mfvi_elbo_update_fits_mixture: the same partials)
+    const int nb = nblocks(work, ELBO_UPDATE_MAX_BLOCKS);
+    hipLaunchKernelGGL(elbo_update_mix_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, (long long)n_vi, (long long)n_bn, *prior,
+                       klmc_key(seed, sample, step, step_dev), temp, beta1, beta2, eps, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)),
+                       (ElboUpdateScratch*)scratch, lr, StepGuard{nullptr, nullptr, nullptr});
+    hipLaunchKernelGGL(elbo_update_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const ElboUpdateScratch*)scratch, nb, kl_out, (int*)nullptr,
+                       StepGuard{nullptr, nullptr, nullptr});
+    return (int)hipGetLastError();
+}
+
+int mfvi_elbo_update_guarded_mixture(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, const mfvi_mixture_prior* prior,
+                                     float temp, float lr, float beta1, float beta2, float eps, int32_t* t_applied, const double* loss_d,
+                                     const float* loss_f, uint64_t seed, uint32_t sample, uint32_t step, const int32_t* step_dev, double* kl_out,
+                                     void* scratch, void* stream)
+{
+    if (const char* why = mixture_refusal(prior)) { set_error("elbo_update_guarded_mixture: %s", why); return -1; }
+    if (!params || !grads || !m || !v || !kl_out || !scratch || !t_applied || n_vi < 0 || n_bn < 0 || n_vi > ((int64_t)1 << 34)) {
+        set_error("elbo_update_guarded_mixture: bad arguments (t_applied: device counter of applied updates)"); return -1; }
+    const long long work = n_vi > n_bn ? n_vi : n_bn;      // the grid of mfvi_elbo_update (and of a row of mfvi_elbo_update_fits_mixture: the same partials)
+    const int nb = nblocks(work, ELBO_UPDATE_MAX_BLOCKS);
+    const StepGuard guard{t_applied, loss_d, loss_f};
+    hipLaunchKernelGGL(elbo_update_mix_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, (long long)n_vi, (long long)n_bn, *prior,
+                       klmc_key(seed, sample, step, step_dev), temp, beta1, beta2, eps, 0.f, 0.f, (ElboUpdateScratch*)scratch, lr, guard);
     hipLaunchKernelGGL(elbo_update_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const ElboUpdateScratch*)scratch, nb, kl_out, t_applied, guard);
     return (int)hipGetLastError();
 }

@@ -13,7 +13,7 @@ as its data term, and one update launch over all D rows closes it (KL[d], Adam w
 owns the global eps samples d * K .. d * K + K - 1 and sample d of the INIT, z0 and perturbation streams whatever slices_per_launch is, so
 slice 0 is ElboEngine(S, S, task="ct", seed, K)."""
 from . import _lib as L
-from .rowbatch import MAX_LAUNCH, ElboRowBatch, check_kl_type, groups, per_fit      # (groups and MAX_LAUNCH re-exported: their home is rowbatch.py)
+from .rowbatch import MAX_LAUNCH, ElboRowBatch, check_kl_type, check_prior_mixtures, groups, per_fit      # (groups and MAX_LAUNCH re-exported: their home is rowbatch.py)
 
 
 def check_args(S, n_slices, slices_per_launch, K, temp, sigma, lr, theta_deg, init):
@@ -57,11 +57,12 @@ class CtVolume(ElboRowBatch):
     sinos = None
 
     def __init__(self, S, n_slices, slices_per_launch=None, K=1, input_depth=16, temp=1.0, sigma=0.1, lr=1e-3, theta_deg=None, seed=1,
-                 net_kwargs=None, init="per_fit", autotune=True, tv_weight=0.0, tv_beta=0.5, kl_type="reverse"):
+                 net_kwargs=None, init="per_fit", autotune=True, tv_weight=0.0, tv_beta=0.5, kl_type="reverse", prior_mixture=None):
         self.S, self.F, self.temps, self.sigmas, self.lrs, self.theta_list = check_args(S, n_slices, slices_per_launch, K, temp, sigma, lr,
                                                                                         theta_deg, init)
         self.D, self.T = int(n_slices), len(self.theta_list)
         self.kl_types = check_kl_type(kl_type, self.D)      # a name, or one per slice
+        self.prior_mixtures = check_prior_mixtures(prior_mixture, self.kl_types)      # None, one scale-mixture prior, or one per slice (None: a Gaussian slice)
         from .tv import check_tv
         self.tv_weights, self.tv_beta = check_tv(tv_weight, tv_beta, "ct", n=self.D)      # a scalar, or one weight per slice
         self.net_kwargs = dict(net_kwargs or {})

@@ -27,12 +27,27 @@ INP_NET = dict(nd=(16, 32, 64, 128, 128, 128), nu=(16, 32, 64, 128, 128, 128), n
 class ElboEngine:
     def __init__(self, H, W, task=TASK_DEN, K=1, input_depth=16, temp=1.0, sigma=0.1, lr=1e-3, seed=1, sr_factor=4,
                  theta_deg=None, rank=0, world_size=1, process_group=None, samples_per_launch=None, net_kwargs=None,
-                 autotune=True, param_dtype="f32", downsampler="nearest", tv_weight=0.0, tv_beta=0.5, kl_type="reverse"):
+                 autotune=True, param_dtype="f32", downsampler="nearest", tv_weight=0.0, tv_beta=0.5, kl_type="reverse", prior_mixture=None):
         # the direction of the KL term: 'reverse' = KL(prior || posterior), what the reference's runners use, 'forward' =
         # KL(posterior || prior), the textbook ELBO's; refused before anything touches the library
         from .rowbatch import KL_TYPES, check_kl_type
         self.kl_type = check_kl_type(kl_type)
         self._klt = KL_TYPES.index(self.kl_type)      # MFVI_KL_REVERSE / MFVI_KL_FORWARD, a by-value argument of every launch that forms the KL
+        # a scale-mixture prior {'pi', 'sigma', 'mu'} in place of the Gaussian one: the KL term becomes the reference's
+        # one-draw Monte-Carlo estimate of KL(posterior || mixture); temp still scales it, sigma no longer enters the prior
+        from .rowbatch import check_prior_mixture, mixture_struct
+        self.prior_mixture = check_prior_mixture(prior_mixture)
+        if self.prior_mixture is not None:
+            if self.kl_type == "reverse":
+                raise NotImplementedError("prior_mixture with kl_type='reverse' is not built: the reference's estimate of that direction takes its "
+                                          "\"sample\" from MixtureNormal.rsample (BayTorch/distributions/distributions.py:17-22), one scalar shared by all "
+                                          "weights that is no draw from the mixture; pass kl_type='forward'")
+            if param_dtype == "bf16":
+                raise NotImplementedError("prior_mixture with param_dtype='bf16': the bf16 update has no mixture term")
+            if type(self) is not ElboEngine:
+                raise TypeError("prior_mixture belongs to ElboEngine")
+            self._mix = mixture_struct(self.prior_mixture)      # host struct, copied into every launch that forms the term
+            self.kl_sample = 0                                   # the draw's sample word: a row of a batch draws with its index, one fit with 0
         # the total-variation term on the image channel of every sample; refused before anything touches the library
         from .tv import check_tv
         self.tv_weight, self.tv_beta = check_tv(tv_weight, tv_beta, task)
@@ -258,6 +273,7 @@ class ElboEngine:
         """Everything of one iteration except the optimizer update; returns nothing (grads, acc hold the result)."""
         lib, sp = L.lib(), L.stream_ptr()
         step = self.t if step is None else step
+        kl_step = step                         # the counter word of the mixture term's draw (with_kl)
         self._gbuf.zero_()                     # grads and acc
         exchange = self.world > 1 or getattr(self, "_force_exchange", False)
         zsrc = self.z0
@@ -296,6 +312,16 @@ class ElboEngine:
         if with_kl:
             # KL and its gradient are deterministic: every rank computes them redundantly (no communication)
             mu, rho = self.mu, self.rho
+            if self.prior_mixture is not None:      # the unfused pair with the draw of iteration `kl_step`, what step() fuses into the update
+                if self.step_dev is not None:
+                    raise NotImplementedError("grad_only(with_kl=True) with a mixture prior on the device-resident iteration: the unfused pair takes "
+                                              "the draw's counter word from the host, the iteration keeps it on the device; use step()")
+                import ctypes
+                mix = ctypes.byref(self._mix)
+                L.check(lib.mfvi_kl_mixture(L.ptr(mu), L.ptr(rho), self.n_vi, 0, mix, None, self.seed, self.kl_sample, kl_step, L.ptr(self.acc[1:]), sp))
+                L.check(lib.mfvi_kl_mixture_backward(L.ptr(mu), L.ptr(rho), self.n_vi, 0, mix, None, self.seed, self.kl_sample, kl_step, self.temp, L.ptr(self.dmu),
+                                                     L.ptr(self.drho), sp))
+                return
             if self.param_dtype == "bf16":      # the KL of the float32 values the bf16 parameters denote (step() fuses this into the update)
                 mu, rho = self.params_f32()[:2]
             kl, kt = self._kl_entry("mfvi_kl")
@@ -379,6 +405,10 @@ class ElboEngine:
         lib, sp = L.lib(), L.stream_ptr()
         self.grad_only(0, with_kl=False, after_forward=after_forward)
         guard = self._guard() if self.task == TASK_CT else (None, None)
+        if self.prior_mixture is not None:      # the draw's counter word is *step_dev, read on the device
+            self._update_mixture(guard, 0, L.ptr(self.step_dev))
+            self.step_dev.add_(1)
+            return
         update, kt = self._kl_entry("mfvi_elbo_update_guarded")
         L.check(update(L.ptr(self.params), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi, self.n_bn, 0.0, self.prior_sigma, self.temp, *kt,
                        self.lr, 0.9, 0.999, 1e-8, L.ptr(self.t_applied), *guard, L.ptr(self.acc[1:]), L.ptr(self.upd_scratch), sp))
@@ -424,6 +454,9 @@ class ElboEngine:
             return
         self.grad_only(self.t, with_kl=False, after_forward=after_forward)
         self.t += 1
+        if self.prior_mixture is not None:      # the draw of the iteration just run: counter word t - 1, as the perturbation's
+            self._update_mixture(self._guard() if self.task == TASK_CT else None, self.t - 1, None)
+            return
         if self.param_dtype == "bf16":
             update, kt = self._kl_entry("mfvi_elbo_update_bf16")
             L.check(update(L.ptr(self.mu), L.ptr(self.rho), L.ptr(self.bn), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi, self.n_bn, 0.0,
@@ -438,6 +471,19 @@ class ElboEngine:
         update, kt = self._kl_entry("mfvi_elbo_update")
         L.check(update(L.ptr(self.params), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi, self.n_bn, 0.0, self.prior_sigma, self.temp, *kt,
                        self.lr, 0.9, 0.999, 1e-8, self.t, L.ptr(self.acc[1:]), L.ptr(self.upd_scratch), sp))
+
+    def _update_mixture(self, guard, step, step_dev):
+        """The fused tail with the Monte-Carlo mixture term.  guard None: update number self.t from the host; else (loss_d, loss_f) of the NaN
+        guard and the device counter of applied updates."""
+        import ctypes
+        lib, sp = L.lib(), L.stream_ptr()
+        head = (L.ptr(self.params), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi, self.n_bn, ctypes.byref(self._mix), self.temp, self.lr, 0.9, 0.999,
+                1e-8)
+        tail = (self.seed, self.kl_sample, step, step_dev, L.ptr(self.acc[1:]), L.ptr(self.upd_scratch), sp)
+        if guard is None:
+            L.check(lib.mfvi_elbo_update_mixture(*head, self.t, *tail))
+        else:
+            L.check(lib.mfvi_elbo_update_guarded_mixture(*head, L.ptr(self.t_applied), *guard, *tail))
 
     def _kl_entry(self, name):
         """(entry point, its direction argument) of a launch that forms the KL: 'reverse' calls the entry itself, as before the direction
@@ -498,6 +544,8 @@ class SiblingEngine(ElboEngine):
         kw.pop("temp", None); kw.pop("sigma", None)
         if "kl_type" in kw:
             raise TypeError("SiblingEngine has no KL term: kl_type belongs to ElboEngine")
+        if "prior_mixture" in kw:
+            raise TypeError("SiblingEngine has no KL term: prior_mixture belongs to ElboEngine")
         super().__init__(H, W, task=task, temp=0.0, sigma=0.0, net_kwargs=nk, **kw)
         self.lr0 = self.lr                    # add_noise keeps using the initial rate (LR, not the scheduler's)
 

@@ -11,7 +11,7 @@ forward, data term, EMA on a second stream beside the backward pass, backward, t
 as its data term, whatever F is.  RNG identity: fit f owns the global samples f * K .. f * K + K - 1 of eps and sample f of the INIT, z0 and input
 perturbation domains, so fit 0 of a batch is the standalone ElboEngine(seed, K)."""
 from . import _lib as L
-from .rowbatch import EXP_WEIGHT, TASKS, ElboRowBatch, check_kl_type, per_fit, prior_sigmas      # (re-exported: the helpers' home is rowbatch.py)
+from .rowbatch import EXP_WEIGHT, TASKS, ElboRowBatch, check_kl_type, check_prior_mixtures, per_fit, prior_sigmas      # (re-exported: the helpers' home is rowbatch.py)
 
 
 def check_args(H, W, n_fits, task, K, temp, sigma, lr, init):
@@ -38,9 +38,10 @@ class FitBatch(ElboRowBatch):
     targets = None
 
     def __init__(self, H, W, n_fits, task="den", K=1, input_depth=16, temp=1.0, sigma=0.1, lr=1e-3, seed=1, sr_factor=4, net_kwargs=None,
-                 init="per_fit", autotune=True, tv_weight=0.0, tv_beta=0.5, kl_type="reverse"):
+                 init="per_fit", autotune=True, tv_weight=0.0, tv_beta=0.5, kl_type="reverse", prior_mixture=None):
         self.temps, self.sigmas, self.lrs = check_args(H, W, n_fits, task, K, temp, sigma, lr, init)
         self.kl_types = check_kl_type(kl_type, int(n_fits))      # a name, or one per fit: one batch can run both directions on one image
+        self.prior_mixtures = check_prior_mixtures(prior_mixture, self.kl_types)      # None, one scale-mixture prior, or one per fit (None: a Gaussian row)
         from .tv import check_tv
         self.tv_weights, self.tv_beta = check_tv(tv_weight, tv_beta, task, n=int(n_fits))      # a scalar, or one weight per fit
         if task == "sr" and (sr_factor < 1 or H % sr_factor or W % sr_factor):

@@ -11,7 +11,7 @@ for denoising and super-resolution; one iteration is the one-group iteration of 
 whatever F is.  The reference's images are 320 x 256: the two deepest maps (10 and 5 wide) are no multiple of 4 wide and run on the generic
 fp32 kernels, which fits mode serves with the fit's own mu / rho.  RNG identity as FitBatch: fit 0 is ElboEngine(task="inp", seed, K)."""
 from . import _lib as L
-from .rowbatch import EXP_WEIGHT, ElboRowBatch, check_kl_type, per_fit
+from .rowbatch import EXP_WEIGHT, ElboRowBatch, check_kl_type, check_prior_mixtures, per_fit
 
 
 def inp_net():
@@ -59,9 +59,10 @@ class InpaintBatch(ElboRowBatch):
     images = None; masks = None; _mask_stride = 0
 
     def __init__(self, H, W, n_fits, K=1, input_depth=32, temp=1.0, sigma=0.1, lr=2e-3, seed=1, net_kwargs=None, init="per_fit", autotune=True,
-                 kl_type="reverse"):
+                 kl_type="reverse", prior_mixture=None):
         self.temps, self.sigmas, self.lrs = check_args(H, W, n_fits, K, temp, sigma, lr, init, net_kwargs)
         self.kl_types = check_kl_type(kl_type, int(n_fits))      # a name, or one per fit
+        self.prior_mixtures = check_prior_mixtures(prior_mixture, self.kl_types)      # None, one scale-mixture prior, or one per fit (None: a Gaussian row)
         self.F = int(n_fits)
         self.net_kwargs = dict(net_kwargs or {})
         kw = inp_net(); kw.update(self.net_kwargs)

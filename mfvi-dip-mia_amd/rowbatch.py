@@ -52,6 +52,72 @@ def check_kl_type(kl_type, n=None, name="kl_type"):
     return names[0] if n is None else names
 
 
+MIXTURE_MAX = 4      # MFVI_MIXTURE_MAX
+
+
+def check_prior_mixture(prior_mixture, name="prior_mixture"):
+    """A scale-mixture prior sum_j pi_j N(m_j, sigma_j^2), refused without the library: {'pi': seq, 'sigma': seq,
+    'mu': seq or absent -> 0} with 1 to 4 components.  The sigma are prior scales as the reference's layers take them: 1e-6 is added and
+    the value rounded to float32 (BayTorch/modules/module.py:34); the pi are used as given, not normalised.  None -> None; else
+    dict(pi, mu, sigma: the given values as floats; scale: the final float32 scales), what mixture_struct packs for the C ABI."""
+    import numpy as np
+    if prior_mixture is None:
+        return None
+    if not isinstance(prior_mixture, dict) or "pi" not in prior_mixture or "sigma" not in prior_mixture or set(prior_mixture) - {"pi", "sigma", "mu"}:
+        raise ValueError("%s=%r: a dict with 'pi' and 'sigma' (and 'mu'), one sequence each" % (name, prior_mixture))
+
+    def seq(key, default=None):
+        v = prior_mixture.get(key, default)
+        try:
+            return [float(x) for x in np.asarray(v, dtype=np.float64).reshape(-1)] if np.ndim(v) == 1 else None
+        except (TypeError, ValueError):
+            return None
+    pi, sigma = seq("pi"), seq("sigma")
+    if pi is None or sigma is None or not 1 <= len(pi) <= MIXTURE_MAX:
+        raise ValueError("%s: 'pi' and 'sigma' are sequences of 1 to %d numbers, got %r" % (name, MIXTURE_MAX, prior_mixture))
+    mu = seq("mu", [0.0] * len(pi))
+    if mu is None or len(sigma) != len(pi) or len(mu) != len(pi):
+        raise ValueError("%s: %d pi, %d sigma and %s mu (one of each per component)" % (name, len(pi), len(sigma), "no" if mu is None else len(mu)))
+    scale = [float(np.float32(s + 1e-6)) for s in sigma]
+    with np.errstate(all="ignore"):
+        for j, (p, s, m) in enumerate(zip(pi, scale, mu)):
+            p32, m32, iv = np.float32(p), np.float32(m), np.float32(1.0) / (np.float32(s) * np.float32(s))
+            if not (np.isfinite(p32) and p32 > 0):
+                raise ValueError("%s: pi[%d]=%r is not a finite positive float32" % (name, j, p))
+            if not (np.isfinite(s) and s > 0):
+                raise ValueError("%s: sigma[%d]=%r + 1e-6 is not a finite positive float32" % (name, j, sigma[j]))
+            if not (np.isfinite(iv) and iv >= np.finfo(np.float32).tiny):
+                raise ValueError("%s: 1 / (sigma[%d] + 1e-6)^2 is not a normal float32 (sigma=%r)" % (name, j, sigma[j]))
+            if not np.isfinite(m32):
+                raise ValueError("%s: mu[%d]=%r is not a finite float32" % (name, j, m))
+    return dict(pi=pi, mu=mu, sigma=sigma, scale=scale)
+
+
+def check_prior_mixtures(prior_mixture, kl_types, name="prior_mixture"):
+    """Per row of a batch: None (no row has a mixture), one prior for every row, or a sequence with one prior or None (a Gaussian row) per
+    row -> the list of checked priors.  A row with a mixture runs the forward direction: 'reverse' is refused as ElboEngine refuses it."""
+    n = len(kl_types)
+    rows = [prior_mixture] * n if prior_mixture is None or isinstance(prior_mixture, dict) else list(prior_mixture)
+    if len(rows) != n:
+        raise ValueError("%s: %d values for %d fits (None, one prior, or one prior or None per fit)" % (name, len(rows), n))
+    rows = [check_prior_mixture(r, "%s[%d]" % (name, f)) for f, r in enumerate(rows)]
+    for f, r in enumerate(rows):
+        if r is not None and kl_types[f] == "reverse":
+            raise NotImplementedError("%s[%d] with kl_type='reverse' is not built: the reference's estimate of that direction samples through "
+                                      "MixtureNormal.rsample (BayTorch/distributions/distributions.py:17-22), no draw from the mixture; pass kl_type='forward'" % (name, f))
+    return rows
+
+
+def mixture_struct(pm):
+    """mfvi_mixture_prior of a checked prior (None: the n == 0 entry of a per-row table, a Gaussian row)."""
+    s = L.MixturePrior()
+    if pm is not None:
+        s.n = len(pm["pi"])
+        for j in range(s.n):
+            s.pi[j], s.mu[j], s.sigma[j] = pm["pi"][j], pm["mu"][j], pm["scale"][j]
+    return s
+
+
 def prior_sigmas(temps, sigmas):
     """Per fit, exactly as ElboEngine computes it (bayesian_optimization.py:1335-1336 + modules/module.py:38, rounded to fp32)."""
     import numpy as np
@@ -261,9 +327,13 @@ class RowBatch:
         return dict(tv_weight=self.tv_weights[f], tv_beta=self.tv_beta) if self.tv_weights is not None else {}
 
     def _kl_kw(self, f):
-        """The keyword that hands row f's direction of the KL term to its standalone engine (none where the class has no KL term)."""
-        kl = getattr(self, "kl_types", None)
-        return dict(kl_type=kl[f]) if kl is not None else {}
+        """The keywords that hand row f's direction of the KL term, and its scale-mixture prior if it has one, to its standalone engine (none
+        where the class has no KL term)."""
+        kl, pm = getattr(self, "kl_types", None), getattr(self, "prior_mixtures", None)
+        kw = dict(kl_type=kl[f]) if kl is not None else {}
+        if pm is not None and pm[f] is not None:
+            kw["prior_mixture"] = {k: pm[f][k] for k in ("pi", "sigma", "mu")}
+        return kw
 
     def recon(self):
         """clip(ema[:, 0], 0, 1) [n_rows, H, W]: the smoothed reconstruction of every row."""
@@ -314,6 +384,8 @@ class ElboRowBatch(RowBatch):
     """The mean-field VI layer: per-row temp / prior sigma / lr / direction of the KL term, the KL term and Adam in one launch over all rows.
     The subclass sets temps, sigmas, lrs (its check_args) and kl_types (check_kl_type) before _allocate."""
     kl_types = None             # per row 'reverse' or 'forward' (DESIGN.md section 25)
+    prior_mixtures = None       # per row a checked scale-mixture prior or None (DESIGN.md section 26)
+    _mix_dev = None             # mfvi_mixture_prior[n_rows] on the device once a row has a mixture; none has: nothing, and the update of before
     _kl_dev = None              # the directions on the device (int32 [n_rows]) once a row is forward; all reverse: nothing, and the untyped update
 
     def _alloc_own(self):
@@ -327,8 +399,20 @@ class ElboRowBatch(RowBatch):
             self.kl_types = ["reverse"] * R
         if any(k != "reverse" for k in self.kl_types):
             self._kl_dev = torch.tensor([KL_TYPES.index(k) for k in self.kl_types], dtype=torch.int32, device="cuda")
+        if self.prior_mixtures is None:
+            self.prior_mixtures = [None] * R
+        if any(pm is not None for pm in self.prior_mixtures):      # a Gaussian row is the n == 0 entry
+            table = b"".join(bytes(mixture_struct(pm)) for pm in self.prior_mixtures)
+            self._mix_dev = torch.frombuffer(bytearray(table), dtype=torch.uint8).cuda()
 
     def _update(self):
+        if self._mix_dev is not None:     # some row has a mixture prior: the same two launches, prior and direction read per row on the device;
+            # row r draws with sample r at counter word t - 1, the iteration just run (what its standalone engine draws with sample 0)
+            L.check(L.lib().mfvi_elbo_update_fits_mixture(L.ptr(self._pbuf), L.ptr(self._grows), L.ptr(self._mbuf), L.ptr(self._vbuf), self.n_vi, self.n_bn,
+                                                          self.stride, self.stride, self.n_rows, L.ptr(self.hyper), L.ptr(self._kl_dev), L.ptr(self._mix_dev),
+                                                          self.seed, 0, self.t - 1, None, 0.9, 0.999, 1e-8, self.t, L.ptr(self.nll_acc), L.ptr(self.dead_dev),
+                                                          L.ptr(self.kl), L.ptr(self.upd_scratch), L.stream_ptr()))
+            return
         if self._kl_dev is not None:      # some row is forward: the same two launches, the direction read per row on the device
             L.check(L.lib().mfvi_elbo_update_fits_typed(L.ptr(self._pbuf), L.ptr(self._grows), L.ptr(self._mbuf), L.ptr(self._vbuf), self.n_vi, self.n_bn,
                                                         self.stride, self.stride, self.n_rows, L.ptr(self.hyper), L.ptr(self._kl_dev), 0.9, 0.999, 1e-8, self.t,

@@ -92,14 +92,43 @@ def _tv_fields(tv_weight, tv_beta, task):
     return dict(tv_weight=w, tv_beta=b) if w > 0.0 else {}
 
 
-def _kl_fields(kl_type, method="mfvi"):
-    """The direction of the KL term of a single-fit run, refused before anything is written or loaded -> the keyword of
-    the engine and the extra locals.txt field: empty with the default 'reverse'."""
-    from .rowbatch import check_kl_type
+def _kl_fields(kl_type, method="mfvi", prior_mixture=None):
+    """The direction of the KL term of a single-fit run and its scale-mixture prior (section 26), refused before
+    anything is written or loaded -> the keywords of the engine and the extra locals.txt fields: empty with the default 'reverse' and no
+    mixture."""
+    from .rowbatch import check_kl_type, check_prior_mixture
     k = check_kl_type(kl_type)
     if k != "reverse" and method != "mfvi":
         raise ValueError("kl_type=%r: the direction of the KL term belongs to mean-field VI (mfvi); %r has no KL term" % (k, method))
-    return dict(kl_type=k) if k != "reverse" else {}
+    out = dict(kl_type=k) if k != "reverse" else {}
+    pm = check_prior_mixture(prior_mixture)
+    if pm is not None:
+        if method != "mfvi":
+            raise ValueError("prior_mixture: the prior belongs to mean-field VI (mfvi); %r has no KL term" % (method,))
+        out["prior_mixture"] = {key: pm[key] for key in ("pi", "sigma", "mu")}      # (with kl_type 'reverse' the engine refuses it)
+    return out
+
+
+def parse_prior_mixture(text):
+    """--prior-mixture PI:SIGMA[:MU],PI:SIGMA[:MU],... -> {'pi': [...], 'sigma': [...], 'mu': [...]} (ValueError on anything else)."""
+    pi, sigma, mu = [], [], []
+    for part in text.split(","):
+        f = part.split(":")
+        if len(f) not in (2, 3):
+            raise ValueError("component %r: PI:SIGMA or PI:SIGMA:MU" % part)
+        pi.append(float(f[0])); sigma.append(float(f[1])); mu.append(float(f[2]) if len(f) == 3 else 0.0)
+    return dict(pi=pi, sigma=sigma, mu=mu)
+
+
+def _mix_keys(batch):
+    """What batch.npz / volume.npz record of the rows' scale-mixture priors, and only when some row has one: per row the number of components
+    (0: a Gaussian row) and pi, sigma (as given), mu padded with zeros to four."""
+    pms = getattr(batch, "prior_mixtures", None) or ()
+    if not any(p is not None for p in pms):
+        return {}
+    pad = lambda p, k: (list(p[k]) + [0.0] * 4)[:4] if p is not None else [0.0] * 4
+    return dict(prior_mixture_n=np.asarray([0 if p is None else len(p["pi"]) for p in pms], np.int64),
+                **{"prior_mixture_" + k: np.asarray([pad(p, k) for p in pms], np.float64) for k in ("pi", "sigma", "mu")})
 
 
 def _check_predict(method, predict_samples):
@@ -238,14 +267,14 @@ def _fit(task, method, fields, prepare, num_iter, show_every, plot, save, save_p
 
 def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, seed, show_every, plot, save, save_path, K, factor=4,
          theta_step=4.0, verbose=False, net_kwargs=None, method="mfvi", weight_decay=0.0, dropout_p=0.3, gamma=0.996, param_dtype="f32", predict_samples=0,
-         calibration=False, calibration_bins=15, downsampler="nearest", tv_weight=0.0, tv_beta=0.5, kl_type="reverse", **unused):
+         calibration=False, calibration_bins=15, downsampler="nearest", tv_weight=0.0, tv_beta=0.5, kl_type="reverse", prior_mixture=None, **unused):
     """What _fit needs of a den / sr / ct run: its locals.txt fields and, once the run directory stands, the image, the task's target and engine,
     the _Book and the two head arrays as the reference writes them per task: den img_gt / img_noisy (:1438), sr img_hr / img_lr (:2258), ct
     img_gt / img_radon (:643) with the reference's shapes (get_image() arrays are (1, H, W), img_lr is squeezed, the CT tensors keep
     (1, 1, ., .))."""
     sib = dict(weight_decay=weight_decay, dropout_p=dropout_p, gamma=gamma)
     tv = _tv_fields(tv_weight, tv_beta, task)      # tv_weight * mean_k TV_beta(out_k[0]) joins the objective (all four methods); off: nothing changes
-    tv.update(_kl_fields(kl_type, method))         # kl_type='forward' (mfvi): KL(posterior || prior) in the objective; 'reverse': nothing changes
+    tv.update(_kl_fields(kl_type, method, prior_mixture))      # kl_type='forward' (mfvi): KL(posterior || prior) in the objective, against prior_mixture if given; 'reverse': nothing changes
     hyper = dict(temp=temp, sigma=sigma) if method == "mfvi" else {"dip": {}, "mcd": dict(dropout_p=dropout_p, weight_decay=weight_decay),
                                                                   "sgld": dict(gamma=gamma, weight_decay=weight_decay)}.get(method, {})
     fields = dict(task=task, method=method, img=img if not isinstance(img, np.ndarray) else "<array>", imsize=imsize, p_sigma=p_sigma,
@@ -351,13 +380,13 @@ def scratch_mask(H, W, seed):
 
 def run_inp_mfvi(img="phantom", mask=None, imsize=(256, 256), num_iter=5000, lr=2e-3, temp=4e-6, sigma=0.01, input_depth=32, seed=42,
                  show_every=100, plot=False, save=True, save_path="../logs", K=1, net_kwargs=None, verbose=False, method="mfvi",
-                 weight_decay=1e-4, dropout_p=0.2, gamma=0.996, predict_samples=0, calibration=False, calibration_bins=15, kl_type="reverse", **unused):
+                 weight_decay=1e-4, dropout_p=0.2, gamma=0.996, predict_samples=0, calibration=False, calibration_bins=15, kl_type="reverse", prior_mixture=None, **unused):
     """bayesian_optimization.py:2892-3114: inpainting with the 6-scale no-skip net (5x5 down filters, nearest up-sampling), sigmoid on
     the colour channels, masked Gaussian NLL.  img: (3, H, W) array in [0, 1] or 'phantom' (three synthetic planes); mask: (1|3, H, W),
     1 = known pixel (the reference ships its masks in data/inpainting/).  save.npz carries the reference's keys for this task
     (img_inpainting, img_mask, mse_corrupted, mse_gt, recons, uncerts, uncerts_ale, psnrs, ssims)."""
     _tv_fields(unused.get("tv_weight", 0.0), unused.get("tv_beta", 0.5), "inp")      # refused with a weight > 0: the term is not built for inpainting
-    kl = _kl_fields(kl_type, method)
+    kl = _kl_fields(kl_type, method, prior_mixture)
     fields = dict(task="inp", imsize=imsize, num_iter=num_iter, lr=lr, temp=temp, sigma=sigma, input_depth=input_depth, seed=seed,
                   show_every=show_every, K=K, save_path=save_path, **kl)
 
@@ -456,7 +485,8 @@ def _drive_batch(batch, gt, kind, keys, num_iter, show_every, save, save_path, v
         np.savez(os.path.join(run_dir, kind + ".npz"), K=np.int64(batch.K), seed=np.int64(batch.seed), num_iter=np.int64(num_iter), iterations=np.asarray(at),
                  psnr_gt_sm=np.stack(psnrs), recon=batch.recon().cpu().numpy(), dead=dead, **keys(losses),
                  **(dict(tv_weight=np.asarray(batch.tv_weights), tv_beta=np.float64(batch.tv_beta), tv=np.stack(tvs)) if tv_on else {}),
-                 **(dict(kl_type=np.asarray(batch.kl_types)) if kl_on else {}))      # fixed-width strings, one per row
+                 **(dict(kl_type=np.asarray(batch.kl_types)) if kl_on else {}),      # fixed-width strings, one per row
+                 **_mix_keys(batch))                                                # the rows' scale-mixture priors, when a row has one (section 26)
         if book is not None:
             _save_bookkeeping(book, run_dir, heads)
     pred = _batch_predict(batch, batch_predict_samples, gt, run_dir, batch_calibration_bins) if batch_predict_samples else None
@@ -484,7 +514,7 @@ def _den_sr_batch(task, jobs, imsize, seed, p_sigma, factor):
 
 def run_fit_batch(task, jobs, imsize=(256, 256), p_sigma=0.1, num_iter=5000, lr=3e-4, input_depth=16, seed=42, show_every=100, save=True,
                   save_path="../logs", K=1, factor=4, net_kwargs=None, verbose=False, autotune=True, batch_predict_samples=0,
-                  batch_calibration_bins=0, batch_bookkeeping=False, tv_weight=0.0, tv_beta=0.5, kl_type="reverse", **unused):
+                  batch_calibration_bins=0, batch_bookkeeping=False, tv_weight=0.0, tv_beta=0.5, kl_type="reverse", prior_mixture=None, **unused):
     """The (image, temp, sigma) jobs of one batch as ONE FitBatch (--fits-per-launch): the loop of run_den_mfvi /
     run_sr_mfvi for every job at once, every fit with the noise of its own RNG samples.  jobs: dicts with img, temp, sigma (and optionally
     lr, tv_weight and kl_type; tv_weight / tv_beta: the run-wide total-variation term, DESIGN.md section 23 -- with a weight > 0 batch.npz also
@@ -506,7 +536,8 @@ def run_fit_batch(task, jobs, imsize=(256, 256), p_sigma=0.1, num_iter=5000, lr=
     temps, sigmas, lrs = [j["temp"] for j in jobs], [j["sigma"] for j in jobs], [j.get("lr", lr) for j in jobs]
     fb = FitBatch(gt.shape[1], gt.shape[2], len(jobs), task=task, K=K, input_depth=input_depth, temp=temps, sigma=sigmas, lr=lrs, seed=seed, sr_factor=factor,
                   net_kwargs=net_kwargs, init="shared", autotune=autotune,      # the reference's candidates all start from one seed
-                  tv_weight=[j.get("tv_weight", tv_weight) for j in jobs], tv_beta=tv_beta, kl_type=[j.get("kl_type", kl_type) for j in jobs])
+                  tv_weight=[j.get("tv_weight", tv_weight) for j in jobs], tv_beta=tv_beta, kl_type=[j.get("kl_type", kl_type) for j in jobs],
+                  prior_mixture=[j.get("prior_mixture", prior_mixture) for j in jobs])      # a job's scale-mixture prior (absent: the run's; None: Gaussian)
     fb.set_targets(torch.from_numpy(targets))
     keys = lambda losses: dict(task=task, temp=np.asarray(temps), sigma=np.asarray(sigmas), lr=np.asarray(lrs), prior_sigma=np.asarray(fb.prior_sigma),
                                **_nll_kl(losses))
@@ -520,7 +551,7 @@ def fit_batch_job(task, jobs, **kw):
 
 
 def run_inpaint_batch(jobs, imsize=(256, 256), num_iter=5000, lr=2e-3, input_depth=32, seed=42, show_every=100, save=True, save_path="../logs",
-                      K=1, net_kwargs=None, verbose=False, autotune=True, mask=None, batch_predict_samples=0, batch_calibration_bins=0, kl_type="reverse",
+                      K=1, net_kwargs=None, verbose=False, autotune=True, mask=None, batch_predict_samples=0, batch_calibration_bins=0, kl_type="reverse", prior_mixture=None,
                       **unused):
     """The (image, mask, temp, sigma) jobs of one batch as ONE InpaintBatch (--inpaint-fits): the loop of run_inp_mfvi for
     every job at once.  jobs: dicts with img ((3, H, W) array, or what run_inp_mfvi loads), temp, sigma and optionally mask ((1|3, H, W);
@@ -548,7 +579,8 @@ def run_inpaint_batch(jobs, imsize=(256, 256), num_iter=5000, lr=2e-3, input_dep
     gt = np.stack(imgs)
     temps, sigmas, lrs = [j["temp"] for j in jobs], [j["sigma"] for j in jobs], [j.get("lr", lr) for j in jobs]
     ib = InpaintBatch(H, W, len(jobs), K=K, input_depth=input_depth, temp=temps, sigma=sigmas, lr=lrs, seed=seed, net_kwargs=net_kwargs, init="shared",
-                      autotune=autotune, kl_type=[j.get("kl_type", kl_type) for j in jobs])                               # the reference's candidates all start from one seed
+                      autotune=autotune, kl_type=[j.get("kl_type", kl_type) for j in jobs],                               # the reference's candidates all start from one seed
+                      prior_mixture=[j.get("prior_mixture", prior_mixture) for j in jobs])
     ib.set_targets(torch.from_numpy(gt), torch.from_numpy(np.stack(masks)))
     keys = lambda losses: dict(task="inp", temp=np.asarray(temps), sigma=np.asarray(sigmas), lr=np.asarray(lrs), prior_sigma=np.asarray(ib.prior_sigma),
                                **_nll_kl(losses), mask=ib.masks.cpu().numpy(), ale=ib.ale().cpu().numpy())
@@ -673,7 +705,7 @@ def _load_volume(volume, imsize, seed):
 
 def run_ct_volume(volume, temp, sigma, slices_per_launch=None, imsize=(256, 256), num_iter=5000, lr=3e-4, input_depth=16, seed=42, show_every=100,
                   save=True, save_path="../logs", K=1, theta_step=4.0, net_kwargs=None, verbose=False, autotune=True, batch_predict_samples=0,
-                  batch_calibration_bins=0, batch_bookkeeping=False, tv_weight=0.0, tv_beta=0.5, kl_type="reverse", **unused):
+                  batch_calibration_bins=0, batch_bookkeeping=False, tv_weight=0.0, tv_beta=0.5, kl_type="reverse", prior_mixture=None, **unused):
     """The loop of run_ct_mfvi (bayesian_optimization.py:442-648) for every slice of a stack at once, as ONE CtVolume (--ct-volume; DESIGN.md
     section 16).  volume: [D, S, S] array, .npy path or 'phantom:D'; temp / sigma / lr / tv_weight: scalars or one value per slice
     (tv_weight > 0: volume.npz also holds tv_weight, tv_beta and tv); kl_type: a name or one per slice (a forward slice:
@@ -687,7 +719,8 @@ def run_ct_volume(volume, temp, sigma, slices_per_launch=None, imsize=(256, 256)
     gt = _load_volume(volume, imsize, seed)
     theta = np.arange(0, 180.0, theta_step, dtype=np.float32)         # :545
     vol = CtVolume(gt.shape[1], gt.shape[0], slices_per_launch=slices_per_launch, K=K, input_depth=input_depth, temp=temp, sigma=sigma, lr=lr,
-                   theta_deg=theta.tolist(), seed=seed, net_kwargs=net_kwargs, autotune=autotune, tv_weight=tv_weight, tv_beta=tv_beta, kl_type=kl_type)
+                   theta_deg=theta.tolist(), seed=seed, net_kwargs=net_kwargs, autotune=autotune, tv_weight=tv_weight, tv_beta=tv_beta, kl_type=kl_type,
+                   prior_mixture=prior_mixture)      # one scale-mixture prior, or one (or None) per slice
     vol.set_volume(torch.from_numpy(gt))                              # img_radon = forward_radon(img_torch) (:547)
     sinos = vol.sinos.cpu().numpy()
     keys = lambda losses: dict(theta=theta, sinograms=sinos, temp=np.asarray(vol.temps), sigma=np.asarray(vol.sigmas), lr=np.asarray(vol.lrs),
@@ -708,7 +741,7 @@ def _check_cli(ap, a):
     """What main() refuses from the parsed arguments alone, before the config is read and before anything loads the library.  The order is
     behaviour (the first refusal that applies is the one reported; tests/golden/cli_refusals.json): --sr-downsampler, --batch-bookkeeping,
     --batch-predict-samples / --batch-calibration, then --sibling-fits, --inpaint-fits, --ct-volume and --fits-per-launch each ahead of the
-    batching flags after it, then --calibration and --predict-samples of a single fit, then --tv-weight / --tv-beta, then --kl-type."""
+    batching flags after it, then --calibration and --predict-samples of a single fit, then --tv-weight / --tv-beta, then --kl-type, then --prior-mixture."""
     on = {"--fits-per-launch": a.fits_per_launch, "--inpaint-fits": a.inpaint_fits, "--sibling-fits": a.sibling_fits, "--ct-volume": a.ct_volume is not None,
           "--predict-samples": a.predict_samples, "--calibration": a.calibration, "--bo-rounds": a.bo_rounds}
 
@@ -797,6 +830,14 @@ def _check_cli(ap, a):
         ap.error("--tv-weight %g does not combine with --task inpainting (the total-variation term serves denoising, super-resolution and ct)" % a.tv_weight)
     if a.kl_type == "forward" and a.bayes != "mfvi":
         ap.error("--kl-type forward chooses the direction of mean-field VI's KL term (--bayes mfvi); %s has no KL term" % a.bayes)
+    if a.prior_mixture is not None:
+        if a.bayes != "mfvi":
+            ap.error("--prior-mixture is the prior of mean-field VI's KL term (--bayes mfvi); %s has no KL term" % a.bayes)
+        from .rowbatch import check_prior_mixture
+        try:
+            check_prior_mixture(parse_prior_mixture(a.prior_mixture), "--prior-mixture")
+        except ValueError as e:
+            ap.error("--prior-mixture %s: %s" % (a.prior_mixture, e))
 
 
 def main(argv=None):
@@ -852,6 +893,10 @@ def main(argv=None):
     ap.add_argument("--kl-type", default=None, choices=["reverse", "forward"],
                     help="--bayes mfvi: the direction of the KL term; reverse = KL(prior || posterior), what the reference's runners use "
                          "(default, or the config's run_params.kl_type), forward = KL(posterior || prior), the textbook ELBO's")
+    ap.add_argument("--prior-mixture", default=None, metavar="PI:SIGMA[:MU],...",
+                    help="--bayes mfvi with --kl-type forward: a scale mixture of 1 to 4 Gaussians as the prior of every weight, one PI:SIGMA[:MU] "
+                         "per component (1e-6 is added to SIGMA; MU defaults to 0); the KL term becomes the one-draw Monte-Carlo estimate of "
+                         "KL(posterior || mixture) (default: the config's run_params.prior_mixture, else the Gaussian prior)")
     a = ap.parse_args(argv)
     _check_cli(ap, a)
     cands, rp, cfg_devices = load_config(a.config, a.bayes, with_devices=True)
@@ -889,6 +934,8 @@ def main(argv=None):
         rp["tv_beta"] = a.tv_beta
     if a.kl_type is not None:
         rp["kl_type"] = a.kl_type
+    if a.prior_mixture is not None:
+        rp["prior_mixture"] = parse_prior_mixture(a.prior_mixture)
     if a.ct_volume is not None:      # one volume fit per candidate of the config
         from .fanout import print_table
         vrp = {k: v for k, v in rp.items() if k not in ("img", "plot", "p_sigma")}
