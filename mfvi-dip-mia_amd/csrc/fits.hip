@@ -9,9 +9,6 @@
 
 namespace {
 
-constexpr int UPDATE_MAX_BLOCKS = 2048;      // as mfvi_elbo_update: the same blocks per fit, so the same KL partial sums in the same order
-inline int nblocks(long long n, int cap = 2048) { long long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > cap ? cap : b)); }
-
 __global__ __launch_bounds__(256) void perturb_fits_kernel(RngKey key, long long n, float std, const float* __restrict__ z0, float* __restrict__ z)
 {
     key.sample += blockIdx.y;      // fit f: sample fit0 + f of RNG domain INPUT
@@ -33,119 +30,63 @@ __global__ __launch_bounds__(256) void gaussian_nll_fits_kernel(const float* __r
     block_atomic_add(v, nll + fit, s_red);
 }
 
+// ---- KL + AdamW of every fit: one kernel pair in three instantiations, so that a batch pays only for what its rows use.
+//   <TYPED, MIX> = <0, 0>  every row reverse against its Gaussian prior (mfvi_elbo_update_fits)
+//                  <1, 0>  the direction of every row's term from kl_type, read once per block: block-uniform, no branch inside the element loop
+//                  <1, 1>  and every row's prior table entry: n == 0 runs the Gaussian prior in the row's direction as <1, 0>; n in
+//                          1..MFVI_MIXTURE_MAX the Monte-Carlo mixture term with sample sample0 + fit of the draw's stream (kl_type may be NULL: reverse)
+// What row `fit` runs -> false for a direction or an entry the single-fit entries would refuse, which can only be met here: the fit's blocks
+// write nothing and its finish block marks it dead.
+template <bool TYPED, bool MIX>
+__device__ __forceinline__ bool fit_row(const int32_t* __restrict__ kl_type, const mfvi_mixture_prior* __restrict__ mix_tab, int fit, int& kt, mfvi_mixture_prior& mix)
+{
+    kt = TYPED && kl_type ? kl_type[fit] : MFVI_KL_REVERSE;
+    if (MIX) mix = mix_tab[fit]; else mix.n = 0;
+    return mix.n == 0 ? (kt == MFVI_KL_REVERSE || kt == MFVI_KL_FORWARD) : mix_prior_fault(mix) == MIX_OK;
+}
+template <bool TYPED, bool MIX>
 __global__ __launch_bounds__(256) void elbo_update_fits_kernel(float* __restrict__ params, float* __restrict__ grads, float* __restrict__ m, float* __restrict__ v,
                                                                long long n_vi, long long n_bn, long long param_stride, long long grad_stride,
-                                                               const mfvi_fit_hyper* __restrict__ hyper, float b1, float b2, float eps, double bc1,
-                                                               float inv_sqrt_bc2, const double* __restrict__ nll, const int32_t* __restrict__ dead,
-                                                               double* __restrict__ partial)
+                                                               const mfvi_fit_hyper* __restrict__ hyper, const int32_t* __restrict__ kl_type,
+                                                               const mfvi_mixture_prior* __restrict__ mix_tab, RngKey key, float b1, float b2, float eps,
+                                                               double bc1, float inv_sqrt_bc2, const double* __restrict__ nll,
+                                                               const int32_t* __restrict__ dead, double* __restrict__ partial)
 {
     __shared__ double s_red[8];
     const int fit = blockIdx.y;
+    int kt; mfvi_mixture_prior mix;
+    if (!fit_row<TYPED, MIX>(kl_type, mix_tab, fit, kt, mix)) return;
     const mfvi_fit_hyper h = hyper[fit];
     // a fit whose data term is not finite (or that died earlier) keeps parameters and moments; its KL is still reported
     const bool skip = dead[fit] != 0 || !isfinite(nll[fit]);
-    const float step_size = (float)((double)h.lr / bc1);
     const long long po = (long long)fit * param_stride;
-    const double acc = elbo_update_share(params + po, grads + (long long)fit * grad_stride, m + po, v + po, n_vi, n_bn, h.prior_mu, h.prior_sigma, h.temp,
-                                         b1, b2, eps, step_size, inv_sqrt_bc2, skip);
+    const AdamStep adam{params + po, m + po, v + po, b1, b2, eps, (float)((double)h.lr / bc1), inv_sqrt_bc2};
+    float* __restrict__ g = grads + (long long)fit * grad_stride;
+    const GaussPrior prior{h.prior_mu, h.prior_sigma};
+    double acc;
+    if (MIX && mix.n != 0) {
+        key = key_now(key);
+        key.sample += (uint32_t)fit;
+        acc = elbo_update_share_quads(KlMixture(mix, key), g, n_vi, n_bn, h.temp, adam, skip);
+    } else if (TYPED && kt == MFVI_KL_FORWARD)
+        acc = elbo_update_share(KlForward(prior), g, n_vi, n_bn, h.temp, adam, skip);
+    else
+        acc = elbo_update_share(KlReverse(prior), g, n_vi, n_bn, h.temp, adam, skip);
     const double tot = block_sum_d(acc, s_red);
-    if (threadIdx.x == 0) partial[(long long)fit * UPDATE_MAX_BLOCKS + blockIdx.x] = tot;
+    if (threadIdx.x == 0) partial[(long long)fit * ELBO_UPDATE_MAX_BLOCKS + blockIdx.x] = tot;
 }
 // one block per fit: its partials in block order (the order of elbo_update_finish_kernel), and the sticky dead flag
+template <bool TYPED, bool MIX>
 __global__ __launch_bounds__(256) void elbo_update_fits_finish_kernel(const double* __restrict__ partial, int n_blocks, const double* __restrict__ nll,
+                                                                      const int32_t* __restrict__ kl_type, const mfvi_mixture_prior* __restrict__ mix_tab,
                                                                       int32_t* __restrict__ dead, double* __restrict__ kl_out)
 {
     __shared__ double s_red[8];
     const int fit = blockIdx.x;
+    int kt; mfvi_mixture_prior mix;
+    if (!fit_row<TYPED, MIX>(kl_type, mix_tab, fit, kt, mix)) { if (threadIdx.x == 0) dead[fit] = 1; return; }
     double t = 0;
-    for (int b = threadIdx.x; b < n_blocks; b += 256) t += partial[(long long)fit * UPDATE_MAX_BLOCKS + b];
-    t = block_sum_d(t, s_red);
-    if (threadIdx.x == 0) { kl_out[fit] = t; if (!isfinite(nll[fit])) dead[fit] = 1; }
-}
-
-// the two kernels above with the direction of every fit's KL term, read once per block (block-uniform: no branch inside the element loop).  A
-// direction outside {MFVI_KL_REVERSE, MFVI_KL_FORWARD} can only be met here: the fit's blocks write nothing and its finish block marks it dead.
-__global__ __launch_bounds__(256) void elbo_update_fits_typed_kernel(float* __restrict__ params, float* __restrict__ grads, float* __restrict__ m, float* __restrict__ v,
-                                                                     long long n_vi, long long n_bn, long long param_stride, long long grad_stride,
-                                                                     const mfvi_fit_hyper* __restrict__ hyper, const int32_t* __restrict__ kl_type, float b1, float b2,
-                                                                     float eps, double bc1, float inv_sqrt_bc2, const double* __restrict__ nll,
-                                                                     const int32_t* __restrict__ dead, double* __restrict__ partial)
-{
-    __shared__ double s_red[8];
-    const int fit = blockIdx.y;
-    const int kt = kl_type[fit];
-    if (kt != MFVI_KL_REVERSE && kt != MFVI_KL_FORWARD) return;
-    const mfvi_fit_hyper h = hyper[fit];
-    const bool skip = dead[fit] != 0 || !isfinite(nll[fit]);
-    const float step_size = (float)((double)h.lr / bc1);
-    const long long po = (long long)fit * param_stride;
-    float* __restrict__ g = grads + (long long)fit * grad_stride;
-    const double acc = kt == MFVI_KL_FORWARD
-        ? elbo_update_share_fwd(params + po, g, m + po, v + po, n_vi, n_bn, h.prior_mu, h.prior_sigma, h.temp, b1, b2, eps, step_size, inv_sqrt_bc2, skip)
-        : elbo_update_share(params + po, g, m + po, v + po, n_vi, n_bn, h.prior_mu, h.prior_sigma, h.temp, b1, b2, eps, step_size, inv_sqrt_bc2, skip);
-    const double tot = block_sum_d(acc, s_red);
-    if (threadIdx.x == 0) partial[(long long)fit * UPDATE_MAX_BLOCKS + blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(256) void elbo_update_fits_typed_finish_kernel(const double* __restrict__ partial, int n_blocks, const double* __restrict__ nll,
-                                                                            const int32_t* __restrict__ kl_type, int32_t* __restrict__ dead,
-                                                                            double* __restrict__ kl_out)
-{
-    __shared__ double s_red[8];
-    const int fit = blockIdx.x;
-    const int kt = kl_type[fit];
-    if (kt != MFVI_KL_REVERSE && kt != MFVI_KL_FORWARD) { if (threadIdx.x == 0) dead[fit] = 1; return; }
-    double t = 0;
-    for (int b = threadIdx.x; b < n_blocks; b += 256) t += partial[(long long)fit * UPDATE_MAX_BLOCKS + b];
-    t = block_sum_d(t, s_red);
-    if (threadIdx.x == 0) { kl_out[fit] = t; if (!isfinite(nll[fit])) dead[fit] = 1; }
-}
-
-// the typed pair with every fit's prior table entry, read once per block: n == 0 runs the Gaussian prior in the fit's direction, as above;
-// n in 1..MFVI_MIXTURE_MAX the Monte-Carlo mixture term with sample sample0 + fit of the draw's stream.  An entry the host entries would
-// refuse can only be met here: the fit's blocks write nothing and its finish block marks it dead.
-__device__ __forceinline__ bool fit_row_runs(const mfvi_mixture_prior& mix, int kt)
-{
-    return mix.n == 0 ? (kt == MFVI_KL_REVERSE || kt == MFVI_KL_FORWARD) : mix_prior_fault(mix) == MIX_OK;
-}
-__global__ __launch_bounds__(256) void elbo_update_fits_mix_kernel(float* __restrict__ params, float* __restrict__ grads, float* __restrict__ m, float* __restrict__ v,
-                                                                   long long n_vi, long long n_bn, long long param_stride, long long grad_stride,
-                                                                   const mfvi_fit_hyper* __restrict__ hyper, const int32_t* __restrict__ kl_type,
-                                                                   const mfvi_mixture_prior* __restrict__ mix_tab, RngKey key, float b1, float b2, float eps,
-                                                                   double bc1, float inv_sqrt_bc2, const double* __restrict__ nll,
-                                                                   const int32_t* __restrict__ dead, double* __restrict__ partial)
-{
-    __shared__ double s_red[8];
-    key = key_now(key);
-    const int fit = blockIdx.y;
-    const int kt = kl_type ? kl_type[fit] : MFVI_KL_REVERSE;
-    const mfvi_mixture_prior mix = mix_tab[fit];
-    if (!fit_row_runs(mix, kt)) return;
-    const mfvi_fit_hyper h = hyper[fit];
-    const bool skip = dead[fit] != 0 || !isfinite(nll[fit]);
-    const float step_size = (float)((double)h.lr / bc1);
-    const long long po = (long long)fit * param_stride;
-    float* __restrict__ g = grads + (long long)fit * grad_stride;
-    double acc;
-    if (mix.n != 0) {
-        key.sample += (uint32_t)fit;
-        acc = elbo_update_share_mix(params + po, g, m + po, v + po, n_vi, n_bn, mix_prepare(mix), key, h.temp, b1, b2, eps, step_size, inv_sqrt_bc2, skip);
-    } else {
-        acc = kt == MFVI_KL_FORWARD
-            ? elbo_update_share_fwd(params + po, g, m + po, v + po, n_vi, n_bn, h.prior_mu, h.prior_sigma, h.temp, b1, b2, eps, step_size, inv_sqrt_bc2, skip)
-            : elbo_update_share(params + po, g, m + po, v + po, n_vi, n_bn, h.prior_mu, h.prior_sigma, h.temp, b1, b2, eps, step_size, inv_sqrt_bc2, skip);
-    }
-    const double tot = block_sum_d(acc, s_red);
-    if (threadIdx.x == 0) partial[(long long)fit * UPDATE_MAX_BLOCKS + blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(256) void elbo_update_fits_mix_finish_kernel(const double* __restrict__ partial, int n_blocks, const double* __restrict__ nll,
-                                                                          const int32_t* __restrict__ kl_type, const mfvi_mixture_prior* __restrict__ mix_tab,
-                                                                          int32_t* __restrict__ dead, double* __restrict__ kl_out)
-{
-    __shared__ double s_red[8];
-    const int fit = blockIdx.x;
-    if (!fit_row_runs(mix_tab[fit], kl_type ? kl_type[fit] : MFVI_KL_REVERSE)) { if (threadIdx.x == 0) dead[fit] = 1; return; }
-    double t = 0;
-    for (int b = threadIdx.x; b < n_blocks; b += 256) t += partial[(long long)fit * UPDATE_MAX_BLOCKS + b];
+    for (int b = threadIdx.x; b < n_blocks; b += 256) t += partial[(long long)fit * ELBO_UPDATE_MAX_BLOCKS + b];
     t = block_sum_d(t, s_red);
     if (threadIdx.x == 0) { kl_out[fit] = t; if (!isfinite(nll[fit])) dead[fit] = 1; }
 }
@@ -211,6 +152,26 @@ __global__ __launch_bounds__(64) void masked_sq_err_fits_finish_kernel(const dou
     }
 }
 
+// the argument check of the three mfvi_elbo_update_fits* entries (`entry` names the caller in the message) and their two launches
+template <bool TYPED, bool MIX>
+int launch_elbo_update_fits(const char* entry, float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, int64_t param_stride, int64_t grad_stride,
+                            int n_fits, const mfvi_fit_hyper* hyper_dev, const int32_t* kl_type_dev, const mfvi_mixture_prior* mix_dev, RngKey key, float beta1,
+                            float beta2, float eps, int t, const double* nll, int32_t* dead, double* kl_out, void* scratch, void* stream)
+{
+    if (!params || !grads || !m || !v || !hyper_dev || !nll || !dead || !kl_out || !scratch || n_vi < 0 || n_bn < 0 || t < 1 || n_fits < 1 || n_fits > 65535 ||
+        param_stride < 2 * n_vi + n_bn || grad_stride < 2 * n_vi + n_bn || (MIX && n_vi > ((int64_t)1 << 34))) {      // a Philox block index is a 32-bit word
+        set_error("%s: bad arguments (t is 1-based, strides >= 2 n_vi + n_bn, scratch of mfvi_elbo_update_fits_scratch_bytes(n_fits) bytes)", entry); return -1; }
+    const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
+    const long long work = n_vi > n_bn ? n_vi : n_bn;      // as mfvi_elbo_update: the same blocks per fit
+    const int nb = nblocks(work, ELBO_UPDATE_MAX_BLOCKS);
+    hipLaunchKernelGGL((elbo_update_fits_kernel<TYPED, MIX>), dim3(nb, n_fits), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, (long long)n_vi, (long long)n_bn,
+                       (long long)param_stride, (long long)grad_stride, hyper_dev, kl_type_dev, mix_dev, key, beta1, beta2, eps, bc1, (float)(1.0 / sqrt(bc2)), nll,
+                       (const int32_t*)dead, (double*)scratch);
+    hipLaunchKernelGGL((elbo_update_fits_finish_kernel<TYPED, MIX>), dim3(n_fits), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, nb, nll, kl_type_dev, mix_dev,
+                       dead, kl_out);
+    return (int)hipGetLastError();
+}
+
 }  // namespace
 
 extern "C" {
@@ -240,23 +201,14 @@ int mfvi_gaussian_nll_fits(const float* out, const float* targets, int64_t targe
     return (int)hipGetLastError();
 }
 
-int64_t mfvi_elbo_update_fits_scratch_bytes(int n_fits) { return n_fits < 1 ? -1 : (int64_t)n_fits * UPDATE_MAX_BLOCKS * (int64_t)sizeof(double); }
+int64_t mfvi_elbo_update_fits_scratch_bytes(int n_fits) { return n_fits < 1 ? -1 : (int64_t)n_fits * ELBO_UPDATE_MAX_BLOCKS * (int64_t)sizeof(double); }
 
 int mfvi_elbo_update_fits(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, int64_t param_stride, int64_t grad_stride, int n_fits,
                           const mfvi_fit_hyper* hyper_dev, float beta1, float beta2, float eps, int t, const double* nll, int32_t* dead, double* kl_out,
                           void* scratch, void* stream)
 {
-    if (!params || !grads || !m || !v || !hyper_dev || !nll || !dead || !kl_out || !scratch || n_vi < 0 || n_bn < 0 || t < 1 || n_fits < 1 || n_fits > 65535 ||
-        param_stride < 2 * n_vi + n_bn || grad_stride < 2 * n_vi + n_bn) {
-        set_error("elbo_update_fits: bad arguments (t is 1-based, strides >= 2 n_vi + n_bn, scratch of mfvi_elbo_update_fits_scratch_bytes(n_fits) bytes)"); return -1; }
-    const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
-    const long long work = n_vi > n_bn ? n_vi : n_bn;
-    const int nb = nblocks(work, UPDATE_MAX_BLOCKS);
-    hipLaunchKernelGGL(elbo_update_fits_kernel, dim3(nb, n_fits), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, (long long)n_vi, (long long)n_bn,
-                       (long long)param_stride, (long long)grad_stride, hyper_dev, beta1, beta2, eps, bc1, (float)(1.0 / sqrt(bc2)), nll, (const int32_t*)dead,
-                       (double*)scratch);
-    hipLaunchKernelGGL(elbo_update_fits_finish_kernel, dim3(n_fits), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, nb, nll, dead, kl_out);
-    return (int)hipGetLastError();
+    return launch_elbo_update_fits<false, false>("elbo_update_fits", params, grads, m, v, n_vi, n_bn, param_stride, grad_stride, n_fits, hyper_dev, nullptr, nullptr,
+                                                 RngKey{}, beta1, beta2, eps, t, nll, dead, kl_out, scratch, stream);
 }
 
 int mfvi_elbo_update_fits_typed(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, int64_t param_stride, int64_t grad_stride, int n_fits,
@@ -266,19 +218,8 @@ int mfvi_elbo_update_fits_typed(float* params, float* grads, float* m, float* v,
     if (!kl_type_dev)      // all reverse: the entry above, as it is
         return mfvi_elbo_update_fits(params, grads, m, v, n_vi, n_bn, param_stride, grad_stride, n_fits, hyper_dev, beta1, beta2, eps, t, nll, dead, kl_out, scratch,
                                      stream);
-    if (!params || !grads || !m || !v || !hyper_dev || !nll || !dead || !kl_out || !scratch || n_vi < 0 || n_bn < 0 || t < 1 || n_fits < 1 || n_fits > 65535 ||
-        param_stride < 2 * n_vi + n_bn || grad_stride < 2 * n_vi + n_bn) {
-        set_error("elbo_update_fits_typed: bad arguments (t is 1-based, strides >= 2 n_vi + n_bn, scratch of mfvi_elbo_update_fits_scratch_bytes(n_fits) bytes)");
-        return -1; }
-    const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
-    const long long work = n_vi > n_bn ? n_vi : n_bn;
-    const int nb = nblocks(work, UPDATE_MAX_BLOCKS);
-    hipLaunchKernelGGL(elbo_update_fits_typed_kernel, dim3(nb, n_fits), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, (long long)n_vi, (long long)n_bn,
-                       (long long)param_stride, (long long)grad_stride, hyper_dev, kl_type_dev, beta1, beta2, eps, bc1, (float)(1.0 / sqrt(bc2)), nll,
-                       (const int32_t*)dead, (double*)scratch);
-    hipLaunchKernelGGL(elbo_update_fits_typed_finish_kernel, dim3(n_fits), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, nb, nll, kl_type_dev, dead,
-                       kl_out);
-    return (int)hipGetLastError();
+    return launch_elbo_update_fits<true, false>("elbo_update_fits_typed", params, grads, m, v, n_vi, n_bn, param_stride, grad_stride, n_fits, hyper_dev, kl_type_dev,
+                                                nullptr, RngKey{}, beta1, beta2, eps, t, nll, dead, kl_out, scratch, stream);
 }
 
 int mfvi_elbo_update_fits_mixture(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, int64_t param_stride, int64_t grad_stride,
@@ -289,20 +230,8 @@ int mfvi_elbo_update_fits_mixture(float* params, float* grads, float* m, float* 
     if (!mix_dev)          // no row has a mixture: the entry above, as it is
         return mfvi_elbo_update_fits_typed(params, grads, m, v, n_vi, n_bn, param_stride, grad_stride, n_fits, hyper_dev, kl_type_dev, beta1, beta2, eps, t, nll, dead,
                                            kl_out, scratch, stream);
-    if (!params || !grads || !m || !v || !hyper_dev || !nll || !dead || !kl_out || !scratch || n_vi < 0 || n_bn < 0 || t < 1 || n_fits < 1 || n_fits > 65535 ||
-        param_stride < 2 * n_vi + n_bn || grad_stride < 2 * n_vi + n_bn || n_vi > ((int64_t)1 << 34)) {
-        set_error("elbo_update_fits_mixture: bad arguments (t is 1-based, strides >= 2 n_vi + n_bn, scratch of mfvi_elbo_update_fits_scratch_bytes(n_fits) bytes)");
-        return -1; }
-    const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
-    const long long work = n_vi > n_bn ? n_vi : n_bn;
-    const int nb = nblocks(work, UPDATE_MAX_BLOCKS);
-    const RngKey key = klmc_key(seed, sample0, step, step_dev);
-    hipLaunchKernelGGL(elbo_update_fits_mix_kernel, dim3(nb, n_fits), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, (long long)n_vi, (long long)n_bn,
-                       (long long)param_stride, (long long)grad_stride, hyper_dev, kl_type_dev, mix_dev, key, beta1, beta2, eps, bc1, (float)(1.0 / sqrt(bc2)), nll,
-                       (const int32_t*)dead, (double*)scratch);
-    hipLaunchKernelGGL(elbo_update_fits_mix_finish_kernel, dim3(n_fits), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, nb, nll, kl_type_dev, mix_dev, dead,
-                       kl_out);
-    return (int)hipGetLastError();
+    return launch_elbo_update_fits<true, true>("elbo_update_fits_mixture", params, grads, m, v, n_vi, n_bn, param_stride, grad_stride, n_fits, hyper_dev, kl_type_dev,
+                                               mix_dev, klmc_key(seed, sample0, step, step_dev), beta1, beta2, eps, t, nll, dead, kl_out, scratch, stream);
 }
 
 int mfvi_ema_fits(const float* out, int n_fits, int S, int C, int H, int W, float* ema, float weight, int first, void* stream)

@@ -4,6 +4,11 @@
 #include "common.h"
 #include "../../include/mfvi_hip.h"
 
+// blocks of 256 threads over n elements, capped (the kernels stride over the rest)
+inline int nblocks(long long n, int cap = 2048) { long long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > cap ? cap : b)); }
+// the grid cap of every fused KL + Adam launch, single fit or one row of a batch: the same blocks, so the same KL partial sums in the same order
+constexpr int ELBO_UPDATE_MAX_BLOCKS = 2048;
+
 __device__ __forceinline__ void block_atomic_add(double v, double* dst, double* red)
 {
     const double s = block_sum_d(v, red);
@@ -74,34 +79,38 @@ __device__ __forceinline__ double gnll_sample_vec(const float* __restrict__ o, c
     return acc / (double)HW;
 }
 
-// ---- fused tail of an ELBO iteration on ONE flat block [MU | RHO | BN]: this thread's share (grid x strides over the elements) of the KL sum;
-// unless `skip`, grads += temp * dKL (written back) and AdamW(weight_decay = 0) on p / m / v ----
-__device__ __forceinline__ double elbo_update_share(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                    long long n_vi, long long n_bn, float m0, float s0, float temp, float b1, float b2, float eps,
-                                                    float step_size, float inv_sqrt_bc2, bool skip)
-{
-    const float log_s0 = logf(s0), s0sq = s0 * s0;
-    auto adam = [&](long long i, float gi) {
+// ---- AdamW(weight_decay = 0) on element i of a flat block: THE statement of the update, for every kernel that applies one.  next() stores
+// the two moments and returns the new value of a parameter that was `pi` (the bf16 update rounds it, adam_kernel decays pi first); () stores it ----
+struct AdamStep {
+    float* __restrict__ p; float* __restrict__ m; float* __restrict__ v;
+    float b1, b2, eps, step_size, inv_sqrt_bc2;
+    __device__ __forceinline__ float next(long long i, float gi, float pi) const
+    {
         const float mi = b1 * m[i] + (1.f - b1) * gi;
         const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
         m[i] = mi; v[i] = vi;
-        p[i] = p[i] - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
-    };
-    double acc = 0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_vi; i += (long long)gridDim.x * 256) {
-        const float mu = p[i], r = p[n_vi + i];
-        const float s = softplus_f(r), d = mu - m0, inv = 1.f / s;
-        acc += (double)(logf(s) - log_s0) + (double)((s0sq + d * d) / (2.f * s * s)) - 0.5;
-        if (skip) continue;
-        const float gmu = g[i] + temp * d * inv * inv;
-        const float grho = g[n_vi + i] + temp * (inv - (s0sq + d * d) * inv * inv * inv) * sigmoid_f(r);
-        g[i] = gmu; g[n_vi + i] = grho;
-        adam(i, gmu); adam(n_vi + i, grho);
+        return pi - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
     }
-    if (!skip)
-        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_bn; i += (long long)gridDim.x * 256) adam(2 * n_vi + i, g[2 * n_vi + i]);
-    return acc;
-}
+    __device__ __forceinline__ void operator()(long long i, float gi) const { p[i] = next(i, gi, p[i]); }
+};
+
+// ---- the KL term of ONE (mu, rho) pair as a policy: term() returns the term, float32 pieces added in float64, and
+// yields smu / srho = scale * its two derivatives.  The scale is applied in here because the directions associate that product differently
+// and the bits depend on it.  Arg is the prior as a kernel takes it: the policy is built on the device (log s0 is the device's logf) ----
+struct GaussPrior { float m0, s0; };
+// the reverse direction KL(prior || posterior) (BayTorch/modules/module.py:64-80): scale * d * inv * inv, left to right
+struct KlReverse {
+    typedef GaussPrior Arg;
+    float m0, log_s0, s0sq;
+    __device__ __forceinline__ explicit KlReverse(const GaussPrior& pr) : m0(pr.m0), log_s0(logf(pr.s0)), s0sq(pr.s0 * pr.s0) {}
+    __device__ __forceinline__ double term(float mu, float r, float scale, float& smu, float& srho) const
+    {
+        const float s = softplus_f(r), d = mu - m0, inv = 1.f / s;
+        smu = scale * d * inv * inv;
+        srho = scale * (inv - (s0sq + d * d) * inv * inv * inv) * sigmoid_f(r);
+        return (double)(logf(s) - log_s0) + (double)((s0sq + d * d) / (2.f * s * s)) - 0.5;
+    }
+};
 
 // ---- the forward direction, KL(posterior || prior) (modules/module.py:76-80 with kl_type != 'reverse'; the textbook ELBO's term), of ONE
 // (mu, rho) pair: returns the term, float32 pieces added in float64 as the reverse kernels add theirs; gmu / grho = its two derivatives.
@@ -116,25 +125,36 @@ __device__ __forceinline__ double kl_forward_terms(float mu, float r, float m0, 
     return (double)(log_s0 - logf(s)) + (double)((s * s + d * d) / (2.f * s0sq)) - 0.5;
 }
 
-// ---- elbo_update_share with the forward KL term: the same loops, the same Adam, the same order of the sum ----
-__device__ __forceinline__ double elbo_update_share_fwd(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                        long long n_vi, long long n_bn, float m0, float s0, float temp, float b1, float b2, float eps,
-                                                        float step_size, float inv_sqrt_bc2, bool skip)
+// the forward direction as a policy: scale * (the derivatives of kl_forward_terms)
+struct KlForward {
+    typedef GaussPrior Arg;
+    float m0, log_s0, s0sq;
+    __device__ __forceinline__ explicit KlForward(const GaussPrior& pr) : m0(pr.m0), log_s0(logf(pr.s0)), s0sq(pr.s0 * pr.s0) {}
+    // the product with the scale is outside the contract-off body: it may fuse with the caller's add
+    __device__ __forceinline__ double term(float mu, float r, float scale, float& smu, float& srho) const
+    {
+        float gmu, grho;
+        const double t = kl_forward_terms(mu, r, m0, log_s0, s0sq, gmu, grho);
+        smu = scale * gmu; srho = scale * grho;
+        return t;
+    }
+};
+
+// ---- fused tail of an ELBO iteration on ONE flat block [MU | RHO | BN] (adam.p): this thread's share (grid x strides over the elements) of
+// the KL sum; unless `skip`, grads += temp * dKL (written back) and Adam on p / m / v.  The loop shape fixes which thread owns which element
+// and with that the order of the float64 sum: this one serves the closed-form terms, elbo_update_share_quads the drawn one ----
+template <class Term>
+__device__ __forceinline__ double elbo_update_share(const Term& kl, float* __restrict__ g, long long n_vi, long long n_bn, float temp, const AdamStep& adam,
+                                                    bool skip)
 {
-    const float log_s0 = logf(s0), s0sq = s0 * s0;
-    auto adam = [&](long long i, float gi) {
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        p[i] = p[i] - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
-    };
+    const float* p = adam.p;
     double acc = 0;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_vi; i += (long long)gridDim.x * 256) {
         float dkm, dkr;
-        acc += kl_forward_terms(p[i], p[n_vi + i], m0, log_s0, s0sq, dkm, dkr);
+        acc += kl.term(p[i], p[n_vi + i], temp, dkm, dkr);
         if (skip) continue;
-        const float gmu = g[i] + temp * dkm;
-        const float grho = g[n_vi + i] + temp * dkr;
+        const float gmu = g[i] + dkm;
+        const float grho = g[n_vi + i] + dkr;
         g[i] = gmu; g[n_vi + i] = grho;
         adam(i, gmu); adam(n_vi + i, grho);
     }
@@ -222,20 +242,30 @@ __device__ __forceinline__ double kl_mixture_terms(float mu, float r, float eps,
     return (double)(-0.5f * (eps * eps) - logf(s)) - (double)L;
 }
 
-// ---- elbo_update_share with the Monte-Carlo mixture term: the same Adam and BN loop; the (mu, rho) pairs go in quads, element i = lane
+// the policy of the drawn term: the prior's constants and the key of the draw, its counter word resolved (Arg: key_now does that here)
+struct KlMixture {
+    struct Arg { mfvi_mixture_prior prior; RngKey key; };
+    MixPrep q; RngKey key;
+    __device__ __forceinline__ KlMixture(const mfvi_mixture_prior& prior, const RngKey& k) : q(mix_prepare(prior)), key(k) {}
+    __device__ __forceinline__ explicit KlMixture(const Arg& a) : q(mix_prepare(a.prior)), key(key_now(a.key)) {}
+    __device__ __forceinline__ double term(float mu, float r, float eps, float scale, float& smu, float& srho) const
+    {
+        float gmu, grho;
+        const double t = kl_mixture_terms(mu, r, eps, q, gmu, grho);
+        smu = scale * gmu; srho = scale * grho;
+        return t;
+    }
+};
+
+// ---- elbo_update_share for the drawn term: the same Adam and BN loop; the (mu, rho) pairs go in quads, element i = lane
 // i & 3 of Philox block i >> 2 of the key's stream (RNG domain KLMC), so a weight's draw costs a quarter of a Philox block and no memory.
 // A quad's four pairs and gradients are requested before any is used, with clamped indices (no branch around a load); the stores and the
 // Adam of a lane past n_vi are predicated ----
-__device__ __forceinline__ double elbo_update_share_mix(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                        long long n_vi, long long n_bn, const MixPrep& prior, const RngKey& key, float temp, float b1,
-                                                        float b2, float eps, float step_size, float inv_sqrt_bc2, bool skip)
+template <class Term>
+__device__ __forceinline__ double elbo_update_share_quads(const Term& kl, float* __restrict__ g, long long n_vi, long long n_bn, float temp,
+                                                          const AdamStep& adam, bool skip)
 {
-    auto adam = [&](long long i, float gi) {
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        p[i] = p[i] - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
-    };
+    const float* p = adam.p;
     double acc = 0;
     const long long nq = (n_vi + 3) >> 2;
     for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long long)gridDim.x * 256) {
@@ -245,17 +275,17 @@ __device__ __forceinline__ double elbo_update_share_mix(float* __restrict__ p, f
             const long long ic = 4 * q + l < n_vi ? 4 * q + l : n_vi - 1;
             mu4[l] = p[ic]; r4[l] = p[n_vi + ic]; gm4[l] = g[ic]; gr4[l] = g[n_vi + ic];
         }
-        spec_normal4(key, (uint32_t)q, z);
+        spec_normal4(kl.key, (uint32_t)q, z);
 #pragma unroll
         for (int l = 0; l < 4; ++l) {
             const long long i = 4 * q + l;
             float dkm, dkr;
-            const double term = kl_mixture_terms(mu4[l], r4[l], z[l], prior, dkm, dkr);
+            const double term = kl.term(mu4[l], r4[l], z[l], temp, dkm, dkr);
             if (i < n_vi) {
                 acc += term;
                 if (!skip) {
-                    const float gmu = gm4[l] + temp * dkm;
-                    const float grho = gr4[l] + temp * dkr;
+                    const float gmu = gm4[l] + dkm;
+                    const float grho = gr4[l] + dkr;
                     g[i] = gmu; g[n_vi + i] = grho;
                     adam(i, gmu); adam(n_vi + i, grho);
                 }

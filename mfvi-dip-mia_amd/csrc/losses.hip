@@ -151,59 +151,35 @@ __global__ __launch_bounds__(64) void dropout_mask_kernel(const DropEntry* __res
 }
 
 // ---- KL ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void kl_kernel(const float* __restrict__ mu, const float* __restrict__ rho, long long n,
-                                                 float m0, float s0, double* __restrict__ kl_out)
+// the unfused sum and gradient of a closed-form term (KlReverse / KlForward, iter_ops.h): one pair of kernels, the same grids for either direction
+template <class Term>
+__global__ __launch_bounds__(256) void kl_sum_kernel(const float* __restrict__ mu, const float* __restrict__ rho, long long n, GaussPrior prior,
+                                                     double* __restrict__ kl_out)
 {
     __shared__ double s_red[8];
+    const Term kl(prior);
     double acc = 0;
-    const float log_s0 = logf(s0), s0sq = s0 * s0;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const float s = softplus_f(rho[i]), d = mu[i] - m0;
-        acc += (double)(logf(s) - log_s0) + (double)((s0sq + d * d) / (2.f * s * s)) - 0.5;
+        float smu, srho;
+        acc += kl.term(mu[i], rho[i], 0.f, smu, srho);
     }
     block_atomic_add(acc, kl_out, s_red);
 }
 
-__global__ __launch_bounds__(256) void kl_bwd_kernel(const float* __restrict__ mu, const float* __restrict__ rho, long long n,
-                                                     float m0, float s0, float scale, float* __restrict__ dmu,
-                                                     float* __restrict__ drho)
+template <class Term>
+__global__ __launch_bounds__(256) void kl_grad_kernel(const float* __restrict__ mu, const float* __restrict__ rho, long long n, GaussPrior prior,
+                                                      float scale, float* __restrict__ dmu, float* __restrict__ drho)
 {
-    const float s0sq = s0 * s0;
+    const Term kl(prior);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const float r = rho[i], s = softplus_f(r), d = mu[i] - m0, inv = 1.f / s;
-        dmu[i] += scale * d * inv * inv;
-        drho[i] += scale * (inv - (s0sq + d * d) * inv * inv * inv) * sigmoid_f(r);
+        float smu, srho;
+        (void)kl.term(mu[i], rho[i], scale, smu, srho);
+        dmu[i] += smu;
+        drho[i] += srho;
     }
 }
 
-// the forward direction KL(posterior || prior) (kl_forward_terms, iter_ops.h): the grids and the order of the sum of the two kernels above
-__global__ __launch_bounds__(256) void kl_fwd_kernel(const float* __restrict__ mu, const float* __restrict__ rho, long long n,
-                                                     float m0, float s0, double* __restrict__ kl_out)
-{
-    __shared__ double s_red[8];
-    double acc = 0;
-    const float log_s0 = logf(s0), s0sq = s0 * s0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        float gmu, grho;
-        acc += kl_forward_terms(mu[i], rho[i], m0, log_s0, s0sq, gmu, grho);
-    }
-    block_atomic_add(acc, kl_out, s_red);
-}
-
-__global__ __launch_bounds__(256) void kl_fwd_bwd_kernel(const float* __restrict__ mu, const float* __restrict__ rho, long long n,
-                                                         float m0, float s0, float scale, float* __restrict__ dmu,
-                                                         float* __restrict__ drho)
-{
-    const float log_s0 = logf(s0), s0sq = s0 * s0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        float gmu, grho;
-        (void)kl_forward_terms(mu[i], rho[i], m0, log_s0, s0sq, gmu, grho);
-        dmu[i] += scale * gmu;
-        drho[i] += scale * grho;
-    }
-}
-
-// the Monte-Carlo term against a scale-mixture prior (kl_mixture_terms, iter_ops.h) on n pairs that are elements i0 .. i0 + n - 1 of the
+// the Monte-Carlo term against a scale-mixture prior (KlMixture, iter_ops.h) on n pairs that are elements i0 .. i0 + n - 1 of the
 // draw's stream: a thread takes the quads of Philox blocks i0 >> 2 .. (i0 + n - 1) >> 2, a lane outside the slice loads a clamped index and
 // adds / stores nothing.  EPS: the normals come from `eps` instead of the draw (a template argument: no run-time branch around the load).
 template <bool BWD, bool EPS>
@@ -212,7 +188,7 @@ __global__ __launch_bounds__(256) void kl_mix_kernel(const float* __restrict__ m
                                                      float* __restrict__ dmu, float* __restrict__ drho, double* __restrict__ kl_out)
 {
     __shared__ double s_red[8];
-    const MixPrep pr = mix_prepare(prior);
+    const KlMixture kl(prior, key);
     const long long q0 = i0 >> 2, nq = ((i0 + n - 1) >> 2) - q0 + 1;
     double acc = 0;
     for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long long)gridDim.x * 256) {
@@ -225,13 +201,13 @@ __global__ __launch_bounds__(256) void kl_mix_kernel(const float* __restrict__ m
             mu4[l] = mu[jc]; r4[l] = rho[jc];
             if (EPS) z[l] = eps[jc];
         }
-        if (!EPS) spec_normal4(key, (uint32_t)(q0 + q), z);
+        if (!EPS) spec_normal4(kl.key, (uint32_t)(q0 + q), z);
 #pragma unroll
         for (int l = 0; l < 4; ++l) {
-            float gmu, grho;
-            const double term = kl_mixture_terms(mu4[l], r4[l], z[l], pr, gmu, grho);
+            float smu, srho;
+            const double term = kl.term(mu4[l], r4[l], z[l], scale, smu, srho);
             if (j4[l] >= 0 && j4[l] < n) {
-                if (BWD) { dmu[j4[l]] += scale * gmu; drho[j4[l]] += scale * grho; }
+                if (BWD) { dmu[j4[l]] += smu; drho[j4[l]] += srho; }
                 else acc += term;
             }
         }
@@ -269,13 +245,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     __shared__ float s_bc[2];
     if (guard_skip(guard)) return;
     adam_bias(guard, lr, b1, b2, s_bc, step_size, inv_sqrt_bc2);
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const float gi = g[i];
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        p[i] = p[i] * decay - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));       // decay = 1 - lr*wd (exactly 1 for wd = 0)
-    }
+    const AdamStep adam{p, m, v, b1, b2, eps, step_size, inv_sqrt_bc2};
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+        p[i] = adam.next(i, g[i], p[i] * decay);       // decay = 1 - lr*wd (exactly 1 for wd = 0)
 }
 __global__ void step_advance_kernel(int* __restrict__ t_applied, StepGuard guard)
 {
@@ -283,52 +255,27 @@ __global__ void step_advance_kernel(int* __restrict__ t_applied, StepGuard guard
 }
 
 // ---- fused tail of an ELBO iteration: KL, its gradient and AdamW(wd = 0) over [MU | RHO | BN] in one pass ----
-// Same per-element arithmetic as kl_kernel / kl_bwd_kernel / adam_kernel.  The KL sum goes through per-block partials that a
+// The per-element arithmetic of kl_sum_kernel / kl_grad_kernel / adam_kernel (the same policies, iter_ops.h).  The KL sum goes through per-block partials that a
 // one-block kernel adds up in block order right behind: deterministic, and no same-address atomic chain (a ticket / atomicAdd
 // per block serialises at ~70 ns each: 2048 blocks cost 150 us on MI355X).
-constexpr int ELBO_UPDATE_MAX_BLOCKS = 2048;
 struct ElboUpdateScratch { double partial[ELBO_UPDATE_MAX_BLOCKS]; };
 
+// Term::Arg: the prior as the kernel takes it (the policy itself is built on the device); the drawn term walks the pairs in quads
+template <class Term>
 __global__ __launch_bounds__(256) void elbo_update_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                          long long n_vi, long long n_bn, float m0, float s0, float temp, float b1, float b2,
+                                                          long long n_vi, long long n_bn, typename Term::Arg prior, float temp, float b1, float b2,
                                                           float eps, float step_size, float inv_sqrt_bc2, ElboUpdateScratch* __restrict__ sc, float lr,
                                                           StepGuard guard)
 {
     __shared__ double s_red[8];
     __shared__ float s_bc[2];
+    const Term kl(prior);
     const bool skip = guard_skip(guard);             // NaN data term: KL is still reported, nothing is written
     adam_bias(guard, lr, b1, b2, s_bc, step_size, inv_sqrt_bc2);
-    const double acc = elbo_update_share(p, g, m, v, n_vi, n_bn, m0, s0, temp, b1, b2, eps, step_size, inv_sqrt_bc2, skip);
-    const double tot = block_sum_d(acc, s_red);
-    if (threadIdx.x == 0) sc->partial[blockIdx.x] = tot;
-}
-// elbo_update_kernel with the forward KL term (elbo_update_share_fwd): same grid, same partials, the finish kernel below
-__global__ __launch_bounds__(256) void elbo_update_fwd_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                              long long n_vi, long long n_bn, float m0, float s0, float temp, float b1, float b2,
-                                                              float eps, float step_size, float inv_sqrt_bc2, ElboUpdateScratch* __restrict__ sc, float lr,
-                                                              StepGuard guard)
-{
-    __shared__ double s_red[8];
-    __shared__ float s_bc[2];
-    const bool skip = guard_skip(guard);
-    adam_bias(guard, lr, b1, b2, s_bc, step_size, inv_sqrt_bc2);
-    const double acc = elbo_update_share_fwd(p, g, m, v, n_vi, n_bn, m0, s0, temp, b1, b2, eps, step_size, inv_sqrt_bc2, skip);
-    const double tot = block_sum_d(acc, s_red);
-    if (threadIdx.x == 0) sc->partial[blockIdx.x] = tot;
-}
-// elbo_update_kernel with the Monte-Carlo mixture term (elbo_update_share_mix): same partials, the finish kernel below; the draw's counter
-// word is resolved on the device (key_now)
-__global__ __launch_bounds__(256) void elbo_update_mix_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                              long long n_vi, long long n_bn, mfvi_mixture_prior prior, RngKey key, float temp, float b1,
-                                                              float b2, float eps, float step_size, float inv_sqrt_bc2, ElboUpdateScratch* __restrict__ sc,
-                                                              float lr, StepGuard guard)
-{
-    key = key_now(key);
-    __shared__ double s_red[8];
-    __shared__ float s_bc[2];
-    const bool skip = guard_skip(guard);
-    adam_bias(guard, lr, b1, b2, s_bc, step_size, inv_sqrt_bc2);
-    const double acc = elbo_update_share_mix(p, g, m, v, n_vi, n_bn, mix_prepare(prior), key, temp, b1, b2, eps, step_size, inv_sqrt_bc2, skip);
+    const AdamStep adam{p, m, v, b1, b2, eps, step_size, inv_sqrt_bc2};
+    double acc;
+    if constexpr (std::is_same<Term, KlMixture>::value) acc = elbo_update_share_quads(kl, g, n_vi, n_bn, temp, adam, skip);
+    else acc = elbo_update_share(kl, g, n_vi, n_bn, temp, adam, skip);
     const double tot = block_sum_d(acc, s_red);
     if (threadIdx.x == 0) sc->partial[blockIdx.x] = tot;
 }
@@ -478,7 +425,6 @@ __global__ __launch_bounds__(256) void ring_stats_kernel(const float* __restrict
     }
 }
 
-inline int nblocks(long long n, int cap = 2048) { long long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > cap ? cap : b)); }
 inline RngKey make_key(uint64_t seed, uint32_t domain, uint32_t stream, uint32_t sample, uint32_t step)
 {
     RngKey k; k.k0 = (uint32_t)seed; k.k1 = (uint32_t)(seed >> 32); k.stream = (domain << 24) | stream; k.sample = sample; k.step = step; k.step_dev = nullptr;
@@ -701,61 +647,16 @@ __global__ __launch_bounds__(256) void round_bf16_kernel(const float* __restrict
 // both Adam moments and the update in fp32; the new mu / rho go back to bf16 by STOCHASTIC rounding with a 16-bit word of the counter
 // RNG: domain ROUND, stream 0 (MU) / 1 (RHO), element j = lane j & 3 of block j >> 2, sample 0, step = t (upper 16 bits of the word).
 // The BatchNorm parameters stay float32.
+template <class Term>
 __global__ __launch_bounds__(256) void elbo_update_bf16_kernel(bf16_t* __restrict__ pm, bf16_t* __restrict__ pr, float* __restrict__ bn, float* __restrict__ g, float* __restrict__ m,
-                                                               float* __restrict__ v, long long n_vi, long long n_bn, float m0, float s0, float temp,
+                                                               float* __restrict__ v, long long n_vi, long long n_bn, GaussPrior prior, float temp,
                                                                float b1, float b2, float eps, float step_size, float inv_sqrt_bc2, RngKey key,
                                                                ElboUpdateScratch* __restrict__ sc)
 {
     key = key_now(key);
     __shared__ double s_red[8];
-    const float log_s0 = logf(s0), s0sq = s0 * s0;
-    auto adam = [&](long long i, float gi, float pi) -> float {
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        return pi - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
-    };
-    double acc = 0;
-    const long long nq = (n_vi + 3) >> 2;
-    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long long)gridDim.x * 256) {
-        uint32_t rm[4], rr[4];
-        RngKey k0 = key; k0.stream = ((uint32_t)DOMAIN_ROUND << 24) | 0u;
-        philox4x32_10((uint32_t)q, k0.stream, k0.sample, k0.step, k0.k0, k0.k1, rm);
-        philox4x32_10((uint32_t)q, k0.stream | 1u, k0.sample, k0.step, k0.k0, k0.k1, rr);
-#pragma unroll
-        for (int l = 0; l < 4; ++l) {
-            const long long i = 4 * q + l;
-            if (i >= n_vi) break;
-            const float mu = bf16_to_f32(pm[i]), r = bf16_to_f32(pr[i]);
-            const float s = softplus_f(r), d = mu - m0, inv = 1.f / s;
-            acc += (double)(logf(s) - log_s0) + (double)((s0sq + d * d) / (2.f * s * s)) - 0.5;
-            const float gmu = g[i] + temp * d * inv * inv;
-            const float grho = g[n_vi + i] + temp * (inv - (s0sq + d * d) * inv * inv * inv) * sigmoid_f(r);
-            g[i] = gmu; g[n_vi + i] = grho;
-            pm[i] = f32_to_bf16_sr(adam(i, gmu, mu), rm[l] >> 16);
-            pr[i] = f32_to_bf16_sr(adam(n_vi + i, grho, r), rr[l] >> 16);
-        }
-    }
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_bn; i += (long long)gridDim.x * 256) bn[i] = adam(2 * n_vi + i, g[2 * n_vi + i], bn[i]);
-    const double tot = block_sum_d(acc, s_red);
-    if (threadIdx.x == 0) sc->partial[blockIdx.x] = tot;
-}
-
-// elbo_update_bf16_kernel with the forward KL term: the same quads, rounding words and Adam
-__global__ __launch_bounds__(256) void elbo_update_bf16_fwd_kernel(bf16_t* __restrict__ pm, bf16_t* __restrict__ pr, float* __restrict__ bn, float* __restrict__ g,
-                                                                   float* __restrict__ m, float* __restrict__ v, long long n_vi, long long n_bn, float m0, float s0,
-                                                                   float temp, float b1, float b2, float eps, float step_size, float inv_sqrt_bc2, RngKey key,
-                                                                   ElboUpdateScratch* __restrict__ sc)
-{
-    key = key_now(key);
-    __shared__ double s_red[8];
-    const float log_s0 = logf(s0), s0sq = s0 * s0;
-    auto adam = [&](long long i, float gi, float pi) -> float {
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        return pi - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
-    };
+    const Term kl(prior);
+    const AdamStep adam{nullptr, m, v, b1, b2, eps, step_size, inv_sqrt_bc2};      // next() only: the parameters are not one float32 block
     double acc = 0;
     const long long nq = (n_vi + 3) >> 2;
     for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long long)gridDim.x * 256) {
@@ -769,15 +670,15 @@ __global__ __launch_bounds__(256) void elbo_update_bf16_fwd_kernel(bf16_t* __res
             if (i >= n_vi) break;
             const float mu = bf16_to_f32(pm[i]), r = bf16_to_f32(pr[i]);
             float dkm, dkr;
-            acc += kl_forward_terms(mu, r, m0, log_s0, s0sq, dkm, dkr);
-            const float gmu = g[i] + temp * dkm;
-            const float grho = g[n_vi + i] + temp * dkr;
+            acc += kl.term(mu, r, temp, dkm, dkr);
+            const float gmu = g[i] + dkm;
+            const float grho = g[n_vi + i] + dkr;
             g[i] = gmu; g[n_vi + i] = grho;
-            pm[i] = f32_to_bf16_sr(adam(i, gmu, mu), rm[l] >> 16);
-            pr[i] = f32_to_bf16_sr(adam(n_vi + i, grho, r), rr[l] >> 16);
+            pm[i] = f32_to_bf16_sr(adam.next(i, gmu, mu), rm[l] >> 16);
+            pr[i] = f32_to_bf16_sr(adam.next(n_vi + i, grho, r), rr[l] >> 16);
         }
     }
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_bn; i += (long long)gridDim.x * 256) bn[i] = adam(2 * n_vi + i, g[2 * n_vi + i], bn[i]);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_bn; i += (long long)gridDim.x * 256) bn[i] = adam.next(2 * n_vi + i, g[2 * n_vi + i], bn[i]);
     const double tot = block_sum_d(acc, s_red);
     if (threadIdx.x == 0) sc->partial[blockIdx.x] = tot;
 }
@@ -805,6 +706,57 @@ const char* kl_mixture_refusal(const float* mu, const float* rho, int64_t n, int
     if (i0 < 0) return "i0 < 0";
     if (n > ((int64_t)1 << 34) || i0 > ((int64_t)1 << 34) - n) return "i0 + n beyond the 2^34 elements of a stream";
     return nullptr;
+}
+
+// ---- the launches behind the KL entry points: an entry checks its own arguments, then calls one of these ----
+template <class Term>
+int launch_kl_sum(const float* mu, const float* rho, int64_t n, const GaussPrior& prior, double* kl_out, hipStream_t st)
+{
+    hipError_t e = hipMemsetAsync(kl_out, 0, sizeof(double), st); if (e) return (int)e;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(kl_sum_kernel<Term>, dim3(nblocks(n, 96)), dim3(256), 0, st, mu, rho, (long long)n, prior, kl_out);
+    return (int)hipGetLastError();
+}
+template <class Term>
+int launch_kl_grad(const float* mu, const float* rho, int64_t n, const GaussPrior& prior, float scale, float* dmu, float* drho, hipStream_t st)
+{
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(kl_grad_kernel<Term>, dim3(nblocks(n)), dim3(256), 0, st, mu, rho, (long long)n, prior, scale, dmu, drho);
+    return (int)hipGetLastError();
+}
+// the fused tail: the main launch and the finish launch.  t_applied == nullptr: update number t from the host, the bias corrections formed
+// here; else the device counter behind the NaN guard (loss_d / loss_f), the corrections formed in the kernel (adam_bias)
+template <class Term>
+int launch_elbo_update(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, const typename Term::Arg& prior, float temp, float lr,
+                       float beta1, float beta2, float eps, int t, int32_t* t_applied, const double* loss_d, const float* loss_f, double* kl_out, void* scratch,
+                       void* stream)
+{
+    float step_size = 0.f, inv_sqrt_bc2 = 0.f;
+    if (!t_applied) {
+        const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
+        step_size = (float)((double)lr / bc1); inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    }
+    const long long work = n_vi > n_bn ? n_vi : n_bn;      // the grid of every fused update, a row of mfvi_elbo_update_fits* included: the same partials
+    const int nb = nblocks(work, ELBO_UPDATE_MAX_BLOCKS);
+    const StepGuard guard{t_applied, loss_d, loss_f};
+    hipLaunchKernelGGL(elbo_update_kernel<Term>, dim3(nb), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, (long long)n_vi, (long long)n_bn, prior, temp,
+                       beta1, beta2, eps, step_size, inv_sqrt_bc2, (ElboUpdateScratch*)scratch, lr, guard);
+    hipLaunchKernelGGL(elbo_update_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const ElboUpdateScratch*)scratch, nb, kl_out, (int*)t_applied, guard);
+    return (int)hipGetLastError();
+}
+template <class Term>
+int launch_elbo_update_bf16(void* mu_bf16, void* rho_bf16, float* bn, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, const GaussPrior& prior,
+                            float temp, float lr, float beta1, float beta2, float eps, int t, uint64_t seed, double* kl_out, void* scratch, void* stream)
+{
+    const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
+    const long long work = std::max<long long>((n_vi + 3) / 4, n_bn);
+    const int nb = nblocks(work, ELBO_UPDATE_MAX_BLOCKS);
+    hipLaunchKernelGGL(elbo_update_bf16_kernel<Term>, dim3(nb), dim3(256), 0, (hipStream_t)stream, (bf16_t*)mu_bf16, (bf16_t*)rho_bf16, bn, grads, m, v,
+                       (long long)n_vi, (long long)n_bn, prior, temp, beta1, beta2, eps, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)),
+                       make_key(seed, DOMAIN_ROUND, 0, 0, (uint32_t)t), (ElboUpdateScratch*)scratch);
+    hipLaunchKernelGGL(elbo_update_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const ElboUpdateScratch*)scratch, nb, kl_out, (int*)nullptr,
+                       StepGuard{nullptr, nullptr, nullptr});
+    return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -904,33 +856,24 @@ int mfvi_gaussian_nll_tensors_backward(const float* mu, const float* neg_logvar,
 
 int mfvi_kl(const float* mu, const float* rho, int64_t n, float prior_mu, float prior_sigma, double* kl_out, void* stream)
 {
-    hipStream_t st = (hipStream_t)stream;
     if (n < 0 || !(prior_sigma > 0.f)) { set_error("kl: bad arguments"); return -1; }
-    hipError_t e = hipMemsetAsync(kl_out, 0, sizeof(double), st); if (e) return (int)e;
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(kl_kernel, dim3(nblocks(n, 96)), dim3(256), 0, st, mu, rho, (long long)n, prior_mu, prior_sigma, kl_out);
-    return (int)hipGetLastError();
+    return launch_kl_sum<KlReverse>(mu, rho, n, GaussPrior{prior_mu, prior_sigma}, kl_out, (hipStream_t)stream);
 }
 
 int mfvi_kl_backward(const float* mu, const float* rho, int64_t n, float prior_mu, float prior_sigma, float scale, float* dmu,
                      float* drho, void* stream)
 {
     if (n < 0 || !(prior_sigma > 0.f)) { set_error("kl_backward: bad arguments"); return -1; }
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(kl_bwd_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, mu, rho, (long long)n, prior_mu, prior_sigma, scale, dmu, drho);
-    return (int)hipGetLastError();
+    return launch_kl_grad<KlReverse>(mu, rho, n, GaussPrior{prior_mu, prior_sigma}, scale, dmu, drho, (hipStream_t)stream);
 }
 
 int mfvi_kl_typed(const float* mu, const float* rho, int64_t n, float prior_mu, float prior_sigma, int kl_type, double* kl_out, void* stream)
 {
-    hipStream_t st = (hipStream_t)stream;
     const char* why = kl_type_refusal(kl_type, prior_sigma);
     if (!why && (!mu || !rho || !kl_out || n < 1)) why = "null pointer or n < 1";
     if (why) { set_error("kl_typed: %s", why); return -1; }
     if (kl_type == MFVI_KL_REVERSE) return mfvi_kl(mu, rho, n, prior_mu, prior_sigma, kl_out, stream);
-    hipError_t e = hipMemsetAsync(kl_out, 0, sizeof(double), st); if (e) return (int)e;
-    hipLaunchKernelGGL(kl_fwd_kernel, dim3(nblocks(n, 96)), dim3(256), 0, st, mu, rho, (long long)n, prior_mu, prior_sigma, kl_out);
-    return (int)hipGetLastError();
+    return launch_kl_sum<KlForward>(mu, rho, n, GaussPrior{prior_mu, prior_sigma}, kl_out, (hipStream_t)stream);
 }
 
 int mfvi_kl_backward_typed(const float* mu, const float* rho, int64_t n, float prior_mu, float prior_sigma, float scale, int kl_type, float* dmu,
@@ -940,8 +883,7 @@ int mfvi_kl_backward_typed(const float* mu, const float* rho, int64_t n, float p
     if (!why && (!mu || !rho || !dmu || !drho || n < 1)) why = "null pointer or n < 1";
     if (why) { set_error("kl_backward_typed: %s", why); return -1; }
     if (kl_type == MFVI_KL_REVERSE) return mfvi_kl_backward(mu, rho, n, prior_mu, prior_sigma, scale, dmu, drho, stream);
-    hipLaunchKernelGGL(kl_fwd_bwd_kernel, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, mu, rho, (long long)n, prior_mu, prior_sigma, scale, dmu, drho);
-    return (int)hipGetLastError();
+    return launch_kl_grad<KlForward>(mu, rho, n, GaussPrior{prior_mu, prior_sigma}, scale, dmu, drho, (hipStream_t)stream);
 }
 
 int mfvi_kl_mixture(const float* mu, const float* rho, int64_t n, int64_t i0, const mfvi_mixture_prior* prior, const float* eps, uint64_t seed,
@@ -990,15 +932,8 @@ int mfvi_elbo_update(float* params, float* grads, float* m, float* v, int64_t n_
 {
     if (!params || !grads || !m || !v || !kl_out || !scratch || n_vi < 0 || n_bn < 0 || t < 1 || !(prior_sigma > 0.f)) {
         set_error("elbo_update: bad arguments (t is 1-based, scratch of mfvi_elbo_update_scratch_bytes() bytes)"); return -1; }
-    const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
-    const long long work = n_vi > n_bn ? n_vi : n_bn;
-    const int nb = nblocks(work, ELBO_UPDATE_MAX_BLOCKS);
-    hipLaunchKernelGGL(elbo_update_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, (long long)n_vi, (long long)n_bn,
-                       prior_mu, prior_sigma, temp, beta1, beta2, eps, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)), (ElboUpdateScratch*)scratch, lr,
-                       StepGuard{nullptr, nullptr, nullptr});
-    hipLaunchKernelGGL(elbo_update_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const ElboUpdateScratch*)scratch, nb, kl_out, (int*)nullptr,
-                       StepGuard{nullptr, nullptr, nullptr});
-    return (int)hipGetLastError();
+    return launch_elbo_update<KlReverse>(params, grads, m, v, n_vi, n_bn, GaussPrior{prior_mu, prior_sigma}, temp, lr, beta1, beta2, eps, t, nullptr, nullptr, nullptr,
+                                         kl_out, scratch, stream);
 }
 
 int mfvi_elbo_update_guarded(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, float prior_mu, float prior_sigma, float temp,
@@ -1007,32 +942,20 @@ int mfvi_elbo_update_guarded(float* params, float* grads, float* m, float* v, in
 {
     if (!params || !grads || !m || !v || !kl_out || !scratch || !t_applied || n_vi < 0 || n_bn < 0 || !(prior_sigma > 0.f)) {
         set_error("elbo_update_guarded: bad arguments (t_applied: device counter of applied updates)"); return -1; }
-    const long long work = n_vi > n_bn ? n_vi : n_bn;
-    const int nb = nblocks(work, ELBO_UPDATE_MAX_BLOCKS);
-    const StepGuard guard{t_applied, loss_d, loss_f};
-    hipLaunchKernelGGL(elbo_update_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, (long long)n_vi, (long long)n_bn,
-                       prior_mu, prior_sigma, temp, beta1, beta2, eps, 0.f, 0.f, (ElboUpdateScratch*)scratch, lr, guard);
-    hipLaunchKernelGGL(elbo_update_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const ElboUpdateScratch*)scratch, nb, kl_out, t_applied, guard);
-    return (int)hipGetLastError();
+    return launch_elbo_update<KlReverse>(params, grads, m, v, n_vi, n_bn, GaussPrior{prior_mu, prior_sigma}, temp, lr, beta1, beta2, eps, 0, t_applied, loss_d, loss_f,
+                                         kl_out, scratch, stream);
 }
 
 int mfvi_elbo_update_typed(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, float prior_mu, float prior_sigma, float temp,
                            int kl_type, float lr, float beta1, float beta2, float eps, int t, double* kl_out, void* scratch, void* stream)
 {
     if (const char* why = kl_type_refusal(kl_type, prior_sigma)) { set_error("elbo_update_typed: %s", why); return -1; }
-    if (kl_type == MFVI_KL_REVERSE)
+    if (kl_type == MFVI_KL_REVERSE)      // the untyped entry, its refusals included
         return mfvi_elbo_update(params, grads, m, v, n_vi, n_bn, prior_mu, prior_sigma, temp, lr, beta1, beta2, eps, t, kl_out, scratch, stream);
     if (!params || !grads || !m || !v || !kl_out || !scratch || n_vi < 0 || n_bn < 0 || t < 1) {
         set_error("elbo_update_typed: bad arguments (t is 1-based, scratch of mfvi_elbo_update_scratch_bytes() bytes)"); return -1; }
-    const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
-    const long long work = n_vi > n_bn ? n_vi : n_bn;
-    const int nb = nblocks(work, ELBO_UPDATE_MAX_BLOCKS);
-    hipLaunchKernelGGL(elbo_update_fwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, (long long)n_vi, (long long)n_bn,
-                       prior_mu, prior_sigma, temp, beta1, beta2, eps, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)), (ElboUpdateScratch*)scratch, lr,
-                       StepGuard{nullptr, nullptr, nullptr});
-    hipLaunchKernelGGL(elbo_update_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const ElboUpdateScratch*)scratch, nb, kl_out, (int*)nullptr,
-                       StepGuard{nullptr, nullptr, nullptr});
-    return (int)hipGetLastError();
+    return launch_elbo_update<KlForward>(params, grads, m, v, n_vi, n_bn, GaussPrior{prior_mu, prior_sigma}, temp, lr, beta1, beta2, eps, t, nullptr, nullptr, nullptr,
+                                         kl_out, scratch, stream);
 }
 
 int mfvi_elbo_update_guarded_typed(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, float prior_mu, float prior_sigma, float temp,
@@ -1040,18 +963,13 @@ int mfvi_elbo_update_guarded_typed(float* params, float* grads, float* m, float*
                                    double* kl_out, void* scratch, void* stream)
 {
     if (const char* why = kl_type_refusal(kl_type, prior_sigma)) { set_error("elbo_update_guarded_typed: %s", why); return -1; }
-    if (kl_type == MFVI_KL_REVERSE)
+    if (kl_type == MFVI_KL_REVERSE)      // the untyped entry, its refusals included
         return mfvi_elbo_update_guarded(params, grads, m, v, n_vi, n_bn, prior_mu, prior_sigma, temp, lr, beta1, beta2, eps, t_applied, loss_d, loss_f, kl_out,
                                         scratch, stream);
     if (!params || !grads || !m || !v || !kl_out || !scratch || !t_applied || n_vi < 0 || n_bn < 0) {
         set_error("elbo_update_guarded_typed: bad arguments (t_applied: device counter of applied updates)"); return -1; }
-    const long long work = n_vi > n_bn ? n_vi : n_bn;
-    const int nb = nblocks(work, ELBO_UPDATE_MAX_BLOCKS);
-    const StepGuard guard{t_applied, loss_d, loss_f};
-    hipLaunchKernelGGL(elbo_update_fwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, (long long)n_vi, (long long)n_bn,
-                       prior_mu, prior_sigma, temp, beta1, beta2, eps, 0.f, 0.f, (ElboUpdateScratch*)scratch, lr, guard);
-    hipLaunchKernelGGL(elbo_update_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const ElboUpdateScratch*)scratch, nb, kl_out, t_applied, guard);
-    return (int)hipGetLastError();
+    return launch_elbo_update<KlForward>(params, grads, m, v, n_vi, n_bn, GaussPrior{prior_mu, prior_sigma}, temp, lr, beta1, beta2, eps, 0, t_applied, loss_d, loss_f,
+                                         kl_out, scratch, stream);
 }
 
 int mfvi_elbo_update_mixture(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, const mfvi_mixture_prior* prior, float temp,
@@ -1061,15 +979,8 @@ int mfvi_elbo_update_mixture(float* params, float* grads, float* m, float* v, in
     if (const char* why = mixture_refusal(prior)) { set_error("elbo_update_mixture: %s", why); return -1; }
     if (!params || !grads || !m || !v || !kl_out || !scratch || n_vi < 0 || n_bn < 0 || t < 1 || n_vi > ((int64_t)1 << 34)) {
         set_error("elbo_update_mixture: bad arguments (t is 1-based, scratch of mfvi_elbo_update_scratch_bytes() bytes)"); return -1; }
-    const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
-    const long long work = n_vi > n_bn ? n_vi : n_bn;      // the grid of mfvi_elbo_update (and of a row of mfvi_elbo_update_fits_mixture: the same partials)
-    const int nb = nblocks(work, ELBO_UPDATE_MAX_BLOCKS);
-    hipLaunchKernelGGL(elbo_update_mix_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, (long long)n_vi, (long long)n_bn, *prior,
-                       klmc_key(seed, sample, step, step_dev), temp, beta1, beta2, eps, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)),
-                       (ElboUpdateScratch*)scratch, lr, StepGuard{nullptr, nullptr, nullptr});
-    hipLaunchKernelGGL(elbo_update_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const ElboUpdateScratch*)scratch, nb, kl_out, (int*)nullptr,
-                       StepGuard{nullptr, nullptr, nullptr});
-    return (int)hipGetLastError();
+    return launch_elbo_update<KlMixture>(params, grads, m, v, n_vi, n_bn, KlMixture::Arg{*prior, klmc_key(seed, sample, step, step_dev)}, temp, lr, beta1, beta2, eps, t,
+                                         nullptr, nullptr, nullptr, kl_out, scratch, stream);
 }
 
 int mfvi_elbo_update_guarded_mixture(float* params, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, const mfvi_mixture_prior* prior,
@@ -1080,13 +991,8 @@ int mfvi_elbo_update_guarded_mixture(float* params, float* grads, float* m, floa
     if (const char* why = mixture_refusal(prior)) { set_error("elbo_update_guarded_mixture: %s", why); return -1; }
     if (!params || !grads || !m || !v || !kl_out || !scratch || !t_applied || n_vi < 0 || n_bn < 0 || n_vi > ((int64_t)1 << 34)) {
         set_error("elbo_update_guarded_mixture: bad arguments (t_applied: device counter of applied updates)"); return -1; }
-    const long long work = n_vi > n_bn ? n_vi : n_bn;      // the grid of mfvi_elbo_update (and of a row of mfvi_elbo_update_fits_mixture: the same partials)
-    const int nb = nblocks(work, ELBO_UPDATE_MAX_BLOCKS);
-    const StepGuard guard{t_applied, loss_d, loss_f};
-    hipLaunchKernelGGL(elbo_update_mix_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, (long long)n_vi, (long long)n_bn, *prior,
-                       klmc_key(seed, sample, step, step_dev), temp, beta1, beta2, eps, 0.f, 0.f, (ElboUpdateScratch*)scratch, lr, guard);
-    hipLaunchKernelGGL(elbo_update_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const ElboUpdateScratch*)scratch, nb, kl_out, t_applied, guard);
-    return (int)hipGetLastError();
+    return launch_elbo_update<KlMixture>(params, grads, m, v, n_vi, n_bn, KlMixture::Arg{*prior, klmc_key(seed, sample, step, step_dev)}, temp, lr, beta1, beta2, eps, 0,
+                                         t_applied, loss_d, loss_f, kl_out, scratch, stream);
 }
 
 int mfvi_adamw_step_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
@@ -1120,15 +1026,8 @@ int mfvi_elbo_update_bf16(void* mu_bf16, void* rho_bf16, float* bn, float* grads
 {
     if (!mu_bf16 || !rho_bf16 || !grads || !m || !v || !kl_out || !scratch || n_vi < 0 || n_bn < 0 || (n_bn > 0 && !bn) || t < 1 || !(prior_sigma > 0.f)) {
         set_error("elbo_update_bf16: bad arguments (t is 1-based)"); return -1; }
-    const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
-    const long long work = std::max<long long>((n_vi + 3) / 4, n_bn);
-    const int nb = nblocks(work, ELBO_UPDATE_MAX_BLOCKS);
-    hipLaunchKernelGGL(elbo_update_bf16_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (bf16_t*)mu_bf16, (bf16_t*)rho_bf16, bn, grads, m, v, (long long)n_vi,
-                       (long long)n_bn, prior_mu, prior_sigma, temp, beta1, beta2, eps, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)),
-                       make_key(seed, DOMAIN_ROUND, 0, 0, (uint32_t)t), (ElboUpdateScratch*)scratch);
-    hipLaunchKernelGGL(elbo_update_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const ElboUpdateScratch*)scratch, nb, kl_out, (int*)nullptr,
-                       StepGuard{nullptr, nullptr, nullptr});
-    return (int)hipGetLastError();
+    return launch_elbo_update_bf16<KlReverse>(mu_bf16, rho_bf16, bn, grads, m, v, n_vi, n_bn, GaussPrior{prior_mu, prior_sigma}, temp, lr, beta1, beta2, eps, t, seed,
+                                              kl_out, scratch, stream);
 }
 
 int mfvi_elbo_update_bf16_typed(void* mu_bf16, void* rho_bf16, float* bn, float* grads, float* m, float* v, int64_t n_vi, int64_t n_bn, float prior_mu,
@@ -1136,20 +1035,13 @@ int mfvi_elbo_update_bf16_typed(void* mu_bf16, void* rho_bf16, float* bn, float*
                                 void* scratch, void* stream)
 {
     if (const char* why = kl_type_refusal(kl_type, prior_sigma)) { set_error("elbo_update_bf16_typed: %s", why); return -1; }
-    if (kl_type == MFVI_KL_REVERSE)
+    if (kl_type == MFVI_KL_REVERSE)      // the untyped entry, its refusals included
         return mfvi_elbo_update_bf16(mu_bf16, rho_bf16, bn, grads, m, v, n_vi, n_bn, prior_mu, prior_sigma, temp, lr, beta1, beta2, eps, t, seed, kl_out, scratch,
                                      stream);
     if (!mu_bf16 || !rho_bf16 || !grads || !m || !v || !kl_out || !scratch || n_vi < 0 || n_bn < 0 || (n_bn > 0 && !bn) || t < 1) {
         set_error("elbo_update_bf16_typed: bad arguments (t is 1-based)"); return -1; }
-    const double bc1 = 1.0 - pow((double)beta1, t), bc2 = 1.0 - pow((double)beta2, t);
-    const long long work = std::max<long long>((n_vi + 3) / 4, n_bn);
-    const int nb = nblocks(work, ELBO_UPDATE_MAX_BLOCKS);
-    hipLaunchKernelGGL(elbo_update_bf16_fwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, (bf16_t*)mu_bf16, (bf16_t*)rho_bf16, bn, grads, m, v, (long long)n_vi,
-                       (long long)n_bn, prior_mu, prior_sigma, temp, beta1, beta2, eps, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)),
-                       make_key(seed, DOMAIN_ROUND, 0, 0, (uint32_t)t), (ElboUpdateScratch*)scratch);
-    hipLaunchKernelGGL(elbo_update_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const ElboUpdateScratch*)scratch, nb, kl_out, (int*)nullptr,
-                       StepGuard{nullptr, nullptr, nullptr});
-    return (int)hipGetLastError();
+    return launch_elbo_update_bf16<KlForward>(mu_bf16, rho_bf16, bn, grads, m, v, n_vi, n_bn, GaussPrior{prior_mu, prior_sigma}, temp, lr, beta1, beta2, eps, t, seed,
+                                              kl_out, scratch, stream);
 }
 
 int mfvi_bf16_to_f32(const void* src, int64_t n, float* dst, void* stream)

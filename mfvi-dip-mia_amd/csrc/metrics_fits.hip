@@ -8,8 +8,6 @@
 
 namespace {
 
-inline int nblocks(long long n, int cap = 2048) { long long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > cap ? cap : b)); }
-
 // grid (pixels, fit): bookkeep_kernel's body (losses.hip) on fit blockIdx.y; the map buffers are [n_fits][HW]
 __global__ __launch_bounds__(256) void bookkeep_fits_kernel(const float* __restrict__ out, int S, int C, long long HW, float* __restrict__ ema, float w, int first,
                                                             float* __restrict__ out_clip, float* __restrict__ avg_clip, float* __restrict__ ale_clip,

@@ -324,10 +324,8 @@ class ElboEngine:
                 return
             if self.param_dtype == "bf16":      # the KL of the float32 values the bf16 parameters denote (step() fuses this into the update)
                 mu, rho = self.params_f32()[:2]
-            kl, kt = self._kl_entry("mfvi_kl")
-            L.check(kl(L.ptr(mu), L.ptr(rho), self.n_vi, 0.0, self.prior_sigma, *kt, L.ptr(self.acc[1:]), sp))
-            kl_bwd, kt = self._kl_entry("mfvi_kl_backward")
-            L.check(kl_bwd(L.ptr(mu), L.ptr(rho), self.n_vi, 0.0, self.prior_sigma, self.temp, *kt, L.ptr(self.dmu), L.ptr(self.drho), sp))
+            L.check(lib.mfvi_kl_typed(L.ptr(mu), L.ptr(rho), self.n_vi, 0.0, self.prior_sigma, self._klt, L.ptr(self.acc[1:]), sp))
+            L.check(lib.mfvi_kl_backward_typed(L.ptr(mu), L.ptr(rho), self.n_vi, 0.0, self.prior_sigma, self.temp, self._klt, L.ptr(self.dmu), L.ptr(self.drho), sp))
 
     def set_allreduce_overlap(self, enabled, tail_fraction=0.9):
         """K sharded over ranks: start the exchange under the tail of the backward pass.  The weight gradients of the deep / up-path ops —
@@ -409,9 +407,9 @@ class ElboEngine:
             self._update_mixture(guard, 0, L.ptr(self.step_dev))
             self.step_dev.add_(1)
             return
-        update, kt = self._kl_entry("mfvi_elbo_update_guarded")
-        L.check(update(L.ptr(self.params), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi, self.n_bn, 0.0, self.prior_sigma, self.temp, *kt,
-                       self.lr, 0.9, 0.999, 1e-8, L.ptr(self.t_applied), *guard, L.ptr(self.acc[1:]), L.ptr(self.upd_scratch), sp))
+        L.check(lib.mfvi_elbo_update_guarded_typed(L.ptr(self.params), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi, self.n_bn, 0.0, self.prior_sigma,
+                                                   self.temp, self._klt, self.lr, 0.9, 0.999, 1e-8, L.ptr(self.t_applied), *guard, L.ptr(self.acc[1:]),
+                                                   L.ptr(self.upd_scratch), sp))
         self.step_dev.add_(1)
 
     def enable_graph(self, warmup=3, side_stream=None):
@@ -458,19 +456,18 @@ class ElboEngine:
             self._update_mixture(self._guard() if self.task == TASK_CT else None, self.t - 1, None)
             return
         if self.param_dtype == "bf16":
-            update, kt = self._kl_entry("mfvi_elbo_update_bf16")
-            L.check(update(L.ptr(self.mu), L.ptr(self.rho), L.ptr(self.bn), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi, self.n_bn, 0.0,
-                           self.prior_sigma, self.temp, *kt, self.lr, 0.9, 0.999, 1e-8, self.t, self.seed, L.ptr(self.acc[1:]), L.ptr(self.upd_scratch), sp))
+            L.check(lib.mfvi_elbo_update_bf16_typed(L.ptr(self.mu), L.ptr(self.rho), L.ptr(self.bn), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi,
+                                                    self.n_bn, 0.0, self.prior_sigma, self.temp, self._klt, self.lr, 0.9, 0.999, 1e-8, self.t, self.seed,
+                                                    L.ptr(self.acc[1:]), L.ptr(self.upd_scratch), sp))
             return
         if self.task == TASK_CT:
             # `if not torch.isnan(loss): optimizer.step()` (bayesian_optimization.py:581-582) decided on the device: no host sync
-            update, kt = self._kl_entry("mfvi_elbo_update_guarded")
-            L.check(update(L.ptr(self.params), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi, self.n_bn, 0.0, self.prior_sigma, self.temp, *kt,
-                           self.lr, 0.9, 0.999, 1e-8, L.ptr(self.t_applied), *self._guard(), L.ptr(self.acc[1:]), L.ptr(self.upd_scratch), sp))
+            L.check(lib.mfvi_elbo_update_guarded_typed(L.ptr(self.params), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi, self.n_bn, 0.0,
+                                                       self.prior_sigma, self.temp, self._klt, self.lr, 0.9, 0.999, 1e-8, L.ptr(self.t_applied), *self._guard(),
+                                                       L.ptr(self.acc[1:]), L.ptr(self.upd_scratch), sp))
             return
-        update, kt = self._kl_entry("mfvi_elbo_update")
-        L.check(update(L.ptr(self.params), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi, self.n_bn, 0.0, self.prior_sigma, self.temp, *kt,
-                       self.lr, 0.9, 0.999, 1e-8, self.t, L.ptr(self.acc[1:]), L.ptr(self.upd_scratch), sp))
+        L.check(lib.mfvi_elbo_update_typed(L.ptr(self.params), L.ptr(self.grads), L.ptr(self.m), L.ptr(self.v), self.n_vi, self.n_bn, 0.0, self.prior_sigma, self.temp,
+                                           self._klt, self.lr, 0.9, 0.999, 1e-8, self.t, L.ptr(self.acc[1:]), L.ptr(self.upd_scratch), sp))
 
     def _update_mixture(self, guard, step, step_dev):
         """The fused tail with the Monte-Carlo mixture term.  guard None: update number self.t from the host; else (loss_d, loss_f) of the NaN
@@ -484,12 +481,6 @@ class ElboEngine:
             L.check(lib.mfvi_elbo_update_mixture(*head, self.t, *tail))
         else:
             L.check(lib.mfvi_elbo_update_guarded_mixture(*head, L.ptr(self.t_applied), *guard, *tail))
-
-    def _kl_entry(self, name):
-        """(entry point, its direction argument) of a launch that forms the KL: 'reverse' calls the entry itself, as before the direction
-        existed; 'forward' calls name_typed, which takes MFVI_KL_FORWARD by value behind the scale of the term."""
-        lib = L.lib()
-        return (getattr(lib, name), ()) if self._klt == L.KL_REVERSE else (getattr(lib, name + "_typed"), (self._klt,))
 
     def _guard(self):
         """(loss_d, loss_f) of the NaN guard: the local double accumulator, or the float that rode the all-reduce when K is sharded

@@ -385,8 +385,8 @@ class ElboRowBatch(RowBatch):
     The subclass sets temps, sigmas, lrs (its check_args) and kl_types (check_kl_type) before _allocate."""
     kl_types = None             # per row 'reverse' or 'forward' (DESIGN.md section 25)
     prior_mixtures = None       # per row a checked scale-mixture prior or None (DESIGN.md section 26)
-    _mix_dev = None             # mfvi_mixture_prior[n_rows] on the device once a row has a mixture; none has: nothing, and the update of before
-    _kl_dev = None              # the directions on the device (int32 [n_rows]) once a row is forward; all reverse: nothing, and the untyped update
+    _mix_dev = None             # mfvi_mixture_prior[n_rows] on the device once a row has a mixture; none has: nothing, and the library runs the typed update
+    _kl_dev = None              # the directions on the device (int32 [n_rows]) once a row is forward; all reverse: nothing, and the library runs the untyped update
 
     def _alloc_own(self):
         import numpy as np
@@ -406,21 +406,12 @@ class ElboRowBatch(RowBatch):
             self._mix_dev = torch.frombuffer(bytearray(table), dtype=torch.uint8).cuda()
 
     def _update(self):
-        if self._mix_dev is not None:     # some row has a mixture prior: the same two launches, prior and direction read per row on the device;
-            # row r draws with sample r at counter word t - 1, the iteration just run (what its standalone engine draws with sample 0)
-            L.check(L.lib().mfvi_elbo_update_fits_mixture(L.ptr(self._pbuf), L.ptr(self._grows), L.ptr(self._mbuf), L.ptr(self._vbuf), self.n_vi, self.n_bn,
-                                                          self.stride, self.stride, self.n_rows, L.ptr(self.hyper), L.ptr(self._kl_dev), L.ptr(self._mix_dev),
-                                                          self.seed, 0, self.t - 1, None, 0.9, 0.999, 1e-8, self.t, L.ptr(self.nll_acc), L.ptr(self.dead_dev),
-                                                          L.ptr(self.kl), L.ptr(self.upd_scratch), L.stream_ptr()))
-            return
-        if self._kl_dev is not None:      # some row is forward: the same two launches, the direction read per row on the device
-            L.check(L.lib().mfvi_elbo_update_fits_typed(L.ptr(self._pbuf), L.ptr(self._grows), L.ptr(self._mbuf), L.ptr(self._vbuf), self.n_vi, self.n_bn,
-                                                        self.stride, self.stride, self.n_rows, L.ptr(self.hyper), L.ptr(self._kl_dev), 0.9, 0.999, 1e-8, self.t,
-                                                        L.ptr(self.nll_acc), L.ptr(self.dead_dev), L.ptr(self.kl), L.ptr(self.upd_scratch), L.stream_ptr()))
-            return
-        L.check(L.lib().mfvi_elbo_update_fits(L.ptr(self._pbuf), L.ptr(self._grows), L.ptr(self._mbuf), L.ptr(self._vbuf), self.n_vi, self.n_bn, self.stride,
-                                              self.stride, self.n_rows, L.ptr(self.hyper), 0.9, 0.999, 1e-8, self.t, L.ptr(self.nll_acc), L.ptr(self.dead_dev),
-                                              L.ptr(self.kl), L.ptr(self.upd_scratch), L.stream_ptr()))
+        # one entry for every batch: a NULL prior table is the typed update, a NULL direction table the all-reverse one (the library delegates).
+        # A row on a mixture draws with sample r at counter word t - 1, the iteration just run (what its standalone engine draws with sample 0)
+        L.check(L.lib().mfvi_elbo_update_fits_mixture(L.ptr(self._pbuf), L.ptr(self._grows), L.ptr(self._mbuf), L.ptr(self._vbuf), self.n_vi, self.n_bn,
+                                                      self.stride, self.stride, self.n_rows, L.ptr(self.hyper), L.ptr(self._kl_dev), L.ptr(self._mix_dev),
+                                                      self.seed, 0, self.t - 1, None, 0.9, 0.999, 1e-8, self.t, L.ptr(self.nll_acc), L.ptr(self.dead_dev),
+                                                      L.ptr(self.kl), L.ptr(self.upd_scratch), L.stream_ptr()))
 
     def losses(self):
         """(nll[n_rows], kl[n_rows], loss[n_rows]) of the last step (kl: of the parameters that step started from, in the row's direction) -- forces a device sync.
