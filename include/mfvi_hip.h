@@ -669,6 +669,44 @@ size_t mfvi_tv_term_scratch_bytes(int n_fits, int S, int H, int W);
 int mfvi_tv_term(const float* out, int n_fits, int S, int C, int H, int W, int channel, float beta, const float* weight, int weight_stride,
                  float grad_scale, int accumulate, float* dout, double* tv, void* scratch, void* stream);
 
+/* ---- signal-to-noise pruning of the fitted posterior (BayTorch/inference/utils.py:104-166 L1UnstructuredFFG / prune_weights_ffg, the SNR
+ * histograms of BayTorch/visualize) --------------------------------------------------------------------------------- */
+/* Parameter rows are laid out [MU n_vi | RHO n_vi | ...], row r `stride` floats behind row r - 1 (one engine: rows = 1).  Everything below
+ * works on the float32 keys key[r][j] = |mu| / softplus(rho) in the total order "unsigned compare of bits(key) & 0x7fffffff, ties by
+ * ascending j": the order of the floats with NaN (0 / 0, or a NaN parameter) above +inf, which is the order of a stable argsort of the
+ * reference's log(snr) (inference/utils.py:116-123, 139-142).  Group 0 = the convolution weights, group 1 = the biases: the reference ranks them in
+ * separate calls (inference/utils.py:159-166).  Membership comes from a DEVICE table of segments sorted by offset; an element in no segment,
+ * or in a segment of another group number, is never pruned.  rows in 1..65535; n_vi >= 2^31 is refused (-2).  Integer atomics only and no
+ * host round-trip: results are bit-identical from call to call. */
+#define MFVI_PRUNE_GROUPS 2
+#define MFVI_PRUNE_MAX_SEGMENTS 512
+#define MFVI_SNR_MAX_BINS 510
+typedef struct { int64_t offset; int64_t count; int32_t group; int32_t pad; } mfvi_prune_segment;
+/* keys [rows][n_vi] (dense) = fabsf(mu) / softplus(rho), softplus as torch's (threshold 20), one IEEE division (inference/utils.py:116-118
+ * ranks by log(|mu| / softplus(rho)), the same order).  -1 for null pointers, rows outside 1..65535 or stride < 2 n_vi. */
+int mfvi_snr_keys(const float* params, int rows, int64_t stride, int64_t n_vi, float* keys, void* stream);
+/* bytes of the scratch region of mfvi_snr_select (8-byte aligned); -1 for rows outside 1..65535 */
+int64_t mfvi_snr_select_scratch_bytes(int rows);
+/* Per row r and group g: mask[r][j] = 0 for the k[r][g] smallest keys of the group in the order above (the reference's
+ * mask[argsort(log snr)[:int(amount * n)]] = 0, inference/utils.py:120-123, 139-142), 1 for every other j < n_vi.  k: int64 [rows][2] on the DEVICE, clamped there
+ * to 0..the group's size.  threshold[r][g] = bits of the largest pruned key and ties[r][g] = the number of pruned keys equal to it (those of
+ * the lowest indices); both 0 where nothing is pruned.  An MSB-first radix select (four digits, LDS histograms, integer atomics), then a
+ * count of the threshold's tie class per block and a fixed-order prefix over blocks: 11 small launches on `stream` whatever rows is.
+ * -2 for n_vi or n_seg (0..MFVI_PRUNE_MAX_SEGMENTS) out of range, -1 for null pointers, a misaligned scratch or rows outside 1..65535. */
+int mfvi_snr_select(const float* keys, int rows, int64_t n_vi, const mfvi_prune_segment* segs, int n_seg, const int64_t* k, uint8_t* mask,
+                    uint32_t* threshold, int64_t* ties, void* scratch, void* stream);
+/* dst rows = src rows over row_floats floats each (2 n_vi <= row_floats <= stride: the BN tail included), except mu = +0 and
+ * rho = -200 (MFVI_PRUNED_RHO of csrc/common.h: softplus(-200) is exactly +0 in every kernel of the library) where mask[r][j] == 0.  The
+ * reference multiplies rho by the mask instead (W_rho is pruned like W_mu, inference/utils.py:159-166), leaving sigma = softplus(0) = 0.69 on a "pruned" weight.
+ * src is only read; dst == src is refused (-1). */
+int mfvi_prune_apply(const float* src, float* dst, const uint8_t* mask, int rows, int64_t stride, int64_t n_vi, int64_t row_floats, void* stream);
+/* counts [rows][2][n_bins + 2] (int64, overwritten): per row and group the keys per bin of the n_bins + 1 non-decreasing DEVICE floats
+ * bounds[] in key space -- slot s holds the keys with exactly s boundaries <= key (numpy.searchsorted(bounds, key, 'right')): slot 0 is the
+ * underflow, slot n_bins + 1 the overflow, where NaN keys count too.  Comparisons only, as mfvi_uce_bins.  -2 for n_bins outside
+ * 1..MFVI_SNR_MAX_BINS. */
+int mfvi_snr_histogram(const float* keys, int rows, int64_t n_vi, const mfvi_prune_segment* segs, int n_seg, const float* bounds, int n_bins,
+                       int64_t* counts, void* stream);
+
 const char* mfvi_last_error(void);
 int mfvi_abi_version(void);
 

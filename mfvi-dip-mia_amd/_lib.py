@@ -33,6 +33,15 @@ class MixturePrior(C.Structure):
     _fields_ = [("n", C.c_int32), ("pi", C.c_float * MIXTURE_MAX), ("mu", C.c_float * MIXTURE_MAX), ("sigma", C.c_float * MIXTURE_MAX)]
 
 
+PRUNE_GROUPS, PRUNE_MAX_SEGMENTS, SNR_MAX_BINS = 2, 512, 510               # MFVI_PRUNE_GROUPS, MFVI_PRUNE_MAX_SEGMENTS, MFVI_SNR_MAX_BINS
+PRUNED_RHO = -200.0                                                       # MFVI_PRUNED_RHO (csrc/common.h): softplus of it is exactly +0
+
+
+class PruneSegment(C.Structure):
+    """mfvi_prune_segment: `count` elements from `offset` on belong to group 0 (weights) or 1 (biases)."""
+    _fields_ = [("offset", C.c_int64), ("count", C.c_int64), ("group", C.c_int32), ("pad", C.c_int32)]
+
+
 class MfviError(RuntimeError):
     pass
 
@@ -146,6 +155,11 @@ SIGNATURES = {
     "mfvi_pair_metrics": (_I, [_P, _I64, _P, _I64, _I, _I, _I, _I, _P, _P, _I64, _P]),
     "mfvi_tv_term_scratch_bytes": (C.c_size_t, [_I, _I, _I, _I]),
     "mfvi_tv_term": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _P, _I, _F, _I, _P, _P, _P, _P]),
+    "mfvi_snr_keys": (_I, [_P, _I, _I64, _I64, _P, _P]),
+    "mfvi_snr_select_scratch_bytes": (_I64, [_I]),
+    "mfvi_snr_select": (_I, [_P, _I, _I64, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "mfvi_prune_apply": (_I, [_P, _P, _P, _I, _I64, _I64, _I64, _P]),
+    "mfvi_snr_histogram": (_I, [_P, _I, _I64, _P, _I, _P, _I, _P, _P]),
     "mfvi_last_error": (C.c_char_p, []),
     "mfvi_abi_version": (_I, []),
 }

@@ -8,11 +8,11 @@ from . import runner
 from .nets import Concat, get_net, skip
 
 __all__ = ["build", "FitBatch", "Plan", "Program", "skip_program", "_lib", "engine", "sharding", "runner", "Concat", "get_net", "skip", "MeanFieldVI", "FusedNet", "Conv2dRT", "Conv2dLRT",
-           "gaussian_nll", "gaussian_nll_inpainting", "uncert_regression_gal", "uceloss", "Downsampler", "lanczos_taps", "FastRadonTransform", "CtVolume", "InpaintBatch", "SiblingBatch", "BatchBook", "tv_loss"]
+           "gaussian_nll", "gaussian_nll_inpainting", "uncert_regression_gal", "uceloss", "Downsampler", "lanczos_taps", "FastRadonTransform", "CtVolume", "InpaintBatch", "SiblingBatch", "BatchBook", "tv_loss", "prune_weights_ffg", "prune_remove"]
 
 
 def __getattr__(name):          # bayes.py needs torch.nn at import: keep `import mfvi_dip_mia_amd` light
-    if name in ("MeanFieldVI", "FusedNet", "Conv2dRT", "Conv2dLRT", "gaussian_nll", "gaussian_nll_inpainting", "uncert_regression_gal"):
+    if name in ("MeanFieldVI", "FusedNet", "Conv2dRT", "Conv2dLRT", "gaussian_nll", "gaussian_nll_inpainting", "uncert_regression_gal", "prune_weights_ffg", "prune_remove"):
         from . import bayes
         return getattr(bayes, name)
     if name == "uceloss":

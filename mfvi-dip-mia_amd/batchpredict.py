@@ -98,7 +98,7 @@ def _group_plan(owner, G, S):
     return cache[(G, S)]
 
 
-def predict_fits(owner, n_samples, target=None, clip=False, step=None, chunk=None, fits_per_call=None, calibration=None):
+def predict_fits(owner, n_samples, target=None, clip=False, step=None, chunk=None, fits_per_call=None, calibration=None, pbuf=None):
     """N posterior draws of EVERY fit of the batch, reduced on the device ->
         dict(mean [F,Cimg,H,W], epi, ale | None, total, err2 | None, mse_mc | None [F,H,W], psnr_mean [F] | None, dead [F], n, step)
     fit f's maps being those of owner.to_engine(f).predict(n_samples, ...) up to the order of the convolutions' sums: the same global
@@ -107,6 +107,7 @@ def predict_fits(owner, n_samples, target=None, clip=False, step=None, chunk=Non
     mse_mc and psnr_mean = 10 log10(1 / mean err2).  chunk: samples per fit and call (default max(1, min(N, 64 // G)));
     fits_per_call: G (default every fit; CtVolume: its slices per launch).  A dead fit is predicted from its frozen parameters and
     flagged in `dead`.  calibration: True or dict(n_bins, range) adds r["calibration"], one Calibration per fit.
+    pbuf: parameter rows [F, stride] to predict from in place of the batch's own (RowBatch.predict(prune=): the pruned clone).
     Leaves the training plan, out, the parameters, the moments and the counters untouched."""
     import numpy as np
     N, S, G, step, cal, kind = check_args(owner, n_samples, target, step, chunk, fits_per_call, calibration)
@@ -134,7 +135,7 @@ def predict_fits(owner, n_samples, target=None, clip=False, step=None, chunk=Non
         if ps is not None and group != (g0, Gn):      # a host array copied by the call: once per group
             plan.set_fit_dropout(ps[g0:g0 + Gn])
         group = (g0, Gn)
-        p = owner._pbuf[g0]
+        p = (owner._pbuf if pbuf is None else pbuf)[g0]
         plan.forward(p[:nv], p[nv:], p[2 * nv:], owner.z0[g0:g0 + Gn], owner.seed, step, c * S, Gn * S, sample_weights, out[:Gn * S])
         L.check(lib.mfvi_predictive_accumulate_fits(L.ptr(out), Gn, S, n_use, C, H, W, code, int(bool(clip)), int(c == 0), L.ptr(acc[g0]), acc_stride, sp))
     maps = torch.empty((cimg + 5) * F * HW, dtype=torch.float32, device="cuda")

@@ -433,7 +433,9 @@ class MeanFieldVI(nn.Module):
     def kl(self, eps=None):
         """Sum of the layers' KL terms (kl_type 'reverse': KL(prior || posterior), else KL(posterior || prior)) as a tensor of shape [1]
         (freq_to_bayes.py:43-48).  With a scale-mixture prior: the one-draw Monte-Carlo estimate, a fresh draw per call; eps (mixture
-        only): n_vi normals in the flat block's order (layer after layer, W | bias) to use instead of the draw."""
+        only): n_vi normals in the flat block's order (layer after layer, W | bias) to use instead of the draw.
+        Raises while the net is pruned (prune_weights_ffg): the KL term of a zero-variance weight is infinite."""
+        self._refuse_pruned("net.kl()")
         m = self._vi[0]
         if eps is not None and self._mix is None:
             raise ValueError("eps is the draw of the Monte-Carlo KL term of a scale-mixture prior; this net's KL term is closed-form")
@@ -452,7 +454,13 @@ class MeanFieldVI(nn.Module):
         vi_params = [p for q in self._vi for p in ([q.W_mu, q.W_rho] + ([q.bias_mu, q.bias_rho] if q._has_bias else []))]
         return _KLFunction.apply(self, 0, self.n_vi, m.prior_mu, m.prior_sigma, *vi_params)
 
+    def _refuse_pruned(self, what):
+        if getattr(self, "_pruned", None) is not None:
+            raise RuntimeError("%s on a pruned net: a pruned weight has zero variance, its KL term is infinite, and training under a mask is "
+                               "not built; call prune_remove(net) first" % what)
+
     def _layer_kl(self, m):
+        self._refuse_pruned("a layer's _kl")
         hi = (m._b_off + m.out_channels) if m._has_bias else m._w_off + m.W_mu.numel()
         if self._mix is not None:      # the layer's slice of the flat block's stream, at a fresh counter value
             return self._hip_kl_mix(m._w_off, hi, self._next_kl_step())[0]
@@ -818,6 +826,67 @@ class _GaussianNLL(torch.autograd.Function):
         L.check(L.lib().mfvi_gaussian_nll_tensors_backward(L.ptr(mu_c), L.ptr(s_c), L.ptr(t_c), L.ptr(m_c), C, Cs, Cm, hw, mean,
                                                            L.ptr(g.reshape(1).contiguous().float()), L.ptr(dmu), L.ptr(ds), L.stream_ptr()))
         return dmu.view(mu_shape), ds.view(s_shape), None, None, None
+
+
+def _vi_spans(net):
+    """Per Bayesian layer [(offset, count, group)] in the flat block: the weights (group 0) and, where the layer has one, the bias (group 1)."""
+    return [[(m._w_off, m.W_mu.numel(), 0)] + ([(m._b_off, m.out_channels, 1)] if m._has_bias else []) for m in net._vi]
+
+
+def prune_weights_ffg(net, mode='percentage', thresh=0., amount=0.):
+    """BayTorch/inference/utils.py:156-166 for a MeanFieldVI: global percentage pruning by signal-to-noise ratio |mu| / softplus(rho)
+    (L1UnstructuredFFG, :104-142).  The int(amount * n) lowest-SNR weights of all layers' W and, ranked separately as the reference's
+    separate W_* / bias_* calls rank them, of all layers' biases are pruned IN PLACE in the flat buffer (flat-parameter mode included); the
+    selection is the exact k-th-smallest select of csrc/prune.hip in the order of a stable argsort of the reference's log(snr).  The
+    originals are kept for prune_remove(net).  Every layer gets the plain tensor attributes W_mu_mask, W_rho_mask (and bias_mu_mask,
+    bias_rho_mask where it has a bias): float32, 1 = kept, the reference's masks -- not registered buffers, so the state_dict keys stay
+    the reference's.  Returns dict(amount, k, n, threshold, ties, layer_sparsity, layer_pruned, mask).
+    Two deviations from the reference: (1) a pruned weight gets mu = 0 and sigma = 0 exactly (rho = -200); the
+    reference multiplies W_rho by the mask, which sets rho = 0, i.e. sigma = softplus(0) = 0.69, larger than any fitted sigma;
+    (2) a layer without a bias is served; the reference crashes on it (bias_mu is None).
+    mode='threshold' raises NotImplementedError: the reference's ThresholdPruning stops in pdb.set_trace().  While a net is pruned,
+    net.kl() raises, and a second prune_weights_ffg is refused (the reference's second pass takes log(0))."""
+    if isinstance(net, FusedNet) or not isinstance(net, MeanFieldVI):
+        raise TypeError("prune_weights_ffg takes a MeanFieldVI (a posterior N(mu, softplus(rho)^2)); %s has no rho to rank by" % type(net).__name__)
+    if mode == 'threshold':
+        raise NotImplementedError("mode='threshold' is not built: the reference's ThresholdPruning stops in pdb.set_trace()")
+    if mode != 'percentage':
+        raise ValueError("mode=%r: 'percentage'" % (mode,))
+    from . import prune as P
+    a = P.check_amount(amount, name="amount")
+    if getattr(net, "_pruned", None) is not None:
+        raise RuntimeError("the net is already pruned: call prune_remove(net) first")
+    net._blocks()                                            # (re-establishes the flat layout if parameter storage was replaced)
+    flat = net._flat
+    sel = P.SnrSelect(torch, _vi_spans(net), net.n_vi, 1, flat.numel(), flat.numel())
+    ks = sel.select(flat, [a])
+    pruned = sel.apply(flat)
+    info = sel.info(ks, [a])[0]
+    net._pruned = dict(orig=flat.clone(), info=info)
+    with torch.no_grad():
+        flat.copy_(pruned)                                   # in place: every Parameter (and the flat Parameter) is a view of it
+    mask = info["mask"].to(torch.float32)
+    for m in net._vi:
+        w = mask[m._w_off:m._w_off + m.W_mu.numel()].view_as(m.W_mu)
+        m.W_mu_mask, m.W_rho_mask = w, w
+        if m._has_bias:
+            b = mask[m._b_off:m._b_off + m.out_channels]
+            m.bias_mu_mask, m.bias_rho_mask = b, b
+    return info
+
+
+def prune_remove(net):
+    """Undo prune_weights_ffg: the flat buffer gets its values from before the call back, bit for bit, and the mask attributes go."""
+    st = getattr(net, "_pruned", None)
+    if st is None:
+        raise RuntimeError("the net is not pruned")
+    with torch.no_grad():
+        net._flat.copy_(st["orig"])
+    for m in net._vi:
+        for k in ("W_mu_mask", "W_rho_mask", "bias_mu_mask", "bias_rho_mask"):
+            if k in m.__dict__:
+                del m.__dict__[k]
+    net._pruned = None
 
 
 def uncert_regression_gal(img_list, reduction='mean'):

@@ -201,6 +201,10 @@ __device__ __forceinline__ float softplus_fast(float x)
     return __logf(1.f + e);
 }
 
+// rho of a pruned weight (prune.hip): finite, and far enough down that expf underflows to +0, so softplus_f, softplus_fast
+// and the local-reparameterisation variance softplus(rho)^2 all return exactly +0 -- a pruned weight samples as exactly 0 with zero variance
+#define MFVI_PRUNED_RHO (-200.f)
+
 // ------------------------------------------------------------------------------------------------
 // Tensor views
 // ------------------------------------------------------------------------------------------------

@@ -193,7 +193,33 @@ class ElboEngine:
             self._pred_plans[chunk] = (plan, out)
         return self._pred_plans[chunk]
 
-    def predict(self, n_samples, target=None, clip=False, step=None, chunk=None, z=None, calibration=None):
+    def _snr_select(self):
+        """The engine's SnrSelect (prune.py), allocated on first use; refuses what SNR pruning does not serve before the library is touched."""
+        from . import prune as P
+        P.check_engine(self)
+        return P.owner_select(self, 1, self.n_params, self.n_params)
+
+    def snr(self):
+        """float32 [n_vi] on the device: |mu| / softplus(rho) of the current posterior."""
+        return self._snr_select().compute_keys(self.params)[0]
+
+    def prune_mask(self, amount):
+        """The global SNR selection of BayTorch/inference/utils.py:104-166 for the current posterior, without applying it: the
+        int(amount * n) lowest-SNR convolution weights and, separately, biases -> dict(mask uint8 [n_vi] on the device (0 = pruned), amount,
+        k [2], n [2], threshold [2] (the largest pruned SNR per group), ties [2], layer_sparsity [n_layers], layer_pruned [n_layers])."""
+        from . import prune as P
+        a = P.check_amount(amount)
+        sel = self._snr_select()
+        return sel.info(sel.select(self.params, [a]), [a])[0]
+
+    def _pruned_params(self, amount):
+        """(mu, rho, bn) views of a pruned COPY of the parameters, and the prune_mask dict without its mask."""
+        sel = self._snr_select()
+        ks = sel.select(self.params, [amount])
+        p, nv = sel.apply(self.params), self.n_vi
+        return (p[:nv], p[nv:2 * nv], p[2 * nv:self.n_params]), sel.info(ks, [amount], with_mask=False)[0]
+
+    def predict(self, n_samples, target=None, clip=False, step=None, chunk=None, z=None, calibration=None, prune=None):
         """Posterior predictive sampling (BayTorch/inference/utils.py:11-24 uncert_regression_gal over N draws of the fit, DESIGN.md
         section 11): N forwards y_k = net_k(z) with the current mu / rho / BN, eps keyed by the GLOBAL sample index k at RNG step
         `step` (default 2**31: no training iteration's draw is reused), reduced on the device into
@@ -205,8 +231,16 @@ class ElboEngine:
         state (params, Adam moments, counters, self.out) untouched.
         calibration: True, or dict(n_bins=15, range=None): adds r["calibration"], the per-bin calibration statistics of the returned
         mse_mc map against the returned total map (calibration.calibration; needs target; every rank computes it
-        from the all-reduced maps, no further communication)."""
+        from the all-reduced maps, no further communication).
+        prune: a share in [0, 1]: the prediction runs on a pruned COPY of mu / rho / BN (prune_mask(prune) applied: the selected weights are
+        exactly 0 with zero variance) and r["prune"] holds the prune_mask dict without its mask; the fit itself stays untouched.  None or
+        0: no pruning code runs."""
         from .predictive import Accumulator, DEFAULT_STEP
+        if prune is not None:
+            from .prune import check_amount, check_engine
+            prune = check_amount(prune)
+            if prune:
+                check_engine(self)
         torch = self.torch
         N = int(n_samples)
         cal = None
@@ -231,15 +265,18 @@ class ElboEngine:
         mode = {TASK_CT: "mean_only", TASK_INP: "inp"}.get(self.task, "logprec")
         plan, out = self._pred_plan(chunk)
         acc = Accumulator(out.shape[1], self.H, self.W, mode)
+        (mu, rho, bn), pruned = ((self.mu, self.rho, self.bn), None) if not prune else self._pruned_params(prune)
         for c0 in range(0, n_local, chunk):
             n = min(chunk, n_local - c0)
-            plan.forward(self.mu, self.rho, self.bn, zin, self.seed, step, k0 + c0, n, self.sample_weights, out)
+            plan.forward(mu, rho, bn, zin, self.seed, step, k0 + c0, n, self.sample_weights, out)
             acc.add(out, n, clip)
         if self.world > 1:
             allreduce_sum_(acc.state, self.pg)
         r = acc.finalize(N, target)
         r.pop("sums")
         r.update(n=N, step=step)
+        if pruned is not None:
+            r["prune"] = pruned
         if cal is not None:
             from .calibration import calibration as _calibration
             r["calibration"] = _calibration(r["mse_mc"], r["total"], n_bins=cal.get("n_bins", 15), range=cal.get("range"))

@@ -360,11 +360,44 @@ class RowBatch:
         with np.errstate(divide="ignore"):
             return 10.0 * np.log10(1.0 / mse)
 
-    def predict(self, n_samples, target=None, clip=False, step=None, chunk=None, fits_per_call=None, calibration=None):
+    def _snr_select(self):
+        """The batch's SnrSelect over all rows (prune.py), allocated on first use; the point-weight siblings are refused before the library is touched."""
+        from . import prune as P
+        P.check_batch(self)
+        return P.owner_select(self, self.n_rows, self.stride, self.n_params)
+
+    def snr(self):
+        """float32 [n_rows, n_vi] on the device: |mu| / softplus(rho) of every row's posterior, one launch."""
+        return self._snr_select().compute_keys(self._pbuf)
+
+    def prune_mask(self, amount):
+        """Per row what ElboEngine.prune_mask returns (a list of n_rows dicts), the selection of all rows in one set of launches.  amount: a
+        share in [0, 1], or one per row."""
+        from . import prune as P
+        P.check_batch(self)
+        a = P.check_amount(amount, self.n_rows)
+        sel = self._snr_select()
+        return sel.info(sel.select(self._pbuf, a), a)
+
+    def predict(self, n_samples, target=None, clip=False, step=None, chunk=None, fits_per_call=None, calibration=None, prune=None):
         """Posterior predictive maps of every row at once (batchpredict.predict_fits): per row what
-        to_engine(f).predict(n_samples, ...) returns, stacked, from one set of launches per chunk of draws instead of one chain per row."""
+        to_engine(f).predict(n_samples, ...) returns, stacked, from one set of launches per chunk of draws instead of one chain per row.
+        prune: a share in [0, 1] or one per row: keys, selection and the pruned clone of ALL rows in one set of launches, the prediction
+        reads the clone, r["prune"] is the list of per-row prune_mask dicts without their masks; _pbuf is untouched.  None, 0 or all 0:
+        no pruning code runs."""
         from .batchpredict import predict_fits
-        return predict_fits(self, n_samples, target=target, clip=clip, step=step, chunk=chunk, fits_per_call=fits_per_call, calibration=calibration)
+        pbuf = info = None
+        if prune is not None:
+            from . import prune as P
+            a = P.check_amount(prune, self.n_rows)
+            if any(a):
+                sel = self._snr_select()
+                ks = sel.select(self._pbuf, a)
+                pbuf, info = sel.apply(self._pbuf).view(self.n_rows, self.stride), sel.info(ks, a, with_mask=False)
+        r = predict_fits(self, n_samples, target=target, clip=clip, step=step, chunk=chunk, fits_per_call=fits_per_call, calibration=calibration, pbuf=pbuf)
+        if info is not None:
+            r["prune"] = info
+        return r
 
     def to_engine(self, f, autotune=False):
         """The standalone engine of the class holding copies of row f's parameters, Adam moments, step count, input and target: predict(),

@@ -204,8 +204,53 @@ def _predict(eng, n, gt, run_dir, drop_ale=False, calibration_bins=0):
     return arrs
 
 
+def parse_prune_amounts(text):
+    """'0,0.5,0.9' -> [0.0, 0.5, 0.9] (ValueError for anything that is not a list of numbers)."""
+    return [float(x) for x in str(text).split(",") if x.strip() != ""]
+
+
+def _check_prune(method, predict_samples, prune_amounts):
+    """The shares of --prune-amounts / run_params.prune_amounts, checked without the library -> list of floats, or None (off)."""
+    if prune_amounts is None or len(prune_amounts) == 0:
+        return None
+    if method != "mfvi":
+        raise ValueError("prune_amounts: SNR pruning ranks the posterior of mean-field VI (mfvi), not %r" % (method,))
+    if not predict_samples:
+        raise ValueError("prune_amounts: the pruned posterior is evaluated by its predictive maps (predict_samples >= 2)")
+    from .prune import check_amount
+    return [check_amount(a, name="prune_amounts") for a in prune_amounts]
+
+
+def _pruning(eng, n, gt, run_dir, amounts):
+    """After the last iteration: per share of `amounts` eng.predict(n, target=gt, prune=share) -> pruning.npz in the
+    run directory (when saving): what was pruned, per-layer sparsity, the PSNR and mean uncertainties of the pruned posterior's predictive
+    maps, and the histogram of log10(snr) of the unpruned posterior per group (weights, biases).  Returns the arrays."""
+    import torch
+    from . import prune as P
+    target = torch.from_numpy(np.ascontiguousarray(gt, np.float32))
+    infos, stats = [], []
+    for a in amounts:
+        r = eng.predict(n, target=target, prune=a)
+        infos.append(r["prune"] if "prune" in r else {k: v for k, v in eng.prune_mask(a).items() if k != "mask"})
+        with np.errstate(divide="ignore"):
+            psnr = 10.0 * np.log10(1.0 / float(r["err2"].double().mean()))
+        stats.append([psnr, float(r["epi"].double().mean()), float(r["ale"].double().mean()) if r["ale"] is not None else np.nan,
+                      float(r["total"].double().mean())])
+    sel = eng._snr_select()
+    sel.compute_keys(eng.params)
+    counts, edges = P.snr_histogram(sel)
+    stats = np.asarray(stats, np.float64)
+    arrs = dict(amount=np.asarray(amounts, np.float64), n_pruned=np.stack([i["k"] for i in infos]), n=infos[0]["n"],
+                snr_threshold=np.stack([i["threshold"] for i in infos]), layer_sparsity=np.stack([i["layer_sparsity"] for i in infos]),
+                layer_names=np.array(P.layer_names(eng.prog)), psnr_mean=stats[:, 0], epi_mean=stats[:, 1], ale_mean=stats[:, 2], total_mean=stats[:, 3],
+                snr_hist_counts=counts[0], snr_hist_edges_log10=edges)
+    if run_dir is not None:
+        np.savez(os.path.join(run_dir, "pruning.npz"), **arrs)
+    return arrs
+
+
 def _fit(task, method, fields, prepare, num_iter, show_every, plot, save, save_path, verbose=False, predict_samples=0, calibration=False,
-         calibration_bins=15, downsampler="nearest", factor=4):
+         calibration_bins=15, downsampler="nearest", factor=4, prune_amounts=None):
     """The loop of every single-fit runner: the refusals; the run directory and the head of locals.txt (`fields`), written
     before anything is loaded; `prepare(n_it)` -> (ground truth, engine with its target set, book, the two head arrays of save.npz, mask or
     None, channel count of recons / uncerts); the iterations with a snapshot every show_every; predictive.npz and calibration.npz; save.npz,
@@ -214,6 +259,7 @@ def _fit(task, method, fields, prepare, num_iter, show_every, plot, save, save_p
     _check_downsampler(task, method, downsampler, factor)
     _check_predict(method, predict_samples)
     _check_calibration(method, calibration, calibration_bins)
+    prune_amounts = _check_prune(method, predict_samples, prune_amounts)
     run_dir = os.path.join(save_path, str(time.time()))
     if save:
         os.makedirs(run_dir, exist_ok=False)
@@ -244,6 +290,7 @@ def _fit(task, method, fields, prepare, num_iter, show_every, plot, save, save_p
                     calibration_bins=calibration_bins if calibration else 0) if predict_samples else None
     cal = _calibrate(run_dir if save else None, gt, recons, uncerts_epi, uncerts_ale, pred.pop("_calibration") if pred else None,
                      calibration_bins, mask=mask) if calibration else None
+    pruning = _pruning(eng, predict_samples, gt, run_dir if save else None, prune_amounts) if prune_amounts else None
     torch.cuda.synchronize()
     mse_corrupted, mse_gt, psnrs, ssims = book.results()
     if save:
@@ -262,12 +309,15 @@ def _fit(task, method, fields, prepare, num_iter, show_every, plot, save, save_p
         res["predictive"] = pred
     if cal is not None:
         res["calibration"] = cal
+    if pruning is not None:
+        res["pruning"] = pruning
     return res
 
 
 def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, seed, show_every, plot, save, save_path, K, factor=4,
          theta_step=4.0, verbose=False, net_kwargs=None, method="mfvi", weight_decay=0.0, dropout_p=0.3, gamma=0.996, param_dtype="f32", predict_samples=0,
-         calibration=False, calibration_bins=15, downsampler="nearest", tv_weight=0.0, tv_beta=0.5, kl_type="reverse", prior_mixture=None, **unused):
+         calibration=False, calibration_bins=15, downsampler="nearest", tv_weight=0.0, tv_beta=0.5, kl_type="reverse", prior_mixture=None, prune_amounts=None,
+         **unused):
     """What _fit needs of a den / sr / ct run: its locals.txt fields and, once the run directory stands, the image, the task's target and engine,
     the _Book and the two head arrays as the reference writes them per task: den img_gt / img_noisy (:1438), sr img_hr / img_lr (:2258), ct
     img_gt / img_radon (:643) with the reference's shapes (get_image() arrays are (1, H, W), img_lr is squeezed, the CT tensors keep
@@ -279,7 +329,10 @@ def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, see
                                                                   "sgld": dict(gamma=gamma, weight_decay=weight_decay)}.get(method, {})
     fields = dict(task=task, method=method, img=img if not isinstance(img, np.ndarray) else "<array>", imsize=imsize, p_sigma=p_sigma,
                   num_iter=num_iter, lr=lr, input_depth=input_depth, seed=seed, show_every=show_every, K=K, save_path=save_path,
-                  **(dict(downsampler=downsampler) if task == "sr" else {}), **hyper, **tv)
+                  **(dict(downsampler=downsampler) if task == "sr" else {}), **hyper, **tv,
+                  **(dict(prune_amounts=list(prune_amounts)) if prune_amounts else {}))
+    if prune_amounts and param_dtype == "bf16":
+        raise NotImplementedError("prune_amounts with param_dtype='bf16' is not built: the pruning kernels read float32 parameter rows")
 
     def prepare(n_it):
         import torch
@@ -312,7 +365,7 @@ def _run(task, img, imsize, p_sigma, num_iter, lr, temp, sigma, input_depth, see
         eng.set_target(torch.from_numpy(target) if isinstance(target, np.ndarray) else target)
         return img_np, eng, _Book(eng, n_it, img_np, noisy, task=task, factor=factor, downsampler=downsampler), head, None, 1
     return _fit(task, method, fields, prepare, num_iter, show_every, plot, save, save_path, verbose, predict_samples, calibration, calibration_bins,
-                downsampler, factor)
+                downsampler, factor, prune_amounts=prune_amounts)
 
 
 def run_den_mfvi(img="phantom", imsize=(256, 256), p_sigma=0.1, num_iter=5000, lr=3e-4, temp=4e-6, sigma=0.01, input_depth=16, seed=42,
@@ -380,7 +433,8 @@ def scratch_mask(H, W, seed):
 
 def run_inp_mfvi(img="phantom", mask=None, imsize=(256, 256), num_iter=5000, lr=2e-3, temp=4e-6, sigma=0.01, input_depth=32, seed=42,
                  show_every=100, plot=False, save=True, save_path="../logs", K=1, net_kwargs=None, verbose=False, method="mfvi",
-                 weight_decay=1e-4, dropout_p=0.2, gamma=0.996, predict_samples=0, calibration=False, calibration_bins=15, kl_type="reverse", prior_mixture=None, **unused):
+                 weight_decay=1e-4, dropout_p=0.2, gamma=0.996, predict_samples=0, calibration=False, calibration_bins=15, kl_type="reverse", prior_mixture=None, prune_amounts=None,
+                 **unused):
     """bayesian_optimization.py:2892-3114: inpainting with the 6-scale no-skip net (5x5 down filters, nearest up-sampling), sigmoid on
     the colour channels, masked Gaussian NLL.  img: (3, H, W) array in [0, 1] or 'phantom' (three synthetic planes); mask: (1|3, H, W),
     1 = known pixel (the reference ships its masks in data/inpainting/).  save.npz carries the reference's keys for this task
@@ -405,7 +459,7 @@ def run_inp_mfvi(img="phantom", mask=None, imsize=(256, 256), num_iter=5000, lr=
         eng.set_target(torch.from_numpy(img_np), torch.from_numpy(mask_np))
         return img_np, eng, _BookInp(eng, n_it, img_np, mask_np), (img_np, mask_np), mask_np, 3
     return _fit("inp", method, fields, prepare, num_iter, show_every, plot, save, save_path, verbose, predict_samples, calibration, calibration_bins,
-                unused.get("downsampler", "nearest"))
+                unused.get("downsampler", "nearest"), prune_amounts=prune_amounts)
 
 
 run_inp_dip = _sibling("inp", "dip", dict(input_depth=32, lr=2e-3))
@@ -838,6 +892,20 @@ def _check_cli(ap, a):
             check_prior_mixture(parse_prior_mixture(a.prior_mixture), "--prior-mixture")
         except ValueError as e:
             ap.error("--prior-mixture %s: %s" % (a.prior_mixture, e))
+    # SNR pruning of the fitted posterior, behind every older check
+    if a.prune_amounts is not None:
+        if a.bayes != "mfvi":
+            ap.error("--prune-amounts ranks the posterior of mean-field VI (--bayes mfvi); %s has no rho" % a.bayes)
+        if not a.predict_samples:
+            ap.error("--prune-amounts evaluates the pruned posterior by its predictive maps: it needs --predict-samples N (N >= 2)")
+        if a.fits_per_launch or a.inpaint_fits or a.sibling_fits or a.ct_volume is not None:
+            ap.error("--prune-amounts serves a single fit; for a batch call batch.predict(N, prune=...) (the batch drivers write no pruning file)")
+        if a.param_dtype == "bf16":
+            ap.error("--prune-amounts does not combine with --param-dtype bf16 (the pruning kernels read float32 parameter rows)")
+        try:
+            _check_prune(a.bayes, a.predict_samples, parse_prune_amounts(a.prune_amounts))
+        except ValueError as e:
+            ap.error("--prune-amounts %s: %s" % (a.prune_amounts, e))
 
 
 def main(argv=None):
@@ -897,6 +965,10 @@ def main(argv=None):
                     help="--bayes mfvi with --kl-type forward: a scale mixture of 1 to 4 Gaussians as the prior of every weight, one PI:SIGMA[:MU] "
                          "per component (1e-6 is added to SIGMA; MU defaults to 0); the KL term becomes the one-draw Monte-Carlo estimate of "
                          "KL(posterior || mixture) (default: the config's run_params.prior_mixture, else the Gaussian prior)")
+    ap.add_argument("--prune-amounts", default=None, metavar="A,B,...",
+                    help="--bayes mfvi with --predict-samples N: after the fit, prune the given shares of the posterior's weights by signal-to-noise "
+                         "ratio |mu| / sigma (a pruned COPY; the fit is untouched), evaluate the predictive maps under each and write pruning.npz "
+                         "(default: the config's run_params.prune_amounts, else off)")
     a = ap.parse_args(argv)
     _check_cli(ap, a)
     cands, rp, cfg_devices = load_config(a.config, a.bayes, with_devices=True)
@@ -936,6 +1008,8 @@ def main(argv=None):
         rp["kl_type"] = a.kl_type
     if a.prior_mixture is not None:
         rp["prior_mixture"] = parse_prior_mixture(a.prior_mixture)
+    if a.prune_amounts is not None:
+        rp["prune_amounts"] = parse_prune_amounts(a.prune_amounts)
     if a.ct_volume is not None:      # one volume fit per candidate of the config
         from .fanout import print_table
         vrp = {k: v for k, v in rp.items() if k not in ("img", "plot", "p_sigma")}
