@@ -35,7 +35,6 @@
  *      MFVI_PHASE=0            stride-2 backward-data: zero-stuffed formulation instead of the phase decomposition
  *      MFVI_FOLD_FUSION=0      1x1 backward-data writes the padded gradient + a finalize_dx launch (fold not fused)
  *      MFVI_FOLD_FUSION3=0     the same for the 3x3 stride-1 layers
- *      MFVI_GRAD_FROM_SLAB=1   grad_finalize reads eps * softplus(rho) as W_k - mu from the sampled-weight slab instead of re-deriving eps
  *      MFVI_SIDE_STREAM=0      backward-weight kernels on the caller's stream (default: the plan's side stream; mfvi_plan_set_side_stream)
  *      MFVI_SIDE_MAXPIX=n      only layers with at most n output pixels fork onto the side stream
  *      MFVI_SIDE_PRIO=0        side stream at default priority (default: lowest)

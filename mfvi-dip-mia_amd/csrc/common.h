@@ -192,7 +192,10 @@ __device__ __forceinline__ void split_pair_bf16x3(float a0, float a1, unsigned& 
 __device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
 // softplus for the conv kernels' hot weight-sampling loops: hardware exp/log (v_exp_f32 / v_log_f32), with the
-// log1p series where 1 + e would lose e's low bits.  Relative error < 3e-6 (tests/test_gpu_parity.py).
+// log1p series where 1 + e would lose e's low bits.  Relative error < 3e-6 for rho in [-30, 20] (exactly rho above 20) and < |rho| 2^-23
+// on [-87, -30), where the rounding of the argument rho * log2(e) of v_exp_f32 grows with |rho|; below -87 the result is a denormal or +0.
+// tests/test_gpu_posterior_range.py::test_draw_weight_by_weight measures it weight by weight over that range on every forward kernel
+// family (the measured maxima per band: profiles/posterior_range_margins.txt).
 __device__ __forceinline__ float softplus_fast(float x)
 {
     if (x > 20.f) return x;
@@ -495,7 +498,6 @@ int launch_sample_weights(const SampleEntry* table_dev, int n_entries, int n_blo
 int launch_expand_bf16(const void* src, long long n, float* dst, hipStream_t st);
 constexpr int SAMPLE_QUADS = 256;       // weight quads per block of the sampling kernel
 struct GradFinEntry { long long w_off, b_off, part_off, stride; int n_w, n_b, strips, layer_id, first_block, pad; };
-// wsamp (optional): the sampled-weight slab of this pass, sample k at wsamp + k*wstride; then eps_k*softplus(rho) is read as W_k - mu
 struct BnGradEntry { long long bsums_off; long long bn_off; int C; int hw; };      // hw = H * W of the normalised tensor
 // BatchNorm parameter gradients of ONE table entry from the accumulated BN-backward sums: d gamma = sum ga * xhat, d beta = sum ga
 // (a block's worth of work: bn_param_grads_kernel, or an extra block of grad_finalize_kernel)
@@ -514,7 +516,7 @@ __device__ __forceinline__ void bn_param_grads_entry(const BnGradEntry e, const 
 }
 // bn_table / n_bn / bsums_base / dbn (optional): the BatchNorm parameter gradients as n_bn extra blocks of the same launch
 int launch_grad_finalize(const GradFinEntry* table_dev, int n_entries, int n_blocks, const float* part_base, const void* rho, RngKey key,
-                         int sample_weights, int n_samples, float* dmu, float* drho, const float* wsamp, long long wstride, const void* mu,
+                         int sample_weights, int n_samples, float* dmu, float* drho,
                          hipStream_t st, int bf16 = 0, const BnGradEntry* bn_table = nullptr, int n_bn = 0, const double* bsums_base = nullptr, float* dbn = nullptr,
                          int fit_s = 0, long long param_fstride = 0, long long grad_fstride = 0);      // fits mode: one grid row per fit
 constexpr int GRAD_FIN_QUADS = 64;      // weight quads per block of the finalize kernel

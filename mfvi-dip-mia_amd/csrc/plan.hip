@@ -24,8 +24,7 @@ const PlanSwitches& switches()
     static const PlanSwitches s = [] {
         auto on = [](const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); };      // default on, "0..." switches off
         auto num = [](const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; };
-        const char* slab = getenv("MFVI_GRAD_FROM_SLAB");
-        return PlanSwitches{on("MFVI_FOLD_FUSION"), on("MFVI_FOLD_FUSION3"), slab && slab[0] == '1', num("MFVI_FWD_FORK", 16384), on("MFVI_FORK_ON_PACKET"),
+        return PlanSwitches{on("MFVI_FOLD_FUSION"), on("MFVI_FOLD_FUSION3"), num("MFVI_FWD_FORK", 16384), on("MFVI_FORK_ON_PACKET"),
                             on("MFVI_SIDE_STREAM"), num("MFVI_SIDE_MAXPIX", 1LL << 40), on("MFVI_SIDE_PRIO"), on("MFVI_FUSE_SKIP_BWD")};
     }();
     return s;

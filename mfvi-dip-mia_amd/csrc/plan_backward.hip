@@ -121,9 +121,7 @@ int finalize_grads(Backward& B, hipStream_t fs, int slot, bool with_bn = false)
     if (!T.holds(fin) && getenv("MFVI_DEBUG_FIN")) for (auto& e : fin) fprintf(stderr, "fin layer %d n_w %d strips %d first_block %d\n", e.layer_id, e.n_w, e.strips, e.first_block);
     const hipError_t e = T.upload_if_changed(fin, plan->n_conv, fs);
     if (e != hipSuccess) { set_error("backward: gradient table upload failed: %s", hipGetErrorString(e)); return (int)e; }
-    // every layer of `fin` (MFMA backward-weight) is also in the sampling table (same shape conditions), so its W_k sit in the slab
-    const int rc = launch_grad_finalize(T.dev, (int)fin.size(), fin_blocks, S.c.farena(), S.rho_v, S.key, S.sample_weights, S.n_samples, B.dmu, B.drho,
-                                        S.presample && S.sample_weights && switches().grad_from_slab ? S.c.wsamp() : nullptr, plan->n_vi, S.mu_v, fs, S.bf16,
+    const int rc = launch_grad_finalize(T.dev, (int)fin.size(), fin_blocks, S.c.farena(), S.rho_v, S.key, S.sample_weights, S.n_samples, B.dmu, B.drho, fs, S.bf16,
                                         with_bn ? plan->table_dev : nullptr, with_bn ? plan->n_entries : 0, S.c.bsums(), B.dbn, plan->fit_s, plan->fit_pstride,
                                         plan->fit_gstride);
     if (rc) { set_error("backward: grad_finalize launch failed: %s", hipGetErrorString((hipError_t)rc)); return rc; }

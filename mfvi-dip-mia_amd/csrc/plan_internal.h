@@ -155,10 +155,6 @@ struct PlanSwitches {
     bool fold_fusion;
     // MFVI_FOLD_FUSION3=0: 3x3 stride-1 backward-data keeps the padded-gradient scratch + finalize_dx (A/B and parity cross-checks)
     bool fold_fusion3;
-    // MFVI_GRAD_FROM_SLAB=1: grad_finalize reads eps * softplus(rho) as W_k - mu from the sampled-weight slab instead of re-deriving eps
-    // from the counter RNG.  Measured slower on MI355X (87 vs 72 us: the extra 66 MB of loads cost more than the Philox work they save),
-    // kept as an A/B switch.
-    bool grad_from_slab;
     // MFVI_FWD_FORK: a skip-branch convolution (its only consumer is a later concat) on a map of up to this many pixels (default 128 x 128;
     // 0 = never) runs on the plan's side stream beside the down path of its scale and is joined in front of that concat: at those sizes both
     // are latency-bound launches that leave most of the chip idle (with the events on the kernels' packets: 3.306 ms per iteration without,

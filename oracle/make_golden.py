@@ -145,14 +145,16 @@ SR = dict(temp=4.381719802264805e-07, sigma=4.9e-08)                   # test_co
 CT = dict(temp=2.2e-10, sigma=1.7e-7)                                  # test_configs/mfvi_ct.json
 
 
-def golden_net(name, onet, seed, K, task="den", full_arrays=True, dtype=torch.float32, save=True, compact=False, bf16=False):
-    """compact: the float64 twin's output and the eval-mode output are stored strided (the 256^2 fixtures stay small).
+def golden_net(name, onet, seed, K, task="den", full_arrays=True, dtype=torch.float32, save=True, compact=False, bf16=False, params=None, with_kl=True):
+    """params: (mu, rho, bn) float32 blocks in the flat layout instead of test_params(onet, seed); with_kl=False leaves temp * kl out of the
+    backward pass (the data term's gradients alone: at rho = -200 the KL gradient is of the order 1 / softplus(rho)^3).
+    compact: the float64 twin's output and the eval-mode output are stored strided (the 256^2 fixtures stay small).
     bf16: mu / rho are rounded to bfloat16 (round-to-nearest-even, O.bf16_round == torch's .bfloat16().float()) before they are loaded
     into the reference's MeanFieldVI — the values a bf16 parameter store holds (BASELINE configs[4])."""
     cfg = dict(den=DEN, sr=SR, ct=CT)[task]
     temp = cfg["temp"]; prior_raw = float(np.sqrt(temp) * cfg["sigma"])
     conv, bn, n_vi, n_bnp = O.net_table(onet)
-    mu, rho, bnp = test_params(onet, seed)
+    mu, rho, bnp = test_params(onet, seed) if params is None else params
     if bf16:
         assert np.array_equal(O.bf16_round(mu), torch.from_numpy(mu).bfloat16().float().numpy())
         mu, rho = O.bf16_round(mu), O.bf16_round(rho)
@@ -192,7 +194,8 @@ def golden_net(name, onet, seed, K, task="den", full_arrays=True, dtype=torch.fl
             nll_sum += float(nll) / K
             outs.append(out.detach().numpy()[0].copy())
         kl = net.kl()
-        (temp * kl).backward()
+        if with_kl:
+            (temp * kl).backward()
     per_layer_kl = np.array([float(m._kl) for m in layers], np.float64)
     dmu, drho, dbn = flat_grads(net, conv, bn, n_vi, n_bnp)
     res.update(dict(seed=seed, K=K, step=3, temp=temp, prior_sigma=np.float32(prior_raw + 1e-6), H=H, W=W,
@@ -225,6 +228,29 @@ def golden_net(name, onet, seed, K, task="den", full_arrays=True, dtype=torch.fl
             res["out"] = res["out"].astype(np.float32)
     np.savez_compressed(os.path.join(GOLD, name + ".npz"), **res)
     print(name, "nll", nll_sum, "kl", float(kl), "out", res["out"].shape, "|dmu|", np.linalg.norm(dmu), "|drho|", np.linalg.norm(drho))
+
+
+def golden_posterior():
+    """The reference's own MeanFieldVI autograd in float64 away from the initial posterior: three_scale_32, den data
+    term, K = 2, at the `fitted` and `pruned` layouts of tests/posterior_cases.py (rho ~ -13.8; a quarter of the weights at rho = -200,
+    mu = 0).  Pins the float64 statement of tests/posterior_cases.py to the reference, not to this project's reading of it."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import posterior_cases as PC
+    from mfvi_dip_mia_amd.program import skip_program            # pure-Python layer program (offsets of the flat layout)
+    kw = PC.NETS["three_scale_32"]
+    onet = O.make_net(**kw)
+    P, _, _, _ = skip_program(**kw)
+    seed, K = PC.NET_SEEDS[("three_scale_32", "fitted")], 2
+    assert PC.NET_SEEDS[("three_scale_32", "pruned")] == seed
+    res = dict(seed=np.int64(seed), K=np.int64(K), step=np.int64(3))
+    for lay in ("fitted", "pruned"):
+        mu, rho, bnp = PC.net_params(P, lay, seed)
+        r = golden_net("posterior_" + lay, onet, seed, K, task="den", dtype=torch.float64, save=False, params=(mu, rho, bnp), with_kl=False)
+        assert int(r["step"]) == 3
+        res.update({lay + "_out": r["out"].astype(np.float32), lay + "_nll": np.float64(r["nll"]), lay + "_mu": mu, lay + "_rho": rho,
+                    lay + "_dmu": r["dmu"].astype(np.float32), lay + "_drho": r["drho"].astype(np.float32), lay + "_dbn": r["dbn"].astype(np.float32)})
+        print("posterior", lay, "nll", r["nll"], "|dmu|", np.linalg.norm(r["dmu"]), "|drho|", np.linalg.norm(r["drho"]))
+    np.savez_compressed(os.path.join(GOLD, "posterior_range.npz"), **res)
 
 
 def golden_traj(name, onet, seed, K, steps, lr=1e-3):
@@ -773,6 +799,8 @@ if __name__ == "__main__":
         sys.exit(0)
     if "--lrt" in sys.argv:
         golden_lrt(); sys.exit(0)
+    if "--posterior" in sys.argv:
+        golden_posterior(); sys.exit(0)
     if "--crop" in sys.argv:            # sides not divisible by 2^n_scales: Concat's centre-crop (models/common.py:29-41) at the deepest scale, both dims
         golden_net("crop_den_36x44_k1", O.make_net(36, 44, input_depth=8, n_out=2, nd=(8, 16, 16), nu=(8, 16, 16), ns=(4, 4, 4)), seed=31, K=1, task="den",
                    full_arrays=True)
@@ -804,3 +832,4 @@ if __name__ == "__main__":
     golden_inp_dip_loss()
     golden_bookkeeping()
     golden_lrt()
+    golden_posterior()

@@ -190,6 +190,34 @@ def test_net_elbo_grad(golden_dir, name):
         assert relerr(_strided(out_eval, 16384), g["out_eval_s"]) < RTOL
 
 
+@pytest.mark.parametrize("lay", ["fitted", "pruned"])
+def test_net_grad_away_from_the_initial_posterior(golden_dir, lay):
+    """tests/golden/posterior_range.npz (oracle/make_golden.py, golden_posterior): the reference's float64 autograd on three_scale_32 at a
+    fitted (rho ~ -13.8) and a pruned (a quarter of the weights at rho = -200, mu = 0) posterior, data term only -- at small_den_k2's
+    tolerances, and drho once more through q = drho / sigmoid(rho) per layer (tests/posterior_cases.py), which the fitted weights do not
+    hide behind the few largest entries."""
+    import posterior_cases as PC
+    import mfvi_dip_mia_amd as M
+    g = load(golden_dir, "posterior_range")
+    kw = PC.NETS["three_scale_32"]
+    net = O.make_net(**kw)
+    seed, K, step = int(g["seed"]), int(g["K"]), int(g["step"])
+    P, zin, out_id, _ = M.skip_program(**kw)
+    mu, rho, bnp = PC.net_params(P, lay, seed)
+    assert np.array_equal(mu, g[lay + "_mu"]) and np.array_equal(rho, g[lay + "_rho"])          # the layout is the one the reference ran
+    z = PC.net_input(kw, seed)
+    tgt = O.noisy(O.phantom(net.H, net.W, seed), 0.1, seed)
+    r = O.elbo_grad(net, mu, rho, bnp, z, tgt, task=0, seed=seed, step=step, K=K, with_kl=False, want_out=True)
+    assert relerr(r["out"], g[lay + "_out"]) < RTOL
+    assert abs(r["nll"] - float(g[lay + "_nll"])) < 3e-5 * abs(float(g[lay + "_nll"]))
+    assert relerr(r["dmu"], g[lay + "_dmu"]) < 5e-5 and relerr(r["drho"], g[lay + "_drho"]) < 5e-5 and relerr(r["dbn"], g[lay + "_dbn"]) < 5e-5
+    worst, rows = PC.layer_q_err(r["drho"], PC.q_of(g[lay + "_drho"], rho), rho, P.layers)
+    assert worst < 5e-5, rows
+    pruned = rho == np.float32(PC.PRUNED_RHO)
+    assert pruned.any() == (lay == "pruned") and np.all(np.abs(g[lay + "_drho"][pruned]) < 1e-30) and np.all(np.abs(r["drho"][pruned]) < 1e-30)
+    assert np.isfinite(g[lay + "_drho"]).all()
+
+
 @pytest.mark.parametrize("name", ["traj_small_k1", "traj_small_k2"])
 def test_trajectory(golden_dir, name):
     """N steps of the loop bayesian_optimization.py:1360-1372 (torch AdamW in the golden run)."""
